@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- BWT+MTF+RLE encode throughput on synthetic ACGTN records.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up (record generation, the workspace placement below), runs W warm-up and K timed steps,
+writes the last step's outputs if --dump-outputs is given (see dump_outputs) and prints the line; its
+`stages_ms` and `roofline` come from the library's counters of those steps.  --full adds, after that, every
+other measurement and check: at N = 1 the `container`, `host_path`, `fm_count`, `classes` and `cpu_baseline`
+legs (the --no-* options drop single ones), at N > 1 the decode of every gathered container on rank 0.
 
 With N > 1 and no WORLD_SIZE in the environment the command launches itself: the parent (which never
 touches the GPU) starts N fresh ranks through torch.distributed.run on 127.0.0.1, forwards rank 0's
@@ -12,8 +18,8 @@ HBM.  N = 1: tc_encode_dev (the runs as arrays: BASELINE configs[2]).  N > 1: ea
 independent record (seed 0xC500 + rank) and encodes it straight into its container
 (tc_encode_container_dev: the RLE stage writes the wire format, nothing is packed afterwards), and the step
 ends with the gather of the containers on rank 0 over RCCL, overlapped with the next record's encode.
-Rank 0 prints ONE JSON line.  After the timed region, at N = 1, the line also gets `container` (the N > 1
-step without its exchange, timed on this one GPU) and `fm_count` (BASELINE configs[3]).
+Rank 0 prints ONE JSON line.  With --full, after the timed region, at N = 1, the line also gets `container`
+(the N > 1 step without its exchange, timed on this one GPU) and `fm_count` (BASELINE configs[3]).
 
 PyTorch here is plumbing only: device buffers, torch.distributed (nccl = RCCL),
 barriers.  The compute is libtextcomp.so through its C ABI.
@@ -37,12 +43,23 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--n", "--record-bytes", dest="n", type=int, default=GIB, help="record size in bytes (default 1 GiB = BASELINE configs[2])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fm", action="store_true", help="skip the FM-index count leg (BASELINE configs[3])")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the host-pointer leg (tc_encode_container, pageable and page-locked buffers)")
-    ap.add_argument("--no-classes", action="store_true", help="skip the input-classes leg (non-iid records at 2^28 bytes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the extra legs (container, host path, FM count, input classes, CPU "
+                         "baseline) and, at N > 1, decode and check every gathered container; off: the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float64; long arrays as a "
+                         "fixed, seeded sample plus slice sums)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fm", action="store_true", help="with --full: skip the FM-index count leg (BASELINE configs[3])")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: skip the host-pointer leg (tc_encode_container, pageable and page-locked buffers)")
+    ap.add_argument("--no-classes", action="store_true", help="with --full: skip the input-classes leg (non-iid records at 2^28 bytes)")
     ap.add_argument("--cpu-sample", type=int, default=64 << 20, help="bytes of the workload timed on the CPU port")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs:
+        a.dump_outputs = os.path.abspath(a.dump_outputs)
+    return a
 
 
 def algorithmic_bytes(st, n):
@@ -115,6 +132,7 @@ def self_launch(a):
                # (rebuilt from the parsed values: torchrun's own parser chokes on abbreviations such as --n)
                "--gpus", str(a.gpus), "--steps", str(a.steps), "--warmup", str(a.warmup), "--record-bytes", str(a.n),
                "--cpu-sample", str(a.cpu_sample)] + (["--no-cpu-baseline"] if a.no_cpu_baseline else []) + (["--no-fm"] if a.no_fm else []) + (["--no-classes"] if a.no_classes else []) + (["--no-host-path"] if a.no_host_path else [])
+        cmd += (["--full"] if a.full else []) + (["--dump-outputs", a.dump_outputs] if a.dump_outputs else [])
         if os.environ.get("TC_BENCH_CHILD_CMD"):      # test hook (CPU suite): the parent's deadline / fallback logic around any child
             import shlex
             cmd = shlex.split(os.environ["TC_BENCH_CHILD_CMD"])
@@ -409,6 +427,49 @@ def fm_count_leg(ctx, lib, torch, no_cpu):
     return res
 
 
+DUMP_BUDGET = 48 << 20      # bytes of sampled arrays --dump-outputs writes at most (all files stay under 64 MB)
+DUMP_SLICES = 4096
+
+
+def dump_outputs(torch, out_dir, scalars, arrays):
+    """--dump-outputs: what the timed path handed its caller in its last step, as float64 .npy files in `out_dir`, so
+    that two builds can be compared output for output.  `scalars`: name -> number or list, written whole.  `arrays`:
+    name -> 1-D integer tensor (any device).  An array of at most S elements is written whole (<name>.npy); a longer
+    one as the values at S positions drawn by a generator seeded from its name (<name>_index.npy, <name>_sample.npy)
+    and, so that every element counts, the sums of its DUMP_SLICES equal slices, plain and weighted by position
+    (<name>_slice_sums.npy, DUMP_SLICES x 2; exact in int64 on the device).  S keeps the files within DUMP_BUDGET."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in scalars.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, dtype=np.float64).reshape(-1))
+    S = min(1 << 18, DUMP_BUDGET // (16 * max(1, len(arrays))))
+    for name, t in arrays.items():
+        m = t.numel()
+        if m <= S:
+            np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float64))
+            continue
+        rng = np.random.default_rng(zlib.crc32(name.encode()))
+        idx = np.unique(rng.integers(0, m, S, dtype=np.int64))
+        vals = t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+        np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, name + "_sample.npy"), vals.astype(np.float64))
+        B = -(-m // DUMP_SLICES)        # elements per slice (the last one zero-padded)
+        G = 64                          # slices per chunk on the device
+        sums = np.zeros((DUMP_SLICES, 2), np.float64)
+        for g in range(0, DUMP_SLICES, G):
+            lo, hi = g * B, min(m, (g + G) * B)
+            if lo >= hi:
+                break
+            seg = torch.zeros(G * B, dtype=torch.int64, device=t.device)
+            seg[:hi - lo] = t[lo:hi]
+            w = torch.arange(lo, lo + G * B, dtype=torch.int64, device=t.device) % 65521 + 1
+            seg = seg.view(G, B)
+            sums[g:g + G, 0] = seg.sum(1).cpu().numpy()
+            sums[g:g + G, 1] = (seg * w.view(G, B)).sum(1).cpu().numpy()
+        np.save(os.path.join(out_dir, name + "_slice_sums.npy"), sums)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -548,11 +609,15 @@ def main():
 
     gathered = None
     if rank == 0 and gatherer is not None:
-        # outside the timed region: EVERY container gathered for the last record is read back on rank 0 --
-        # header, checksum, unpack, full decode -- and compared with the record its rank encoded
-        # (regenerated here from the rank's seed): what arrived over RCCL is the right block of bytes.
         last = gatherer.completed[-1]
         assert len(last) == world and all(int(h[0]) == len(p) for h, p in last), "gather shape"
+        if a.dump_outputs:      # what rank 0 received in the last step: every rank's container
+            dump_outputs(torch, a.dump_outputs, {"container_bytes": [int(h[0]) for h, _ in last]},
+                         {"container_rank%d" % r: p for r, (_, p) in enumerate(last)})
+    if rank == 0 and gatherer is not None and a.full:
+        # --full, outside the timed region: EVERY container gathered for the last record is read back on rank 0 --
+        # header, checksum, unpack, full decode -- and compared with the record its rank encoded
+        # (regenerated here from the rank's seed): what arrived over RCCL is the right block of bytes.
         d_chk = torch.empty(n, dtype=torch.uint8, device=dev)
         d_back = torch.empty(n, dtype=torch.uint8, device=dev)
         vb = Block()
@@ -570,6 +635,8 @@ def main():
             assert lib.tc_generate_dev(ctx.handle, 0, 0xC500 + r, n, C.c_void_p(d_chk.data_ptr())) == 0
             torch.cuda.synchronize()
             assert torch.equal(d_back, d_chk), "record of rank %d does not decode to its text" % r
+        del d_chk, d_back
+    if rank == 0 and gatherer is not None:
         wm = list(gatherer.wait_ms)
         gathered = {"path": "native" if isinstance(gatherer, NativeGather) else "torch",
                     "fallback_reason": os.environ.get("TC_BENCH_FALLBACK_REASON"),
@@ -579,11 +646,17 @@ def main():
                                          "calls": len(wm), "last": [round(x, 3) for x in wm[-4:]]},
                     "ranks_in_communicator": dist.get_world_size(),
                     "backend": "tc_comm (RCCL behind the C ABI)" if isinstance(gatherer, NativeGather) else dist.get_backend(),
-                    "containers_verified": world, "container_bytes": [int(h[0]) for h, _ in last],
+                    "containers_verified": world if a.full else 0, "container_bytes": [int(h[0]) for h, _ in last],
                     "comm_cus": getattr(gatherer, "comm_cus", 0)}
-        del d_chk, d_back
     if rank == 0:
         st = ctx.stats()
+        if a.dump_outputs and gatherer is None:
+            # what tc_encode_dev returned in the last timed step: the block's header fields and its two run arrays
+            nr = int(blk.nruns)
+            dump_outputs(torch, a.dump_outputs,
+                         {"primary": int(blk.primary), "sigma": int(blk.sigma), "nruns": nr,
+                          "final_list": [int(blk.final_list[i]) for i in range(int(blk.sigma))]},
+                         {"run_count": d_cnt[:nr], "run_value": d_val[:nr]})
         total_bytes = n * world * a.steps
         value = total_bytes / dt / 1e6
         A = algorithmic_bytes(st, n)
@@ -639,29 +712,30 @@ def main():
                           "passes": [int(st.passes[i]) for i in range(st.rounds)], "runs": int(st.runs),
                           "ticket_fallbacks": int(st.ticket_fallbacks)},
         }
-        # the extra legs never take the headline with them: a failure is reported in their place
-        if world == 1 and os.environ.get("TC_BENCH_CONTAINER", "1") != "0":
+        # --full: the extra legs, after the headline's outputs are written.  They never take the headline with them:
+        # a failure is reported in their place
+        if a.full and world == 1 and os.environ.get("TC_BENCH_CONTAINER", "1") != "0":
             try:
                 out["container"] = container_leg(ctx, lib, torch, d_text, n, a.steps, out["ms_per_step"])
             except Exception as e:   # noqa: BLE001
                 out["container"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not a.no_host_path and n >= (1 << 24):
+        if a.full and world == 1 and not a.no_host_path and n >= (1 << 24):
             try:
                 out["host_path"] = host_path_leg(ctx, lib, torch, d_text, n, out["ms_per_step"])
             except Exception as e:   # noqa: BLE001
                 out["host_path"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not a.no_fm and n == GIB:
+        if a.full and world == 1 and not a.no_fm and n == GIB:
             del d_cnt, d_val
             try:
                 out["fm_count"] = fm_count_leg(ctx, lib, torch, a.no_cpu_baseline)
             except Exception as e:   # noqa: BLE001
                 out["fm_count"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not a.no_classes and n == GIB:
+        if a.full and world == 1 and not a.no_classes and n == GIB:
             try:
                 out["classes"] = classes_leg(ctx, lib, torch)
             except Exception as e:   # noqa: BLE001
                 out["classes"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if not a.no_cpu_baseline and world == 1:   # the CPU port is timed at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:   # the CPU port is timed at N = 1 only
             try:
                 out["cpu_baseline"] = cpu_baseline(min(a.cpu_sample, n), seed)
             except Exception as e:   # noqa: BLE001

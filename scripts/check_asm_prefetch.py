@@ -14,6 +14,7 @@ tests/test_asm_prefetch_registers.py for the default build and the diagnostic va
 import os
 import re
 import subprocess
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "text-compression_amd")
@@ -35,12 +36,13 @@ def check(defs=()):
     checked, raises AssertionError with the offending instruction otherwise"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     tag = "_".join(d.strip("-").replace("=", "") for d in defs) or "default"
-    isa = "/tmp/textcomp_isa_%s.s" % tag
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                          "-I" + os.path.join(PKG, "csrc"), "-S", "--cuda-device-only", "-o", isa] + list(defs) +
-                         [os.path.join(PKG, "csrc", "textcomp.hip")], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    lines = open(isa).read().split("\n")
+    with tempfile.TemporaryDirectory() as d:
+        isa = os.path.join(d, "textcomp_isa_%s.s" % tag)
+        out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
+                              "-I" + os.path.join(PKG, "csrc"), "-S", "--cuda-device-only", "-o", isa] + list(defs) +
+                             [os.path.join(PKG, "csrc", "textcomp.hip")], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = open(isa).read().split("\n")
     checked = 0
     for frag in KERNELS:
         start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and frag in l and l.rstrip().endswith(":") or (l.startswith("_Z") and frag in l and ":" in l.split(";")[0]))

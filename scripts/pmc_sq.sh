@@ -1,4 +1,6 @@
 #!/bin/bash
+# SQ / GRBM counters of the encode kernels in a plain bench run (the encode step only: the kernels filtered below are
+# all of it; the extra legs' kernels would need --full)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 N=${1:-268435456}
 i=0

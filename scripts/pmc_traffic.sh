@@ -4,22 +4,26 @@
 # scripts/pmc_calib.sh on 4/8/16-byte-per-lane streams), WRITE_SIZE is exact.  Units: KB.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 N=${1:-1073741824}
+export OUT=${OUT:-pmc_out}   # raw counters, logs and traffic_latest.json
+mkdir -p "$OUT"
 export TC_BENCH_PLACE=0   # (one placement: the counters are per launch, the mode does not change the bytes)
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf gpurun_out/pmc_$c
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d gpurun_out/pmc_$c -- python bench.py --n $N --steps 1 --warmup 1 --no-cpu-baseline > gpurun_out/pmc_$c.log 2>&1
+  rm -rf "$OUT/pmc_$c"
+  # --full: the FM-count and container legs launch fm_count_kernel and rle_nib_kernel, read below
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/pmc_$c" -- python bench.py --n $N --steps 1 --warmup 1 --full --no-cpu-baseline > "$OUT/pmc_$c.log" 2>&1
 done
 # the whole step by the counters: ONE encode call and nothing else in the process (no warm-up, no extra legs)
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf gpurun_out/pmcstep_$c
-  TC_BENCH_CONTAINER=0 rocprofv3 --pmc $c --kernel-trace --output-format csv -d gpurun_out/pmcstep_$c -- python bench.py --n $N --steps 1 --warmup 0 --no-cpu-baseline --no-fm --no-classes --no-host-path > gpurun_out/pmcstep_$c.log 2>&1
+  rm -rf "$OUT/pmcstep_$c"
+  TC_BENCH_CONTAINER=0 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OUT/pmcstep_$c" -- python bench.py --n $N --steps 1 --warmup 0 --no-cpu-baseline --no-fm --no-classes --no-host-path > "$OUT/pmcstep_$c.log" 2>&1
 done
 python - <<'PY'
-import csv,glob,collections,json
+import csv,glob,collections,json,os
+OUT=os.environ["OUT"]
 N=1073741824
 tot=collections.defaultdict(lambda: {"FETCH_SIZE":[], "WRITE_SIZE":[]})
 for c in ("FETCH_SIZE","WRITE_SIZE"):
-    f=glob.glob("gpurun_out/pmc_%s/*/*counter_collection.csv"%c)[0]
+    f=glob.glob(OUT+"/pmc_%s/*/*counter_collection.csv"%c)[0]
     for r in csv.DictReader(open(f)):
         tot[r["Kernel_Name"].split("(")[0][:60]][c].append(float(r["Counter_Value"])*1024)
 out={}
@@ -52,7 +56,7 @@ for k,d in tot.items():
 # one encode step: every dispatch of the one-call run except the generator (and anything of torch's)
 step=collections.defaultdict(float); nd=collections.Counter()
 for c,mul in (("FETCH_SIZE",2.0),("WRITE_SIZE",1.0)):
-    fs=glob.glob("gpurun_out/pmcstep_%s/*/*counter_collection.csv"%c)
+    fs=glob.glob(OUT+"/pmcstep_%s/*/*counter_collection.csv"%c)
     for r in (csv.DictReader(open(fs[0])) if fs else []):
         k=r["Kernel_Name"].split("(")[0][:60]
         if "generate" in k or "at::" in k or "elementwise" in k: continue
@@ -63,5 +67,5 @@ if step:
     res["step_traffic_by_kernel"]={k:{"bytes":v,"dispatches":nd[k]} for k,v in sorted(step.items(), key=lambda kv:-kv[1]) if v>=5e7}
     res["step_note"]="one tc_encode_dev call of the 1 GiB record alone in the process: sum over ALL its dispatches of 2*FETCH_SIZE + WRITE_SIZE"
     print("whole step: %.2f GB in %d dispatches"%(res["step_traffic_bytes"]/1e9, sum(nd.values())))
-json.dump(res, open("gpurun_out/traffic_latest.json","w"), indent=1)
+json.dump(res, open(OUT+"/traffic_latest.json","w"), indent=1)
 PY

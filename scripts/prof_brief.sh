@@ -1,5 +1,7 @@
 #!/bin/bash
 # rocprofv3 kernel-trace of the bench; prints per-kernel avg times; $1 = tag
+# (a plain bench run: the kernels of the encode steps only; give --full, forwarded with the other arguments, for the
+# container, host-path, FM-count and classes kernels -- profiles taken before --full existed have them mixed in)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=${1:-x}; shift
 rm -rf gpurun_out/prof_$TAG

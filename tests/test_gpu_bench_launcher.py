@@ -25,7 +25,7 @@ def _run(args, extra_env, timeout=600):
 
 @pytest.mark.gpu
 def test_bare_command_launches_two_ranks():
-    p = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--n", str(1 << 24)], {"TC_BENCH_REHEARSAL": "1"})
+    p = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--n", str(1 << 24), "--full"], {"TC_BENCH_REHEARSAL": "1"})
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -51,7 +51,7 @@ def test_stalled_first_exchange_falls_back_within_the_deadline():
     the conservative exchange, and the line says which path ran and why"""
     import time
     t0 = time.time()
-    p = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--n", str(1 << 22)],
+    p = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--n", str(1 << 22), "--full"],
              {"TC_BENCH_REHEARSAL": "1", "TC_BENCH_STALL_RANK": "1", "TC_BENCH_DEADLINE_S": "60"}, timeout=400)
     took = time.time() - t0
     assert p.returncode == 0, p.stderr[-4000:]

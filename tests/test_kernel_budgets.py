@@ -5,6 +5,7 @@ pins the budgets the measured numbers were taken with."""
 import os
 import re
 import subprocess
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "text-compression_amd")
@@ -39,10 +40,11 @@ BUDGETS = {
 
 def test_kernel_register_budgets():
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread",
-                          "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"),
-                          "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/libtextcomp_budget.so",
-                          os.path.join(PKG, "csrc", "textcomp.hip")], capture_output=True, text=True, timeout=600)
+    with tempfile.TemporaryDirectory() as d:
+        out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread",
+                              "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"),
+                              "-Rpass-analysis=kernel-resource-usage", "-o", os.path.join(d, "libtextcomp_budget.so"),
+                              os.path.join(PKG, "csrc", "textcomp.hip")], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     seen = {}
     for blk in out.stderr.split("Function Name: ")[1:]:
