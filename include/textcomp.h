@@ -21,7 +21,13 @@
  *     TC_ERR_MALFORMED marks inputs on which the reference itself throws
  *     (fromJust / DS.index / read).
  *   - one tc_ctx = one device + one HIP stream + one workspace; calls on one ctx
- *     are serialised by the caller, distinct ctxs are independent.
+ *     are serialised by the caller, distinct ctxs are independent: calls on
+ *     distinct ctxs may run at the same time from different threads, on one
+ *     device, and ctxs may be created and destroyed meanwhile
+ *     (tests/test_gpu_concurrency.py).  A tc_fm is read-only once built: count
+ *     and locate carve their scratch from the CALLING ctx's workspace, so any
+ *     number of ctxs on the index's device may query one tc_fm at the same
+ *     time; tc_fm_free must not overlap a query of that index.
  *   - `*_dev` entry points take DEVICE pointers for the bulk arrays (the
  *     benchmark path: inputs and outputs resident in HBM); scalar outputs are
  *     host words.  All calls return after the ctx stream has drained.

@@ -48,9 +48,16 @@ def _assert_digest(lib, ctx, d, blk, d_cnt, d_val, d_text):
     assert _checksum(lib, ctx, d_L, d_L.numel()) == d["last_column_checksum64"]
 
 
-@pytest.mark.parametrize("n", [1 << 20, 1 << 24])
+# round 0's way by size, default settings: the MSD way is considered from N = n + 1 = 2^27 suffixes on
+# (msd_min_n); these iid ACGTN records pass its sample and field checks, so the threshold alone decides
+MSD_PATH = {1 << 20: 0, 1 << 24: 0, (1 << 27) - 2: 0, (1 << 27) - 1: 1, (1 << 27) + 40961: 1}
+
+
+@pytest.mark.parametrize("n", [1 << 20, 1 << 24, (1 << 27) - 2, (1 << 27) - 1, (1 << 27) + 40961])
 def test_digest_matches_oracle_small(n):
-    """same digest machinery at sizes where tests/test_gpu_encode.py also compares element-wise"""
+    """same digest machinery at sizes where tests/test_gpu_encode.py also compares element-wise, and on
+    both sides of the MSD threshold: N = 2^27 - 1 (below), N = 2^27 (at it), N = 2^27 + 40962 (above it,
+    not a power of two) -- each by the way the threshold picks, with no selector set"""
     import torch
     import textcomp
     from textcomp import Block
@@ -65,6 +72,7 @@ def test_digest_matches_oracle_small(n):
     blk = Block()
     blk.nruns, blk.run_count, blk.run_value = cap, d_cnt.data_ptr(), d_val.data_ptr()
     assert lib.tc_encode_dev(ctx.handle, C.c_void_p(d_text.data_ptr()), n, C.byref(blk)) == 0
+    assert ctx.stats().msd_path == MSD_PATH[n]
     _assert_digest(lib, ctx, d, blk, d_cnt, d_val, d_text)
     ctx.close()
 

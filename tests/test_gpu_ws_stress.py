@@ -58,7 +58,8 @@ elif mode == "contexts":
             assert st.ws_chunks > 0
 elif mode == "cycle":
     # chunked workspaces of two sizes created and released 30 times (small records: TC_WS_VMM_MIN_LOG2 lowered),
-    # a second context alive all the while with work of its own in flight on its stream
+    # a second context alive all the while, used between them (each call drains its stream before it returns, so
+    # nothing of it is in flight during a release: contexts at work at the same time are tests/test_gpu_concurrency.py)
     with textcomp.Context(0) as other:
         for i in range(30):
             with textcomp.Context(0) as ctx:

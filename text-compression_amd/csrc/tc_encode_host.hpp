@@ -269,25 +269,41 @@ static void sa_choose_config(tc_ctx *ctx, const u32 *counts, u64 n, SaConfig &c)
 static void sa_run(tc_ctx *ctx, SaBuffers &b, const u8 *d_text, u64 n, u32 *d_sa, u8 *d_L,
                    u64 *primary, u32 *counts256_out);
 
+// The sharded tile tickets of round 0's radix passes (the only passes that draw them) assume blocks
+// start in roughly increasing blockIdx order.  If a bounded look-back spin ran out (bit 1 of the error
+// word), the scatter of that pass left slots unwritten, and a stale value in them is a suffix start that
+// finish_kernel, group_kernel or a later round's ISA scatter would use as an index.  So the flag is read
+// right after those passes, before anything consumes their output, and the attempt is abandoned:
+// sa_build runs the sort again with the single counter (every status, ticket and histogram word is
+// zeroed again where it is used, and SA / last column are written anew, as in any call on a reused
+// workspace).  TC_DBG_TICKET_TRIP=1 (tests): the first attempt's check finds the flag set -- only the
+// flag is simulated, the passes themselves ran normally.
+struct TicketTrip {};
+__global__ void err_or_kernel(u32 *err, u32 bits) { atomicOr(err, bits); }
+static void ticket_check(tc_ctx *ctx) {
+    if (env_int("TC_DBG_TICKET_TRIP", 0) != 0) {
+        err_or_kernel<<<1, 1, 0, ctx->stream>>>(ctx->d_err, 2u);
+        TC_LAUNCH_CHECK(ctx);
+    }
+    TC_HIP(ctx, hipMemcpyAsync(&ctx->h_scalars[62], ctx->d_err, sizeof(u32), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((u32)ctx->h_scalars[62] & 2u) throw TicketTrip{};
+}
+
 static void sa_build(tc_ctx *ctx, Arena &A, const u8 *d_text, u64 n, u32 *d_sa, u8 *d_L,
                      u64 *primary, u32 *counts256_out, bool dry) {
     const u64 N = n + 1;
     SaBuffers b;
     sa_carve(A, N, b, d_sa == nullptr);
     if (dry) return;
-    sa_run(ctx, b, d_text, n, d_sa, d_L, primary, counts256_out);
-    // The sharded tile tickets of the radix pass assume blocks start in roughly increasing
-    // blockIdx order; if a bounded look-back spin tripped, redo with the single counter.
-    if (!ctx->safe_tickets) {
-        TC_HIP(ctx, hipMemcpyAsync(&ctx->h_scalars[62], ctx->d_err, sizeof(u32), hipMemcpyDeviceToHost,
-                                   ctx->stream));
-        TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if ((u32)ctx->h_scalars[62] & 2u) {
-            tc_memset_async(ctx, ctx->d_err, 0, sizeof(u32));
-            ctx->safe_tickets = 1;
-            ctx->ticket_fallbacks++;
-            sa_run(ctx, b, d_text, n, d_sa, d_L, primary, counts256_out);
-        }
+    try {
+        sa_run(ctx, b, d_text, n, d_sa, d_L, primary, counts256_out);
+    } catch (const TicketTrip &) {
+        tc_memset_async(ctx, ctx->d_err, 0, sizeof(u32));
+        ctx->safe_tickets = 1;
+        ctx->ticket_fallbacks++;
+        sa_run(ctx, b, d_text, n, d_sa, d_L, primary, counts256_out);
     }
     ctx->stats.ticket_fallbacks = ctx->ticket_fallbacks;
 }
@@ -423,9 +439,10 @@ static void sa_run(tc_ctx *ctx, SaBuffers &b, const u8 *d_text, u64 n, u32 *d_sa
         rb.hist = b.hist;
         rb.status = b.rstatus; rb.status_cap = radix_status_words(N);
         ctx->pev_used = 0;
+        const bool xcd_group = !ctx->safe_tickets && env_int("TC_XCD_GROUP", 1) != 0;
         radix_sort_pairs(ctx, rb, (u32)N, plan, /*gen_idx=*/true, /*hist_ready=*/true, /*timed=*/true,
-                         d_text, fuse ? &kg : nullptr,
-                         /*xcd_group=*/!ctx->safe_tickets && env_int("TC_XCD_GROUP", 1) != 0);
+                         d_text, fuse ? &kg : nullptr, xcd_group);
+        if (xcd_group) ticket_check(ctx);   // (throws TicketTrip: nothing below reads a broken scatter)
     };
     const int rbits = ceil_log2_u64(N);
     int keybits = (int)(cfg.P * cfg.w);

@@ -828,7 +828,10 @@ int tc_encode_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, tc_block *out)
     if (!out || n > TC_MAX_N) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
     const u64 cap = out->nruns;
     out->n = n; out->primary = 0; out->sigma = 0; out->nruns = 0;
-    if (n == 0) return TC_OK;  // empty in, empty out (BWT.hs:58, MTF.hs:157, RLE.hs:119)
+    if (n == 0) {              // empty in, empty out (BWT.hs:58, MTF.hs:157, RLE.hs:119)
+        ctx->stats = tc_stats{};   // (the stats describe this call alone: encode_device resets them otherwise)
+        return TC_OK;
+    }
     if (!d_text || !out->run_count || !out->run_value) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
     encode_device(ctx, d_text, n, out, cap);
     TC_API_END(ctx)
@@ -853,22 +856,7 @@ struct HostPipe {
     u8 *d_buf[4] = {};        // persistent device buffers: 0 text / container in, 1 container / text out, 2 run counts, 3 run values
     size_t d_cap[4] = {};
 };
-static HostPipe *hp_get(tc_ctx *ctx) {
-    if (ctx->hostpipe) return static_cast<HostPipe *>(ctx->hostpipe);
-    HostPipe *hp = new HostPipe();
-    ctx->hostpipe = hp;
-    for (int w = 0; w < HP_WORKERS; w++) {
-        TC_HIP(ctx, hipStreamCreateWithFlags(&hp->st[w], hipStreamNonBlocking));
-        for (int q = 0; q < 2; q++) {
-            TC_HIP(ctx, hipHostMalloc((void **)&hp->pin[w][q], HP_CHUNK, hipHostMallocDefault));
-            TC_HIP(ctx, hipEventCreateWithFlags(&hp->ev[w][q], hipEventDisableTiming));
-        }
-    }
-    return hp;
-}
-static void hp_release(tc_ctx *ctx) {
-    HostPipe *hp = static_cast<HostPipe *>(ctx->hostpipe);
-    if (!hp) return;
+static void hp_destroy(HostPipe *hp) {
     for (int w = 0; w < HP_WORKERS; w++) {
         if (hp->st[w]) (void)hipStreamSynchronize(hp->st[w]);
         for (int q = 0; q < 2; q++) {
@@ -880,6 +868,31 @@ static void hp_release(tc_ctx *ctx) {
     for (int i = 0; i < 4; i++)
         if (hp->d_buf[i]) (void)hipFree(hp->d_buf[i]);
     delete hp;
+}
+static HostPipe *hp_get(tc_ctx *ctx) {
+    if (ctx->hostpipe) return static_cast<HostPipe *>(ctx->hostpipe);
+    // attached only once complete: a failed allocation leaves the context without a pipe (the next
+    // call builds one again), never with a half-built one whose null streams and buffers get used
+    HostPipe *hp = new HostPipe();
+    try {
+        for (int w = 0; w < HP_WORKERS; w++) {
+            TC_HIP(ctx, hipStreamCreateWithFlags(&hp->st[w], hipStreamNonBlocking));
+            for (int q = 0; q < 2; q++) {
+                TC_HIP(ctx, hipHostMalloc((void **)&hp->pin[w][q], HP_CHUNK, hipHostMallocDefault));
+                TC_HIP(ctx, hipEventCreateWithFlags(&hp->ev[w][q], hipEventDisableTiming));
+            }
+        }
+    } catch (...) {
+        hp_destroy(hp);
+        throw;
+    }
+    ctx->hostpipe = hp;
+    return hp;
+}
+static void hp_release(tc_ctx *ctx) {
+    HostPipe *hp = static_cast<HostPipe *>(ctx->hostpipe);
+    if (!hp) return;
+    hp_destroy(hp);
     ctx->hostpipe = nullptr;
 }
 // persistent device buffer `which` of at least `bytes` (kept across calls; a longer request replaces it)
@@ -983,7 +996,10 @@ int tc_encode(tc_ctx *ctx, const uint8_t *text, uint64_t n, tc_block *out) {
     u32 *h_count = out->run_count;
     u16 *h_value = out->run_value;
     out->n = n; out->primary = 0; out->sigma = 0; out->nruns = 0;
-    if (n == 0) return TC_OK;
+    if (n == 0) {
+        ctx->stats = tc_stats{};   // (the stats describe this call alone: encode_device resets them otherwise)
+        return TC_OK;
+    }
     if (!text || !h_count || !h_value) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
     // the device-side buffers live outside the workspace (the pipeline re-carves it) and stay with the context
     u8 *d_text = hp_dev(ctx, 0, n + 16);
