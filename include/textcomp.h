@@ -234,6 +234,53 @@ int tc_block_unpack_dev(tc_ctx *ctx, const uint8_t *d_packed, uint64_t packed_by
  * tc_container_bound is always enough).  Reading verifies magic, sizes and the checksum
  * (TC_ERR_MALFORMED). */
 #define TC_CONTAINER_HEADER 640
+/* ---- entropy-coded container bodies (an addition to the reference's surface, as the container is) ----
+ * What a context's container WRITERS (tc_block_to_container_dev, tc_encode_container_dev, tc_encode_container,
+ * tc_encode_stream) put behind the header: TC_CODING_PACKED, the fixed-width packings above (run format id 0..2 =
+ * nibble stream / one byte / two bytes per run; the default, and the bytes of every earlier version), or
+ * TC_CODING_HUFFMAN, run format id 3, described below.  The setting is state of the context like
+ * tc_ctx_set_profile: it survives calls and failed calls; contexts hold it independently; a fresh context is
+ * TC_CODING_PACKED.  READERS never look at it: they go by the header's format id, so a stream may mix codings
+ * record by record.  Never larger: with TC_CODING_HUFFMAN a record whose Huffman body would not be STRICTLY
+ * smaller than its packed body is written packed (format id 0..2), and so is a block with a run of count 0 or a
+ * value >= sigma (no token for it) -- tc_container_bound / tc_stream_bound stay sufficient, and the header always
+ * says what the body is.  tc_container_coding: coding of a container in HOST memory from its header alone
+ * (TC_ERR_MALFORMED if it is none).
+ *
+ * Body of a format-3 container (all integers little-endian; every part zero-padded to a multiple of 16 bytes):
+ *   head       4 x uint32: K (runs per chunk, a power of two; this library writes 1024), nchunks = ceil(nruns / K),
+ *              nsyms = sigma + 2, L_max (longest code length; 1 <= L_max <= 12; this library writes 12)
+ *   lengths    uint8 length[nsyms]: code length of every token, 0 = the token does not occur and has no code;
+ *              every length <= L_max and sum over the coded tokens of 2^-length <= 1
+ *   directory  uint32 chunk_bits[nchunks]: number of payload bits of every chunk
+ *   payload    uint32 words; chunk k starts at word sum over j < k of ceil(chunk_bits[j] / 32) and occupies
+ *              ceil(chunk_bits[k] / 32) words; the payload is exactly the sum of these over all chunks, in words,
+ *              padded to 16 bytes
+ * Tokens: a run (value v < sigma, count c >= 1) is the token v followed, when c > 1, by the digits of c - 1 in
+ *   bijective base 2, least significant first, as tokens RUNA = sigma (digit 1) and RUNB = sigma + 1 (digit 2) --
+ *   equivalently: the floor(log2 c) low bits of c, lowest first, RUNA for a 0 bit and RUNB for a 1 bit.  At most 31
+ *   digits (c <= 2^32 - 1).  Count 0 has no tokens.
+ * Code: canonical.  Coded tokens sorted by (length, token) receive consecutive code values starting from 0, the
+ *   value being doubled (shifted left by one) for every step up in length -- code(first) = 0, code(next) =
+ *   (code(previous) + 1) << (length(next) - length(previous)).  Only the lengths are stored; a reader depends on
+ *   nothing about how they were chosen.  A record with a single distinct token stores length 1 for it.
+ * Bits: a code is emitted most significant bit first; bit b of a chunk (b = 0 first) is bit 31 - (b mod 32) of
+ *   the chunk's word b / 32.  Chunk k holds the tokens of runs k * K .. min(nruns, (k + 1) * K) - 1 and nothing else:
+ *   its first token is a value token, it decodes without looking at any other chunk, and the bits behind
+ *   chunk_bits[k] up to the word boundary are zero padding that a reader ignores.  (The directory stores bits, not
+ *   words, because zero padding could otherwise be read as digit tokens of the chunk's last run.)  No two chunks
+ *   share a word, so a writer needs no read-modify-write across workgroups.
+ * Header fields: format = 3, nesc = 0; nruns, body_bytes and the checksum (over the whole body, verified before
+ *   anything is decoded) as for the other formats.  The magic stays "TCBLK01": a build without this format
+ *   refuses format 3 as inconsistent.  A reader answers TC_ERR_MALFORMED to: K not a power of two, nchunks or
+ *   nsyms that do not follow from the header, L_max outside 1..12, a length above L_max, a Kraft sum above 1, a
+ *   directory that does not sum to the payload's size, bits that match no code, a chunk that ends inside a code, a
+ *   digit before the chunk's first value, more than 31 digits, more or fewer runs in a chunk than it must hold. */
+#define TC_CODING_PACKED 0
+#define TC_CODING_HUFFMAN 1
+int tc_ctx_set_container_coding(tc_ctx *ctx, int coding);   /* TC_ERR_ARG for anything else */
+int tc_ctx_get_container_coding(const tc_ctx *ctx);
+int tc_container_coding(tc_ctx *ctx, const uint8_t *container, uint64_t bytes, int *coding);
 uint64_t tc_container_bound(uint64_t nruns, uint32_t sigma);
 int tc_block_to_container_dev(tc_ctx *ctx, const tc_block *blk /* device runs */, uint8_t *d_out, uint64_t *bytes);
 /* Text -> container in one call, everything on the device: the bytes of tc_encode_dev followed by

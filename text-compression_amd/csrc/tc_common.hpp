@@ -39,6 +39,7 @@ struct tc_ctx {
     hipEvent_t ev[8] = {};
     hipEvent_t pev[2 * 16] = {};  // per-pass event pairs (profile mode)
     int profile = 0;
+    int coding = 0;        // TC_CODING_*: the body the container writers produce (tc_ctx_set_container_coding)
     int num_cus = 0;
     int reserved_cus = 0;  // CUs left to a tc_comm's stream: the partition levels split their work over the others
     void *hostpipe = nullptr;   // page-locked staging ring + persistent device buffers of the host entry points (textcomp.hip)

@@ -8,6 +8,7 @@
 #include "tc_decode_host.hpp"
 #include "tc_fm_host.hpp"
 #include "tc_pack.hpp"
+#include "tc_huff.hpp"
 #include "tc_comm.hpp"
 #include "textcomp_debug.h"
 
@@ -733,6 +734,18 @@ int tc_ctx_set_profile(tc_ctx *ctx, int on) {
     return TC_OK;
 }
 
+int tc_ctx_set_container_coding(tc_ctx *ctx, int coding) {
+    if (!ctx) return TC_ERR_ARG;
+    if (coding != TC_CODING_PACKED && coding != TC_CODING_HUFFMAN) {
+        ctx->err = "unknown container coding";
+        return TC_ERR_ARG;
+    }
+    ctx->coding = coding;
+    return TC_OK;
+}
+
+int tc_ctx_get_container_coding(const tc_ctx *ctx) { return ctx ? ctx->coding : TC_ERR_ARG; }
+
 // ================================================================= Data.BWT
 int tc_bwt_encode_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint8_t *d_L,
                       uint64_t *primary) {
@@ -1169,6 +1182,19 @@ static size_t block_pack_scratch(u64 nruns) {
     return (((size_t)(nruns / PR_TILE + nruns / PK_TILE + 8) * sizeof(u64) + 255) & ~(size_t)255) +
            (((size_t)(nruns + 8) * sizeof(u32) + 255) & ~(size_t)255) + 512;
 }
+// the same for a context whose containers are Huffman-coded: the Huffman writer's scratch, or -- when the record falls
+// back to the packing -- the packer's, one after the other in the same place
+static size_t huff_scratch(u64 nruns) {
+    const size_t nchunks = (size_t)(nruns / HF_K + 1);
+    return (((size_t)HF_HIST_WORDS * sizeof(u32) + 255) & ~(size_t)255) + (((nchunks + 4) * sizeof(u32) + 255) & ~(size_t)255) +
+           (((nchunks + 2) * sizeof(u64) + 255) & ~(size_t)255);
+}
+static size_t container_scratch(const tc_ctx *ctx, u64 nruns) {
+    const size_t p = block_pack_scratch(nruns);
+    if (ctx->coding != TC_CODING_HUFFMAN) return p;
+    const size_t h = huff_scratch(nruns);
+    return p > h ? p : h;
+}
 static void block_pack_device(tc_ctx *ctx, const tc_block *blk, uint8_t *d_packed, uint64_t *packed_bytes,
                               uint64_t *nesc, size_t ws_base = 0) {
     if (!blk || !packed_bytes || !nesc) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
@@ -1384,6 +1410,149 @@ static u64 checksum64_device(tc_ctx *ctx, const u8 *d_p, u64 bytes) {
     return ctx->h_scalars[16] ^ (bytes * 0x9E3779B97F4A7C15ull);
 }
 
+// ---- the Huffman body (format 3; tc_huff.hpp, layout in include/textcomp.h) ------------------------------------------
+// Writes blk's runs as a Huffman body into d_body (*body_bytes: in capacity, out bytes used) and returns true -- or
+// returns false, nothing of value written, when the record is to be packed instead: the Huffman body would not be
+// strictly smaller than the packed one (whose size the histogram pass has summed from the counts), or a run has no
+// token (count 0, value >= sigma).  Two host synchronisations of its own: the histogram, and the payload size.
+static bool huff_write_device(tc_ctx *ctx, const tc_block *blk, u8 *d_body, u64 *body_bytes, size_t ws_base) {
+    const u64 nruns = blk->nruns, cap = *body_bytes;
+    const u32 sigma = blk->sigma;
+    if (nruns == 0 || sigma == 0) return false;
+    if (!blk->run_count || !blk->run_value) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (nruns > (u64)TC_MAX_N + 2) TC_FAIL(ctx, TC_ERR_ARG, "too many runs");
+    const u32 nsyms = sigma + 2;
+    const u32 nchunks = tc_cdiv(nruns, HF_K);
+    u32 *hist = nullptr, *dirbits = nullptr;
+    u64 *offs = nullptr;
+    auto carve = [&](Arena &A) {
+        hist = A.get<u32>(HF_HIST_WORDS);
+        dirbits = A.get<u32>((size_t)nchunks + 4);
+        offs = A.get<u64>((size_t)nchunks + 2);
+    };
+    Arena dry(nullptr);
+    carve(dry);
+    tc_ws_reserve(ctx, ws_base + dry.off);
+    Arena A(ctx->ws + ws_base);
+    carve(A);
+    hipStream_t s = ctx->stream;
+    tc_memset_async(ctx, hist, 0, HF_HIST_WORDS * sizeof(u32));
+    u32 grid = tc_persistent_grid(ctx, 8);
+    {
+        HuffHistArgs a;
+        a.cnt = blk->run_count; a.val = blk->run_value; a.nruns = nruns; a.sigma = sigma; a.hist = hist;
+        const u32 g = tc_cdiv(nruns, HF_NT * 4);
+        huff_hist_kernel<<<g < grid ? g : grid, HF_NT, 0, s>>>(a);
+        TC_LAUNCH_CHECK(ctx);
+    }
+    u32 h_hist[HF_HIST_WORDS];
+    tc_d2h(ctx, h_hist, hist, sizeof h_hist);
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    u64 tot[HF_TOT_WORDS / 2];
+    memcpy(tot, h_hist + 264, sizeof tot);
+    if (tot[4]) return false;   // a run without a token: such a block is packed
+    const int fmt = pack_format(sigma);
+    const u64 packed = fmt == 0 ? ((tot[0] + 31) / 32) * 16 + 4 * tot[1]
+                                : (((u64)fmt * nruns + 7) & ~7ull) + 8 * (fmt == 1 ? tot[2] : tot[3]);
+    const u64 fixed = hf_fixed_bytes(nsyms, nchunks);
+    if (fixed + 16 >= packed) return false;   // head, lengths and directory alone outweigh the packed body
+    u8 len[HF_MAXSYM + 1];
+    huff_build_lengths(h_hist, nsyms, len);
+    HuffEncArgs e;
+    huff_assign_codes(len, nsyms, &e.codes);
+    e.cnt = blk->run_count; e.val = blk->run_value; e.nruns = nruns; e.sigma = sigma; e.nchunks = nchunks;
+    e.dirbits = dirbits; e.offs = offs; e.payload = nullptr; e.payload_words = 0;
+    if (grid > nchunks) grid = nchunks;
+    huff_encode_kernel<false><<<grid, HF_NT, 0, s>>>(e);
+    TC_LAUNCH_CHECK(ctx);
+    huff_dir_scan_kernel<<<1, HF_SCAN_NT, 0, s>>>(dirbits, nchunks, offs);
+    TC_LAUNCH_CHECK(ctx);
+    tc_d2h(ctx, &ctx->h_scalars[14], offs + nchunks, sizeof(u64));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    const u64 words = ctx->h_scalars[14];
+    const u64 body = fixed + hf_pad16(4 * words);
+    if (body >= packed) return false;
+    *body_bytes = body;
+    if (body > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "container body needs %llu bytes", (unsigned long long)body);
+    if (!d_body) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    // head and lengths (through the pinned header staging, which is idle until the container's header is written)
+    const u64 lens_off = 16, dir_off = 16 + hf_pad16(nsyms), pay_off = fixed;
+    u8 *stage = ctx->h_hdr;
+    memset(stage, 0, (size_t)dir_off);
+    const u32 head[4] = {HF_K, nchunks, nsyms, HF_LMAX};
+    memcpy(stage, head, 16);
+    memcpy(stage + lens_off, len, nsyms);
+    tc_h2d(ctx, d_body, stage, (size_t)dir_off);
+    tc_memset_async(ctx, d_body + body - 16, 0, 16);                 // the payload's padding
+    tc_memset_async(ctx, d_body + pay_off - 16, 0, 16);             // the directory's padding
+    TC_HIP(ctx, hipMemcpyAsync(d_body + dir_off, dirbits, 4 * (size_t)nchunks, hipMemcpyDeviceToDevice, s));
+    e.payload = reinterpret_cast<u32 *>(d_body + pay_off);
+    e.payload_words = words;
+    huff_encode_kernel<true><<<grid, HF_NT, 0, s>>>(e);
+    TC_LAUNCH_CHECK(ctx);
+    return true;
+}
+
+// Inverse: validates head, lengths and directory, then fills blk->run_count / run_value (device, capacity
+// blk->nruns >= nruns).  Anything that is not a body of exactly nruns runs is TC_ERR_MALFORMED.
+static void huff_read_device(tc_ctx *ctx, const u8 *d_body, u64 body_bytes, u64 nruns, u32 sigma, tc_block *blk) {
+    if (!blk || blk->nruns < nruns) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    if (nruns == 0 || sigma == 0 || sigma > TC_MAX_SIGMA) TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body without runs");
+    if (!d_body || !blk->run_count || !blk->run_value) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    const u32 nsyms = sigma + 2;
+    const u64 dir_off = 16 + hf_pad16(nsyms);
+    if (body_bytes < dir_off || (body_bytes & 15)) TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body too short");
+    hipStream_t s = ctx->stream;
+    u8 fix[16 + ((HF_MAXSYM + 15) & ~15)];
+    tc_d2h(ctx, fix, d_body, (size_t)dir_off);
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    u32 head[4];
+    memcpy(head, fix, 16);
+    const u32 K = head[0], nchunks = head[1], lmax = head[3];
+    if (K == 0 || (K & (K - 1)) || head[2] != nsyms || lmax < 1 || lmax > HF_LMAX ||
+        (u64)nchunks != (nruns + K - 1) / K)
+        TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body: bad head (K %u, chunks %u, symbols %u, longest code %u)", K, nchunks,
+                head[2], lmax);
+    u64 kraft = 0;   // in units of 2^-lmax
+    for (u32 i = 0; i < nsyms; i++) {
+        const u32 l = fix[16 + i];
+        if (l > lmax) TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body: code length %u above %u", l, lmax);
+        if (l) kraft += 1ull << (lmax - l);
+    }
+    if (kraft > (1ull << lmax)) TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body: code lengths are no prefix code");
+    const u64 fixed = hf_fixed_bytes(nsyms, nchunks);
+    if (fixed > body_bytes) TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body: directory longer than the body");
+    const u64 payload_words = (body_bytes - fixed) / 4;
+    u64 *offs = nullptr;
+    auto carve = [&](Arena &A) { offs = A.get<u64>((size_t)nchunks + 2); };
+    Arena dry(nullptr);
+    carve(dry);
+    tc_ws_reserve(ctx, dry.off);
+    Arena A(ctx->ws);
+    carve(A);
+    const u32 *dirbits = reinterpret_cast<const u32 *>(d_body + dir_off);
+    huff_dir_scan_kernel<<<1, HF_SCAN_NT, 0, s>>>(dirbits, nchunks, offs);
+    TC_LAUNCH_CHECK(ctx);
+    tc_d2h(ctx, &ctx->h_scalars[14], offs + nchunks, sizeof(u64));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    const u64 words = ctx->h_scalars[14];
+    if (((words + 3) & ~3ull) != payload_words)
+        TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body: directory sums to %llu words, payload has %llu",
+                (unsigned long long)words, (unsigned long long)payload_words);
+    HuffDecArgs a;
+    a.len = d_body + 16; a.dirbits = dirbits; a.offs = offs;
+    a.payload = reinterpret_cast<const u32 *>(d_body + fixed); a.payload_words = payload_words;
+    a.nruns = nruns; a.K = K; a.nchunks = nchunks; a.sigma = sigma; a.lmax = lmax;
+    a.cnt = blk->run_count; a.val = blk->run_value; a.err = ctx->d_err;
+    u32 grid = tc_persistent_grid(ctx, 8);
+    const u32 g = tc_cdiv(nchunks, HF_NT);
+    huff_decode_kernel<<<g < grid ? g : grid, HF_NT, 0, s>>>(a);
+    TC_LAUNCH_CHECK(ctx);
+    tc_sync_check(ctx);
+    blk->nruns = nruns;
+    blk->sigma = sigma;
+}
+
 uint64_t tc_container_bound(uint64_t nruns, uint32_t sigma) {
     return TC_CONTAINER_HEADER + tc_block_packed_bound(nruns, sigma);
 }
@@ -1406,7 +1575,12 @@ static void container_write_device(tc_ctx *ctx, const tc_block *blk, u8 *d_out, 
     for (u32 i = 0; i < blk->sigma; i++) h.final_list[i] = blk->final_list[i];
     u64 body = cap - TC_CONTAINER_HEADER, nesc = 0;
     try {
-        block_pack_device(ctx, blk, d_out + TC_CONTAINER_HEADER, &body, &nesc, ws_base);
+        if (ctx->coding == TC_CODING_HUFFMAN && huff_write_device(ctx, blk, d_out + TC_CONTAINER_HEADER, &body, ws_base)) {
+            h.format = HF_FORMAT;
+        } else {
+            body = cap - TC_CONTAINER_HEADER;
+            block_pack_device(ctx, blk, d_out + TC_CONTAINER_HEADER, &body, &nesc, ws_base);
+        }
     } catch (const TcFail &f) {
         if (f.code == TC_ERR_CAPACITY) *bytes = TC_CONTAINER_HEADER + body;
         throw;
@@ -1432,7 +1606,7 @@ static ContainerHeader container_header(tc_ctx *ctx, const u8 *d_in, u64 bytes) 
     memcpy(&h, hdr, sizeof h);
     if (memcmp(h.magic, kContainerMagic, 8) != 0) TC_FAIL(ctx, TC_ERR_MALFORMED, "not a textcomp container");
     if (h.n > TC_MAX_N || h.sigma > TC_MAX_SIGMA || h.nruns > (u64)TC_MAX_N + 2 || h.nesc > h.nruns ||
-        h.format != (u32)pack_format(h.sigma) || h.body_bytes != bytes - TC_CONTAINER_HEADER ||
+        (h.format != (u32)pack_format(h.sigma) && !(h.format == HF_FORMAT && h.nesc == 0)) || h.body_bytes != bytes - TC_CONTAINER_HEADER ||
         (h.n > 0 && (h.primary > h.n || h.nruns == 0)))
         TC_FAIL(ctx, TC_ERR_MALFORMED, "container header is inconsistent");
     return h;
@@ -1447,7 +1621,8 @@ static void container_read_device(tc_ctx *ctx, const u8 *d_in, u64 bytes, tc_blo
     }
     if (checksum64_device(ctx, d_in + TC_CONTAINER_HEADER, h.body_bytes) != h.checksum)
         TC_FAIL(ctx, TC_ERR_MALFORMED, "container checksum mismatch");
-    block_unpack_device(ctx, d_in + TC_CONTAINER_HEADER, h.body_bytes, h.nruns, h.sigma, h.nesc, blk);
+    if (h.format == HF_FORMAT) huff_read_device(ctx, d_in + TC_CONTAINER_HEADER, h.body_bytes, h.nruns, h.sigma, blk);
+    else block_unpack_device(ctx, d_in + TC_CONTAINER_HEADER, h.body_bytes, h.nruns, h.sigma, h.nesc, blk);
     blk->n = h.n; blk->primary = h.primary; blk->sigma = h.sigma; blk->nruns = h.nruns;
     for (u32 i = 0; i < h.sigma; i++) blk->final_list[i] = h.final_list[i];
 }
@@ -1515,6 +1690,8 @@ static void encode_container_device(tc_ctx *ctx, const u8 *d_text, u64 n, u8 *d_
     const u32 ntiles = tc_cdiv(N, RN_TILE);
     const u64 esc_cap = N / 5 + 16;
     bool fused = false;
+    // a Huffman-coded container is written from the run arrays (as sigma > 6 is): neither fused nibble path is taken
+    const bool huff = ctx->coding == TC_CODING_HUFFMAN;
     tc_block blk;
     memset(&blk, 0, sizeof blk);
     size_t pack_base = 0;
@@ -1562,7 +1739,7 @@ static void encode_container_device(tc_ctx *ctx, const u8 *d_text, u64 n, u8 *d_
             tc_d2h(ctx, &ctx->h_scalars[20], result, 3 * sizeof(u64));
         };
         bool one_kernel = false;
-        if (!dry && env_int("TC_MTF_RLE", 1) != 0 && env_int("TC_MTF_FORCE_GENERAL", 0) == 0 && N + 64 < (1ull << 32)) {
+        if (!dry && !huff && env_int("TC_MTF_RLE", 1) != 0 && env_int("TC_MTF_FORCE_GENERAL", 0) == 0 && N + 64 < (1ull << 32)) {
             Alphabet al;
             al.build(counts257);
             if (al.sigma <= PK_NIB_SIGMA) {
@@ -1618,7 +1795,7 @@ static void encode_container_device(tc_ctx *ctx, const u8 *d_text, u64 n, u8 *d_
             u64 t = 0;
             rle_encode_device<U16Acc, u16>(ctx, A, iacc, N, r_cnt, r_val, N + 2, &t, true);
             pack_base = A.off;
-            (void)A.get<u8>(block_pack_scratch(N + 2));
+            (void)A.get<u8>(container_scratch(ctx, N + 2));
             if (A.off < end_sa) A.off = end_sa;
             return;
         }
@@ -1626,7 +1803,7 @@ static void encode_container_device(tc_ctx *ctx, const u8 *d_text, u64 n, u8 *d_
             if (A.off < end_sa) A.off = end_sa;
             return;
         }
-        fused = idx8 && sigma <= PK_NIB_SIGMA;
+        fused = idx8 && sigma <= PK_NIB_SIGMA && !huff;
         if (fused) {
             tc_memset_async(ctx, status, 0, (2 * (size_t)ntiles + 32) * sizeof(u64));
             u8 *body = d_out + TC_CONTAINER_HEADER;
@@ -1734,6 +1911,23 @@ int tc_container_info(tc_ctx *ctx, const uint8_t *container, uint64_t bytes, uin
         if (memcmp(h.magic, kContainerMagic, 8) != 0) TC_FAIL(ctx, TC_ERR_MALFORMED, "not a textcomp container");
         if (n) *n = h.n;
         if (nruns) *nruns = h.nruns;
+        return TC_OK;
+    } catch (const TcFail &f) {
+        return f.code;
+    }
+}
+
+int tc_container_coding(tc_ctx *ctx, const uint8_t *container, uint64_t bytes, int *coding) {
+    if (!ctx) return TC_ERR_ARG;
+    try {
+        if (!coding) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+        if (!container || bytes < TC_CONTAINER_HEADER) TC_FAIL(ctx, TC_ERR_MALFORMED, "container shorter than its header");
+        ContainerHeader h;
+        memcpy(&h, container, sizeof h);
+        if (memcmp(h.magic, kContainerMagic, 8) != 0) TC_FAIL(ctx, TC_ERR_MALFORMED, "not a textcomp container");
+        if (h.format == HF_FORMAT) *coding = TC_CODING_HUFFMAN;
+        else if (h.sigma <= TC_MAX_SIGMA && h.format == (u32)pack_format(h.sigma)) *coding = TC_CODING_PACKED;
+        else TC_FAIL(ctx, TC_ERR_MALFORMED, "container header names no known body format");
         return TC_OK;
     } catch (const TcFail &f) {
         return f.code;

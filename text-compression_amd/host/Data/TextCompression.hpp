@@ -37,6 +37,9 @@ class Context {
     static void check(int rc) {
         if (rc != TC_OK) throw TextCompError(rc, tc_last_error(get()));
     }
+    // what the context's container writers put behind the header: TC_CODING_PACKED (default) or TC_CODING_HUFFMAN
+    static void setContainerCoding(int coding) { check(tc_ctx_set_container_coding(get(), coding)); }
+    static int containerCoding() { return tc_ctx_get_container_coding(get()); }
 
   private:
     Context() {

@@ -21,6 +21,18 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+CODINGS = {"packed": _lib.TC_CODING_PACKED, "huffman": _lib.TC_CODING_HUFFMAN}
+_CODING_NAMES = {v: k for k, v in CODINGS.items()}
+
+
+def _coding_id(coding):
+    if coding in CODINGS:
+        return CODINGS[coding]
+    if coding in _CODING_NAMES:
+        return coding
+    raise ValueError("container coding must be 'packed' or 'huffman', not %r" % (coding,))
+
+
 def _u8(b):
     if isinstance(b, np.ndarray):
         return np.ascontiguousarray(b, dtype=np.uint8)
@@ -76,6 +88,33 @@ class Context:
         ch = C.c_int(-1)
         self._check(self._lib.tc_ctx_place_workspace(self._h, C.c_void_p(d_text_ptr), n, C.byref(blk), tries, ms, C.byref(ch)))
         return [x for x in ms if x > 0], ch.value
+
+    # ------------------------------------------------ container coding
+    def set_container_coding(self, coding):
+        """what the container writers of this context put behind the header: "packed" (the fixed-width
+        packings, the default) or "huffman" (run format id 3; textcomp.h).  Readers go by the header."""
+        self._check(self._lib.tc_ctx_set_container_coding(self._h, _coding_id(coding)))
+
+    @property
+    def container_coding(self):
+        return _CODING_NAMES[self._lib.tc_ctx_get_container_coding(self._h)]
+
+    def _with_coding(self, coding):
+        """context manager: `coding` (None: leave it) for the duration, the previous value afterwards"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            if coding is None:
+                yield
+                return
+            before = self._lib.tc_ctx_get_container_coding(self._h)
+            self.set_container_coding(coding)
+            try:
+                yield
+            finally:
+                self._lib.tc_ctx_set_container_coding(self._h, before)
+        return cm()
 
     def stats(self):
         s = Stats()
@@ -240,14 +279,16 @@ class Context:
         return out.tobytes()
 
     # --------------------------------------------------------- container
-    def encode_container(self, text, cap=None):
-        """text -> one self-describing byte string (header + packed runs); see textcomp.h."""
+    def encode_container(self, text, cap=None, coding=None):
+        """text -> one self-describing byte string (header + packed runs); see textcomp.h.
+        coding: "packed" / "huffman" for this call (the context's setting is restored afterwards)."""
         t = _u8(text)
         n = len(t)
         cap = int(self._lib.tc_container_bound(n + 2, 257 if n else 0)) if cap is None else int(cap)
         out = np.empty(max(cap, 1), np.uint8)
         used = C.c_uint64(cap)
-        self._check(self._lib.tc_encode_container(self._h, _ptr(t), n, _ptr(out), C.byref(used)))
+        with self._with_coding(coding):
+            self._check(self._lib.tc_encode_container(self._h, _ptr(t), n, _ptr(out), C.byref(used)))
         return out[:used.value].tobytes()
 
     def encode_container_dev(self, d_text_ptr, n, d_out_ptr, cap):
@@ -268,8 +309,9 @@ class Context:
         return out[:got.value].tobytes()
 
     # ------------------------------------------------------ chunked stream
-    def encode_stream(self, text, block_bytes=0, cap=None):
-        """text of any length -> containers of independent records of block_bytes, back to back
+    def encode_stream(self, text, block_bytes=0, cap=None, coding=None):
+        """coding: "packed" / "huffman" for this call (the context's setting is restored afterwards).
+        text of any length -> containers of independent records of block_bytes, back to back
         (copies overlap the encode); see textcomp.h.  Without `cap` the output buffer starts at
         2 bytes per input byte and falls back to tc_stream_bound when that is too small."""
         t = _u8(text)
@@ -279,7 +321,8 @@ class Context:
         for i, c in enumerate(caps):
             out = np.empty(max(c, 1), np.uint8)
             used = C.c_uint64(c)
-            rc = self._lib.tc_encode_stream(self._h, _ptr(t), n, int(block_bytes), _ptr(out), C.byref(used))
+            with self._with_coding(coding):
+                rc = self._lib.tc_encode_stream(self._h, _ptr(t), n, int(block_bytes), _ptr(out), C.byref(used))
             if rc == _lib.TC_ERR_CAPACITY and i + 1 < len(caps):
                 continue
             self._check(rc)
@@ -418,6 +461,15 @@ class FMIndexHandle:
 
 
 _DEFAULT = None
+
+
+def container_coding(blob):
+    """"packed" or "huffman": the coding of a container, from its header alone (tc_container_coding)."""
+    b = np.frombuffer(bytes(blob[:_lib.TC_CONTAINER_HEADER]), np.uint8)
+    out = C.c_int(-1)
+    ctx = default_context()
+    ctx._check(ctx.lib.tc_container_coding(ctx.handle, _ptr(b), len(b), C.byref(out)))
+    return _CODING_NAMES[out.value]
 
 
 def default_context():

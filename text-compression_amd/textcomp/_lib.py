@@ -10,8 +10,10 @@ TC_OK = 0
 TC_ERR_ARG, TC_ERR_CAPACITY, TC_ERR_MALFORMED, TC_ERR_HIP, TC_ERR_OOM, TC_ERR_INTERNAL, TC_ERR_NCCL = (
     -1, -2, -3, -4, -5, -6, -7)
 TC_COMM_ID_BYTES = 128
+TC_CONTAINER_HEADER = 640
 TC_MAX_SIGMA = 257
 TC_MAX_ROUNDS = 40
+TC_CODING_PACKED, TC_CODING_HUFFMAN = 0, 1
 
 ERR_NAMES = {-1: "TC_ERR_ARG", -2: "TC_ERR_CAPACITY", -3: "TC_ERR_MALFORMED", -4: "TC_ERR_HIP",
              -5: "TC_ERR_OOM", -6: "TC_ERR_INTERNAL", -7: "TC_ERR_NCCL"}
@@ -58,6 +60,9 @@ SYMBOLS = [
     ("tc_get_stats", _INT, [_P, C.POINTER(Stats)]),
     ("tc_ctx_stream", _P, [_P]),
     ("tc_ctx_set_profile", _INT, [_P, _INT]),
+    ("tc_ctx_set_container_coding", _INT, [_P, _INT]),
+    ("tc_ctx_get_container_coding", _INT, [_P]),
+    ("tc_container_coding", _INT, [_P, _P, _U64, C.POINTER(_INT)]),
     ("tc_ctx_place_workspace", _INT, [_P, _P, _U64, _P, _INT, _P, _P]),
     ("tc_bwt_encode", _INT, [_P, _P, _U64, _P, _PU64]),
     ("tc_bwt_encode_dev", _INT, [_P, _P, _U64, _P, _PU64]),
