@@ -27,7 +27,9 @@
  *     (tests/test_gpu_concurrency.py).  A tc_fm is read-only once built: count
  *     and locate carve their scratch from the CALLING ctx's workspace, so any
  *     number of ctxs on the index's device may query one tc_fm at the same
- *     time; tc_fm_free must not overlap a query of that index.
+ *     time; tc_fm_free must not overlap a query of that index.  The same holds
+ *     for tc_fm_locate_dev and for a sampled index (tc_fm_build_sampled): the
+ *     walk's scratch and its error flag belong to the calling ctx.
  *   - `*_dev` entry points take DEVICE pointers for the bulk arrays (the
  *     benchmark path: inputs and outputs resident in HBM); scalar outputs are
  *     host words.  All calls return after the ctx stream has drained.
@@ -325,6 +327,30 @@ int tc_fm_build(tc_ctx *ctx, const uint8_t *text, uint64_t n, tc_fm **out);
  * it may be released once the call has returned). */
 int tc_fm_build_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, tc_fm **out);
 void tc_fm_free(tc_fm *fm);
+/* The same index with a SAMPLED suffix array (an addition to the reference's surface).  The suffix array is 4 of the 5 bytes
+ * per text byte that locate costs; a sampled index keeps SA[j] only for the rows whose suffix starts at a multiple of sa_rate
+ * (text positions 0, sa_rate, 2 sa_rate, ... <= n) and finds the others by walking the LF mapping to the next sampled row.
+ * sa_rate: a power of two, 1 .. TC_FM_MAX_SA_RATE; 1 = the full suffix array, the index tc_fm_build makes.  Anything else:
+ * TC_ERR_ARG (*out = NULL).  count is unaffected; locate answers the same hits in the same order, at up to sa_rate - 1
+ * (on average (sa_rate - 1) / 2) LF steps per hit.
+ * Layout of the locate part, instead of the N x 4 bytes of the suffix array:
+ *   marks    one more rank bit-vector in the format of the others (64-byte lines {u64 ones-before, 7 x u64 bits}, 448 rows
+ *            per line, N / 448 + 1 lines): bit j set iff SA[j] % sa_rate == 0.  One line answers both "is row j sampled"
+ *            and "which sample is it".  The row of the whole text (SA = 0, whose last-column symbol is Nothing) is always
+ *            marked, so a walk never steps from it.
+ *   samples  uint32 samples[n / sa_rate + 1] in ROW order: samples[rank_marks(j)] = SA[j].
+ * i.e. 1 + 1/7 + 4 / sa_rate bytes per text byte instead of 5 (tc_fm_device_bytes).  What the saving is NOT: the build
+ * still sorts all suffixes, and during the call the full suffix array lies in the ctx's workspace (carved there instead of
+ * being allocated for the index), so the peak device memory of a build is what it is for tc_fm_build; the workspace stays
+ * with the ctx afterwards as after any call.  The saving is in what the index KEEPS, and in what an export ships. */
+#define TC_FM_MAX_SA_RATE 4096
+int tc_fm_build_sampled(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sa_rate, tc_fm **out);
+int tc_fm_build_sampled_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t sa_rate, tc_fm **out);
+/* sa_rate of an index (1: full suffix array; 0: no locate part -- a count-only import, the empty index, NULL) */
+uint32_t tc_fm_sa_rate(const tc_fm *fm);
+/* device bytes the index holds: part 0 = everything, part 1 = the locate part alone (L + SA, or L + marks + samples);
+ * the sizes asked of the allocator, without its rounding.  0 for the empty index or any other part. */
+uint64_t tc_fm_device_bytes(const tc_fm *fm, int part);
 /* bytestringFMIndexCountS / ...CountP (FMIndex.hs:362-379,411-432) =
  * countFMIndex (FMIndex/Internal.hs:347-438) mapped over the patterns in ONE
  * batched launch; pattern j = pats[offs[j] .. offs[j+1]).  out[j] = count, 0 for
@@ -339,6 +365,14 @@ int tc_fm_count_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const u
  * *nhits: in capacity, out total hits (TC_ERR_CAPACITY sets the needed total). */
 int tc_fm_locate(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs,
                  uint64_t npat, uint64_t *hit_offs, uint64_t *hits, uint64_t *nhits);
+/* tc_fm_locate with everything in HBM: d_pats, d_offs as tc_fm_count_dev; d_hit_offs [npat + 1] and d_hits [*nhits] are
+ * device arrays; *nhits (host): in = capacity, out = total (TC_ERR_CAPACITY sets the needed total and writes nothing to
+ * d_hits).  tc_fm_locate is this call between a copy in and a copy out.
+ * Locate on a sampled index that was IMPORTED walks caller data: the walk is bounded on any bytes (at most sa_rate - 1
+ * steps, every row < N, every sample index within the samples, every position within the text), and a walk that runs into
+ * one of its bounds makes the call answer TC_ERR_MALFORMED; on an index this library built it never does. */
+int tc_fm_locate_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs,
+                     uint64_t npat, uint64_t *d_hit_offs, uint64_t *d_hits, uint64_t *nhits);
 /* seqToCc / seqFromFMIndex views for the Haskell shim: present symbols (sorted,
  * Nothing first) with C[c]; and L / primary. */
 int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, uint64_t *c_val,
@@ -346,9 +380,12 @@ int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, ui
 
 /* Replication of a built index over the GPUs of a node (FM-count shards by pattern batch,
  * the index is broadcast once): the index as ONE device byte string (header, C / code tables, rank
- * bit-vectors; with_locate != 0 adds the last column and the suffix array that tc_fm_locate needs) and
+ * bit-vectors; with_locate != 0 adds the last column and the suffix array that tc_fm_locate needs -- of a sampled index
+ * the last column, the marks and the samples, and the header's formerly reserved word carries sa_rate; a full index
+ * writes 0 there, its export is byte for byte what it was -- ) and
  * back.  The caller moves the bytes (RCCL broadcast); tc_fm_import_dev checks the header
- * (TC_ERR_MALFORMED) and copies out of d_in, which may be released afterwards.  An index imported
+ * (TC_ERR_MALFORMED; for a sampled index also: the rate, the sizes that follow from N and the rate, and that the marks hold
+ * exactly one bit per sample) and copies out of d_in, which may be released afterwards.  An index imported
  * without the locate part answers tc_fm_count only (tc_fm_locate: TC_ERR_ARG).  Buffers 16-byte
  * aligned.  *bytes: in = capacity, out = bytes used (TC_ERR_CAPACITY: bytes needed).  The byte string is BUILD-SPECIFIC
  * (it carries a format version: "TCFMI02" since round 3; an export of another version is refused with a message that

@@ -42,6 +42,14 @@ struct tc_fm {
     u64 lines = 0;
     u32 counts[256];
     i16 sym_of_code[256];
+    // the locate part.  sa_rate 1: d_L + d_sa (the full suffix array).  sa_rate k > 1 (tc_fm_build_sampled): d_L + d_marks +
+    // d_samples and no d_sa -- marks is one more rank bit-vector in the line format above, bit j set iff SA[j] % k == 0 (the
+    // primary row, SA = 0, is always marked and, unlike in the symbol vectors, takes part); samples holds the marked rows'
+    // SA values in ROW order: samples[rank_marks(j)] = SA[j], floor(n / k) + 1 of them.  sa_rate 0: no locate part.
+    u32 sa_rate = 0;
+    u64 *d_marks = nullptr;   // [lines][8]
+    u32 *d_samples = nullptr; // [nsamples]
+    u64 nsamples = 0;
 };
 
 #ifdef __HIPCC__
@@ -309,6 +317,146 @@ __global__ __launch_bounds__(256) void fm_locate_fill_kernel(const u64 *__restri
     }
 }
 
+// ---- locate from a sampled suffix array --------------------------------------------------------------------------
+// the marks vector of a sampled index: one wave per line, ballots of (SA[j] % rate == 0); word 0 = the line's ones,
+// made cumulative by fm_scan_kernel like every other vector
+__global__ __launch_bounds__(256) void fm_marks_kernel(const u32 *__restrict__ sa, u64 N, u32 rate, u64 lines,
+                                                       u64 *__restrict__ marks) {
+    const u64 line = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (line >= lines) return;
+    const u32 l = threadIdx.x & 63;
+    u64 mine = 0;
+    u32 pc = 0;
+#pragma unroll
+    for (int w = 0; w < 7; w++) {
+        const u64 j = line * FM_LINE_BITS + (u64)w * 64 + l;
+        const u64 m = __ballot(j < N && (sa[j] & (rate - 1)) == 0);
+        pc += (u32)__popcll(m);
+        if ((int)l == w + 1) mine = m;
+    }
+    if (l == 0) mine = pc;
+    if (l < 8) marks[line * 8 + l] = mine;
+}
+
+// ordered compaction of the sampled entries (after the scan): samples[rank_marks(j)] = SA[j] for every marked row j
+__global__ __launch_bounds__(256) void fm_samples_kernel(const u32 *__restrict__ sa, u64 N, u64 lines,
+                                                         const u64 *__restrict__ marks, u64 nsamples,
+                                                         u32 *__restrict__ samples) {
+    const u64 line = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (line >= lines) return;
+    const u32 l = threadIdx.x & 63;
+    u64 base = marks[line * 8];
+#pragma unroll
+    for (int w = 0; w < 7; w++) {
+        const u64 m = marks[line * 8 + 1 + w];
+        const u64 j = line * FM_LINE_BITS + (u64)w * 64 + l;
+        if (((m >> l) & 1) && j < N) {
+            const u64 idx = base + (u64)__popcll(m & lanemask_lt());
+            if (idx < nsamples) samples[idx] = sa[j];
+        }
+        base += (u64)__popcll(m);
+    }
+}
+
+// ones of a whole vector (import check: the marks of a sampled index must hold exactly nsamples ones); *total zeroed before
+__global__ __launch_bounds__(256) void fm_popcount_kernel(const u64 *__restrict__ bits, u64 lines,
+                                                          unsigned long long *__restrict__ total) {
+    u32 pc = 0;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < lines * 8; i += (u64)gridDim.x * 256)
+        if (i & 7) pc += (u32)__popcll(bits[i]);
+    pc = wave_sum(pc);
+    if (lane_id() == 0 && pc) atomicAdd(total, (unsigned long long)pc);
+}
+
+// fm_locate_fill_kernel for a sampled index: hits[off[p] + t] = the ROW s - 1 + t (0-based) of the hit; fm_locate_walk_kernel
+// turns rows into positions
+__global__ __launch_bounds__(256) void fm_locate_rows_kernel(const u64 *__restrict__ ranges,
+                                                             const u64 *__restrict__ hoffs, u64 npat,
+                                                             u64 cap, u64 *__restrict__ hits) {
+    u64 p = (u64)blockIdx.x * 256 + threadIdx.x;
+    bool in = p < npat;
+    u64 s = in ? ranges[2 * p] : 0, e = in ? ranges[2 * p + 1] : 0;
+    u64 o = in ? hoffs[p] : 0;
+    u64 len = (in && s) ? e - s + 1 : 0;
+    const u64 LONG = 32;
+    if (len && len < LONG)
+        for (u64 t = 0; t < len; t++)
+            if (o + t < cap) hits[o + t] = s - 1 + t;
+    u64 longmask = __ballot(len >= LONG);
+    while (longmask) {
+        int src = __builtin_ctzll(longmask);
+        longmask &= longmask - 1;
+        u64 ls = __shfl(s, src, 64), ll = __shfl(len, src, 64), lo = __shfl(o, src, 64);
+        for (u64 t = lane_id(); t < ll; t += 64)
+            if (lo + t < cap) hits[lo + t] = ls - 1 + t;
+    }
+}
+
+#define FM_ERR_WALK 0x4000u   // device error bit of a walk that ran into one of its bounds (in 0xff00: TC_ERR_MALFORMED)
+
+// One lane per HIT, flat over all hits of the batch: row -> text position by walking the LF mapping to the next sampled row.
+//   steps = 0; while row is not marked: c = code(L[row]); row = C[c] + Occ(c, row); steps++
+//   hits[h] = samples[rank_marks(row)] + steps + 1
+// with the index's own conventions: rows are 0-based, tab[256 + c] = C[c] counts the '$' row (it starts at 1), Occ(c, k)
+// counts L[0 .. k) without the primary row -- LF(j) = C + Occ(c, j) is the 0-based form of the s' = C + Occ(c, s - 1) + 1
+// of fm_count_kernel -- and SA[LF(j)] = SA[j] - 1, so a row `steps` steps before a sample of value v has SA = v + steps;
+// the answer is 1-based (FMIndex.hs:496).  SA = 0 (the primary row, whose L is Nothing) is a multiple of every rate: a walk
+// on a well-formed index ends there at the latest and never steps from it.
+// A step is two dependent levels of random reads: {the L byte, the marks line} of the row, issued together, then the rank
+// line of (c, row).  Lanes leave the loop after different step counts (0 .. rate - 1); nothing in it is cross-lane.
+// The index may be an imported byte string, i.e. caller data: every row is kept < N, every sample index < nsamples, the
+// loop ends after rate - 1 steps, a byte without a code or a step from the primary row stops the walk, and a position must
+// be a multiple of the rate plus the steps and lie in the text; a lane that runs into any of these raises FM_ERR_WALK (the
+// call answers TC_ERR_MALFORMED) and writes 0.  So no content can make the kernel spin or read outside L [N + 16], the
+// vectors [lines = N / 448 + 1 lines each] and samples [nsamples].
+__global__ __launch_bounds__(256) void fm_locate_walk_kernel(const u64 *__restrict__ bits, const u64 *__restrict__ marks,
+                                                             u64 lines, const u32 *__restrict__ tab, u32 sigma,
+                                                             const u8 *__restrict__ L, const u32 *__restrict__ samples,
+                                                             u64 nsamples, u64 N, u64 primary, u32 rate, u64 total,
+                                                             u64 *__restrict__ hits, u32 *__restrict__ err) {
+    __shared__ u32 s_tab[512];
+    for (int i = threadIdx.x; i < 512; i += 256) s_tab[i] = tab[i];
+    __syncthreads();
+    const u64 h = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (h >= total) return;
+    u64 row = hits[h];
+    bool bad = row >= N;
+    if (bad) row = 0;
+    u32 steps = 0;
+    u64 pos = 0;
+    while (true) {
+        const u32 byte = L[row];
+        const u64 line = row / FM_LINE_BITS;
+        const u32 off = (u32)(row - line * FM_LINE_BITS);
+        const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(marks + line * 8);
+        const ulonglong2 a = p[0], b = p[1], cc = p[2], d = p[3];
+        const u64 w[7] = {a.y, b.x, b.y, cc.x, cc.y, d.x, d.y};
+        u64 r = a.x, cur = 0;
+        const u32 full = off >> 6, rem = off & 63;
+#pragma unroll
+        for (int i = 0; i < 7; i++) {
+            const u64 m = ((u32)i < full) ? ~0ull : (((u32)i == full) ? ((1ull << rem) - 1ull) : 0ull);
+            r += (u64)__popcll(w[i] & m);
+            if ((u32)i == full) cur = w[i];
+        }
+        if ((cur >> rem) & 1) {            // a sampled row: r = rank_marks(row)
+            if (r >= nsamples) { bad = true; break; }
+            const u64 v = samples[r];
+            pos = v + steps;
+            if ((v & (rate - 1)) != 0 || pos >= N) bad = true;
+            break;
+        }
+        const u32 c = s_tab[byte];
+        if (steps + 1 >= rate || row == primary || c >= sigma) { bad = true; break; }
+        const u64 nr = (u64)s_tab[256 + c] + fm_occ(bits, lines, c, row);
+        if (nr >= N) { bad = true; break; }
+        row = nr;
+        steps++;
+    }
+    if (bad) atomicOr(err, FM_ERR_WALK);
+    hits[h] = bad ? 0 : pos + 1;
+}
+
 #endif  // __HIPCC__
 
 // code of byte / C[code] / count[code] from the byte histogram; returns the number of present byte values
@@ -334,6 +482,8 @@ static void fm_release(tc_fm *fm) {
     (void)hipSetDevice(fm->device);
     if (fm->d_L) (void)hipFree(fm->d_L);
     if (fm->d_sa) (void)hipFree(fm->d_sa);
+    if (fm->d_marks) (void)hipFree(fm->d_marks);
+    if (fm->d_samples) (void)hipFree(fm->d_samples);
     if (fm->d_bits) (void)hipFree(fm->d_bits);
     if (fm->bits2_chunks) tc_chunked_free(fm->bits2_chunks);
     else if (fm->d_bits2) (void)hipFree(fm->d_bits2);
@@ -358,26 +508,35 @@ static void fm_alloc_bits2(tc_ctx *ctx, tc_fm *fm, size_t bytes) {
 }
 
 // text_host or text_dev (a text already in HBM is used where it lies: no copy at all)
-static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 *text_dev = nullptr) {
+// sa_rate 1: the index owns the full suffix array.  sa_rate k > 1: the suffix array lives in the context's workspace for the
+// duration of the call (the same peak: the 4 N bytes are carved there instead of allocated) and the index keeps marks + samples.
+static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 *text_dev = nullptr, u32 sa_rate = 1) {
     tc_fm *fm = new tc_fm();
     fm->device = ctx->device;
     fm->n = n;
     fm->N = n + 1;
+    fm->sa_rate = sa_rate;
     try {
         const u64 N = n + 1;
         hipStream_t s = ctx->stream;
+        const bool sampled = sa_rate > 1;
         TC_HIP(ctx, hipMalloc((void **)&fm->d_L, N + 16));
-        TC_HIP(ctx, hipMalloc((void **)&fm->d_sa, N * sizeof(u32)));
+        if (!sampled) TC_HIP(ctx, hipMalloc((void **)&fm->d_sa, N * sizeof(u32)));
         TC_HIP(ctx, hipMalloc((void **)&fm->d_tab, 768 * sizeof(u32)));
         u8 *d_text = nullptr;
+        u32 *d_sa = fm->d_sa;
         auto plan = [&](Arena &A, bool dry) {
+            if (sampled) {   // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
+                u32 *p = A.get<u32>(N);
+                d_sa = dry ? reinterpret_cast<u32 *>(sizeof(u32)) : p;
+            }
             if (text_dev) {
                 d_text = const_cast<u8 *>(text_dev);
             } else {
                 d_text = A.get<u8>(n + 16);
                 if (!dry) tc_h2d(ctx, d_text, text_host, n);
             }
-            sa_build(ctx, A, d_text, n, fm->d_sa, fm->d_L, &fm->primary, fm->counts, dry);
+            sa_build(ctx, A, d_text, n, d_sa, fm->d_L, &fm->primary, fm->counts, dry);
         };
         ctx->stats = tc_stats{};
         ctx->stats.n = n; ctx->stats.N = N;
@@ -403,12 +562,24 @@ static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 
             TC_HIP(ctx, hipMalloc((void **)&fm->d_tab2, FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32)));
             fm_alloc_bits2(ctx, fm, (size_t)sig * sig * fm->lines * 64);
             TC_HIP(ctx, hipMemsetAsync(fm->d_tab2, 0, FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32), s));
-            fm_bits2_kernel<<<tc_cdiv(fm->lines, 4), 256, 0, s>>>(fm->d_L, fm->d_sa, d_text, N, fm->d_tab, sig,
+            fm_bits2_kernel<<<tc_cdiv(fm->lines, 4), 256, 0, s>>>(fm->d_L, d_sa, d_text, N, fm->d_tab, sig,
                                                                  fm->lines, fm->d_bits2);
             TC_LAUNCH_CHECK(ctx);
             fm_scan_kernel<<<sig * sig, 1024, 0, s>>>(fm->d_bits2, fm->lines);
             TC_LAUNCH_CHECK(ctx);
             fm_c2_kernel<<<1, 64, 0, s>>>(fm->d_bits, fm->lines, fm->d_tab, sig, fm->d_tab2);
+            TC_LAUNCH_CHECK(ctx);
+        }
+        if (sampled) {
+            fm->nsamples = n / sa_rate + 1;
+            TC_HIP(ctx, hipMalloc((void **)&fm->d_marks, (size_t)fm->lines * 64));
+            TC_HIP(ctx, hipMalloc((void **)&fm->d_samples, (size_t)fm->nsamples * sizeof(u32)));
+            fm_marks_kernel<<<tc_cdiv(fm->lines, 4), 256, 0, s>>>(d_sa, N, sa_rate, fm->lines, fm->d_marks);
+            TC_LAUNCH_CHECK(ctx);
+            fm_scan_kernel<<<1, 1024, 0, s>>>(fm->d_marks, fm->lines);
+            TC_LAUNCH_CHECK(ctx);
+            fm_samples_kernel<<<tc_cdiv(fm->lines, 4), 256, 0, s>>>(d_sa, N, fm->lines, fm->d_marks, fm->nsamples,
+                                                                   fm->d_samples);
             TC_LAUNCH_CHECK(ctx);
         }
         tc_sync_check(ctx);

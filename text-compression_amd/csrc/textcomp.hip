@@ -2251,6 +2251,51 @@ int tc_fm_build_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, tc_fm **out)
     TC_API_END(ctx)
 }
 
+static inline bool fm_rate_ok(u32 r) { return r >= 1 && r <= TC_FM_MAX_SA_RATE && (r & (r - 1)) == 0; }
+
+int tc_fm_build_sampled(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sa_rate, tc_fm **out) {
+    TC_API_BEGIN(ctx)
+    if (out) *out = nullptr;
+    if (!out || n > TC_MAX_N || !fm_rate_ok(sa_rate)) TC_FAIL(ctx, TC_ERR_ARG, "bad argument (sa_rate: a power of two, 1 .. %d)", TC_FM_MAX_SA_RATE);
+    if (n == 0) {
+        tc_fm *fm = new tc_fm();
+        fm->device = ctx->device;
+        *out = fm;
+        return TC_OK;
+    }
+    if (!text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    *out = fm_build_device(ctx, text, n, nullptr, sa_rate);
+    TC_API_END(ctx)
+}
+
+int tc_fm_build_sampled_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t sa_rate, tc_fm **out) {
+    TC_API_BEGIN(ctx)
+    if (out) *out = nullptr;
+    if (!out || n > TC_MAX_N || !fm_rate_ok(sa_rate)) TC_FAIL(ctx, TC_ERR_ARG, "bad argument (sa_rate: a power of two, 1 .. %d)", TC_FM_MAX_SA_RATE);
+    if (n == 0) {
+        tc_fm *fm = new tc_fm();
+        fm->device = ctx->device;
+        *out = fm;
+        return TC_OK;
+    }
+    if (!d_text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    *out = fm_build_device(ctx, nullptr, n, d_text, sa_rate);
+    TC_API_END(ctx)
+}
+
+uint32_t tc_fm_sa_rate(const tc_fm *fm) { return fm ? fm->sa_rate : 0; }
+
+uint64_t tc_fm_device_bytes(const tc_fm *fm, int part) {
+    if (!fm || fm->n == 0 || (part != 0 && part != 1)) return 0;
+    u64 loc = 0;
+    if (fm->sa_rate == 1) loc = (fm->N + 16) + fm->N * sizeof(u32);
+    else if (fm->sa_rate > 1) loc = (fm->N + 16) + fm->lines * 64 + fm->nsamples * sizeof(u32);
+    if (part == 1) return loc;
+    u64 b = loc + 768 * sizeof(u32) + (u64)fm->sigma_bytes * fm->lines * 64;
+    if (fm->d_bits2) b += (u64)fm->sigma_bytes * fm->sigma_bytes * fm->lines * 64 + FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32);
+    return b;
+}
+
 void tc_fm_free(tc_fm *fm) { fm_release(fm); }
 
 // ---- the index as one device byte string (replication over the GPUs of a node) ----------------
@@ -2258,7 +2303,9 @@ struct FmWire {
     char magic[8];   // "TCFMI02\0"
     u64 n, N, primary, lines, bytes;
     u32 sigma_bytes, with_locate;
-    u32 with_pairs, reserved;   // 1: the pair vectors (sigma_bytes^2 of them) follow the per-byte vectors
+    u32 with_pairs, sa_rate;    // 1: the pair vectors (sigma_bytes^2 of them) follow the per-byte vectors.  sa_rate (the word was
+                                // reserved = 0 before sampled indexes): 0 or 1 = the locate part is L + the full suffix array;
+                                // k > 1 = L + marks + samples (a full index writes 0: its export is what it always was)
     u32 counts[256];
     i16 sym_of_code[256];
 };
@@ -2269,7 +2316,9 @@ static u64 fm_wire_bytes(const tc_fm *fm, int with_locate) {
     if (fm->n == 0) return b;
     b += fm_wire_align((u64)fm->sigma_bytes * fm->lines * 64);
     if (fm->d_bits2) b += fm_wire_align((u64)fm->sigma_bytes * fm->sigma_bytes * fm->lines * 64);
-    if (with_locate) b += fm_wire_align(fm->N + 16) + fm_wire_align(fm->N * sizeof(u32));
+    if (with_locate && fm->sa_rate > 1)
+        b += fm_wire_align(fm->N + 16) + fm_wire_align(fm->lines * 64) + fm_wire_align(fm->nsamples * sizeof(u32));
+    else if (with_locate) b += fm_wire_align(fm->N + 16) + fm_wire_align(fm->N * sizeof(u32));
     return b;
 }
 
@@ -2287,6 +2336,7 @@ int tc_fm_export_dev(tc_ctx *ctx, const tc_fm *fm, int with_locate, uint8_t *d_o
     h.n = fm->n; h.N = fm->N; h.primary = fm->primary; h.lines = fm->lines; h.bytes = need;
     h.sigma_bytes = fm->sigma_bytes; h.with_locate = (fm->n && with_locate) ? 1u : 0u;
     h.with_pairs = fm->d_bits2 ? 1u : 0u;
+    h.sa_rate = (h.with_locate && fm->sa_rate > 1) ? fm->sa_rate : 0u;
     memcpy(h.counts, fm->counts, sizeof h.counts);
     memcpy(h.sym_of_code, fm->sym_of_code, sizeof h.sym_of_code);
     hipStream_t s = ctx->stream;
@@ -2303,7 +2353,13 @@ int tc_fm_export_dev(tc_ctx *ctx, const tc_fm *fm, int with_locate, uint8_t *d_o
         if (with_locate) {
             TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_L, fm->N, hipMemcpyDeviceToDevice, s));
             o += fm_wire_align(fm->N + 16);
-            TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_sa, fm->N * sizeof(u32), hipMemcpyDeviceToDevice, s));
+            if (fm->sa_rate > 1) {
+                TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_marks, fm->lines * 64, hipMemcpyDeviceToDevice, s));
+                o += fm_wire_align(fm->lines * 64);
+                TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_samples, fm->nsamples * sizeof(u32), hipMemcpyDeviceToDevice, s));
+            } else {
+                TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_sa, fm->N * sizeof(u32), hipMemcpyDeviceToDevice, s));
+            }
         }
     }
     TC_HIP(ctx, hipStreamSynchronize(s));   // h is a stack object
@@ -2339,6 +2395,11 @@ int tc_fm_import_dev(tc_ctx *ctx, const uint8_t *d_in, uint64_t bytes, tc_fm **o
     }
     if (h.with_pairs > 1 || (h.with_pairs && (h.sigma_bytes > FM_PAIR_SIGMA || h.n < 2)))
         TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: header is inconsistent");
+    // the sampling rate rides in the word that was reserved: 0 or 1 = full suffix array; otherwise a power of two within range,
+    // and only where there is a locate part
+    const bool wire_sampled = h.sa_rate > 1;
+    if (wire_sampled && (!fm_rate_ok(h.sa_rate) || !h.with_locate || !h.n))
+        TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: bad suffix-array sampling rate %u", h.sa_rate);
     tc_fm *fm = new tc_fm();
     fm->device = ctx->device;
     fm->n = h.n; fm->N = h.N; fm->primary = h.primary; fm->lines = h.lines; fm->sigma_bytes = h.sigma_bytes;
@@ -2349,7 +2410,12 @@ int tc_fm_import_dev(tc_ctx *ctx, const uint8_t *d_in, uint64_t bytes, tc_fm **o
             const u64 bb = (u64)fm->sigma_bytes * fm->lines * 64;
             u64 need = fm_wire_align(sizeof(FmWire)) + fm_wire_align(bb);
             if (h.with_pairs) need += fm_wire_align(bb * fm->sigma_bytes);
-            if (h.with_locate) need += fm_wire_align(fm->N + 16) + fm_wire_align(fm->N * sizeof(u32));
+            if (wire_sampled) {
+                fm->nsamples = fm->n / h.sa_rate + 1;
+                need += fm_wire_align(fm->N + 16) + fm_wire_align(fm->lines * 64) + fm_wire_align(fm->nsamples * sizeof(u32));
+            } else if (h.with_locate) {
+                need += fm_wire_align(fm->N + 16) + fm_wire_align(fm->N * sizeof(u32));
+            }
             if (need != h.bytes) TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: size mismatch");
             u32 tab[768];
             (void)fm_make_tab(fm->counts, tab, nullptr);
@@ -2369,12 +2435,36 @@ int tc_fm_import_dev(tc_ctx *ctx, const uint8_t *d_in, uint64_t bytes, tc_fm **o
                 fm_c2_kernel<<<1, 64, 0, s>>>(fm->d_bits, fm->lines, fm->d_tab, fm->sigma_bytes, fm->d_tab2);
                 TC_LAUNCH_CHECK(ctx);
             }
-            if (h.with_locate) {
+            if (wire_sampled) {
+                TC_HIP(ctx, hipMalloc((void **)&fm->d_L, fm->N + 16));
+                TC_HIP(ctx, hipMalloc((void **)&fm->d_marks, fm->lines * 64));
+                TC_HIP(ctx, hipMalloc((void **)&fm->d_samples, fm->nsamples * sizeof(u32)));
+                TC_HIP(ctx, hipMemsetAsync(fm->d_L + fm->N, 0, 16, s));
+                TC_HIP(ctx, hipMemcpyAsync(fm->d_L, d_in + o, fm->N, hipMemcpyDeviceToDevice, s));
+                o += fm_wire_align(fm->N + 16);
+                TC_HIP(ctx, hipMemcpyAsync(fm->d_marks, d_in + o, fm->lines * 64, hipMemcpyDeviceToDevice, s));
+                o += fm_wire_align(fm->lines * 64);
+                TC_HIP(ctx, hipMemcpyAsync(fm->d_samples, d_in + o, fm->nsamples * sizeof(u32), hipMemcpyDeviceToDevice, s));
+                // what only the device can check: the marks hold exactly one bit per sample (the walk bounds everything else)
+                unsigned long long *d_ones = reinterpret_cast<unsigned long long *>(ctx->d_scalars + 10);
+                TC_HIP(ctx, hipMemsetAsync(d_ones, 0, sizeof(u64), s));
+                u32 grid = tc_cdiv(fm->lines * 8, 256 * 16);
+                if (grid > 4096) grid = 4096;
+                fm_popcount_kernel<<<grid, 256, 0, s>>>(fm->d_marks, fm->lines, d_ones);
+                TC_LAUNCH_CHECK(ctx);
+                TC_HIP(ctx, hipMemcpyAsync(&ctx->h_scalars[10], d_ones, sizeof(u64), hipMemcpyDeviceToHost, s));
+                TC_HIP(ctx, hipStreamSynchronize(s));
+                if (ctx->h_scalars[10] != fm->nsamples)
+                    TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: %llu rows are marked as sampled, %llu samples follow",
+                            (unsigned long long)ctx->h_scalars[10], (unsigned long long)fm->nsamples);
+                fm->sa_rate = h.sa_rate;
+            } else if (h.with_locate) {
                 TC_HIP(ctx, hipMalloc((void **)&fm->d_L, fm->N + 16));
                 TC_HIP(ctx, hipMalloc((void **)&fm->d_sa, fm->N * sizeof(u32)));
                 TC_HIP(ctx, hipMemcpyAsync(fm->d_L, d_in + o, fm->N, hipMemcpyDeviceToDevice, s));
                 o += fm_wire_align(fm->N + 16);
                 TC_HIP(ctx, hipMemcpyAsync(fm->d_sa, d_in + o, fm->N * sizeof(u32), hipMemcpyDeviceToDevice, s));
+                fm->sa_rate = 1;
             }
             TC_HIP(ctx, hipStreamSynchronize(s));
         }
@@ -2433,6 +2523,57 @@ int tc_fm_count(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_
     TC_API_END(ctx)
 }
 
+// scratch of one locate batch besides patterns and results
+struct FmLocateScratch {
+    i64 *d_cnt = nullptr;
+    u64 *d_ranges = nullptr, *d_len = nullptr, *d_tsum = nullptr;
+    u64 tiles = 0;
+    void carve(Arena &A, u64 npat) {
+        tiles = tc_cdiv(npat, SCAN_TILE);
+        d_cnt = A.get<i64>(npat);
+        d_ranges = A.get<u64>(2 * npat);
+        d_len = A.get<u64>(npat + 1);
+        d_tsum = A.get<u64>(tiles + 2);
+    }
+};
+
+// everything on the device: ranges, hit offsets (d_hoffs[0 .. npat); the total is returned), then the hits -- from the suffix
+// array (a full index: the table lookup) or as rows walked to positions (a sampled one).  Returns the total; when it exceeds
+// cap nothing is written to d_hits.  The caller synchronises (tc_sync_check: the walk's bounds raise the device error word).
+static u64 fm_locate_device(tc_ctx *ctx, const tc_fm *fm, const FmLocateScratch &W, const u8 *d_pats, const u64 *d_offs,
+                            u64 npat, u64 *d_hoffs, u64 *d_hits, u64 cap) {
+    hipStream_t s = ctx->stream;
+    const u64 tiles = W.tiles;
+    fm_count_device(ctx, fm, d_pats, d_offs, npat, W.d_cnt, W.d_ranges);
+    fm_cnt_to_u64_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(W.d_cnt, npat, W.d_len);
+    TC_LAUNCH_CHECK(ctx);
+    scan64_reduce_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(W.d_len, npat, W.d_tsum);
+    TC_LAUNCH_CHECK(ctx);
+    scan64_spine_kernel<<<1, 1024, 0, s>>>(W.d_tsum, tiles);
+    TC_LAUNCH_CHECK(ctx);
+    scan64_down_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(W.d_len, npat, W.d_tsum, d_hoffs);
+    TC_LAUNCH_CHECK(ctx);
+    tc_d2h(ctx, &ctx->h_scalars[9], W.d_tsum + tiles, sizeof(u64));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    const u64 need = ctx->h_scalars[9];
+    if (need > cap) return need;
+    if (fm->sa_rate > 1) {
+        fm_locate_rows_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(W.d_ranges, d_hoffs, npat, cap, d_hits);
+        TC_LAUNCH_CHECK(ctx);
+        if (need) {
+            fm_locate_walk_kernel<<<tc_cdiv(need, 256), 256, 0, s>>>(fm->d_bits, fm->d_marks, fm->lines, fm->d_tab,
+                                                                    fm->sigma_bytes, fm->d_L, fm->d_samples, fm->nsamples,
+                                                                    fm->N, fm->primary, fm->sa_rate, need, d_hits,
+                                                                    ctx->d_err);
+            TC_LAUNCH_CHECK(ctx);
+        }
+    } else {
+        fm_locate_fill_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(W.d_ranges, d_hoffs, fm->d_sa, npat, cap, d_hits);
+        TC_LAUNCH_CHECK(ctx);
+    }
+    return need;
+}
+
 int tc_fm_locate(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs,
                  uint64_t npat, uint64_t *hit_offs, uint64_t *hits, uint64_t *nhits) {
     TC_API_BEGIN(ctx)
@@ -2445,21 +2586,16 @@ int tc_fm_locate(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64
         memset(hit_offs, 0, (npat + 1) * sizeof(u64));
         return TC_OK;
     }
-    if (!fm->d_sa) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
+    if (!fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
     const u64 total = offs[npat];
-    const u64 tiles = tc_cdiv(npat, SCAN_TILE);
     u8 *d_pats = nullptr;
-    u64 *d_offs = nullptr, *d_ranges = nullptr, *d_len = nullptr, *d_hoffs = nullptr, *d_tsum = nullptr,
-        *d_hits = nullptr;
-    i64 *d_cnt = nullptr;
+    u64 *d_offs = nullptr, *d_hoffs = nullptr, *d_hits = nullptr;
+    FmLocateScratch W;
     auto carve = [&](Arena &A) {
         d_pats = A.get<u8>(total + 16);
         d_offs = A.get<u64>(npat + 1);
-        d_cnt = A.get<i64>(npat);
-        d_ranges = A.get<u64>(2 * npat);
-        d_len = A.get<u64>(npat + 1);
+        W.carve(A, npat);
         d_hoffs = A.get<u64>(npat + 1);
-        d_tsum = A.get<u64>(tiles + 2);
         d_hits = A.get<u64>(cap + 1);
     };
     Arena dry(nullptr);
@@ -2467,31 +2603,47 @@ int tc_fm_locate(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64
     tc_ws_reserve(ctx, dry.off);
     Arena A(ctx->ws);
     carve(A);
-    hipStream_t s = ctx->stream;
     tc_h2d(ctx, d_pats, pats, total);
     tc_h2d(ctx, d_offs, offs, (npat + 1) * sizeof(u64));
-    fm_count_device(ctx, fm, d_pats, d_offs, npat, d_cnt, d_ranges);
-    fm_cnt_to_u64_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(d_cnt, npat, d_len);
-    TC_LAUNCH_CHECK(ctx);
-    scan64_reduce_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(d_len, npat, d_tsum);
-    TC_LAUNCH_CHECK(ctx);
-    scan64_spine_kernel<<<1, 1024, 0, s>>>(d_tsum, tiles);
-    TC_LAUNCH_CHECK(ctx);
-    scan64_down_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(d_len, npat, d_tsum, d_hoffs);
-    TC_LAUNCH_CHECK(ctx);
-    tc_d2h(ctx, &ctx->h_scalars[9], d_tsum + tiles, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 need = ctx->h_scalars[9];
+    const u64 need = fm_locate_device(ctx, fm, W, d_pats, d_offs, npat, d_hoffs, d_hits, cap);
     *nhits = need;
     if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu hit slots, have %llu",
                             (unsigned long long)need, (unsigned long long)cap);
-    fm_locate_fill_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(d_ranges, d_hoffs, fm->d_sa, npat, cap,
-                                                            d_hits);
-    TC_LAUNCH_CHECK(ctx);
     tc_d2h(ctx, hit_offs, d_hoffs, npat * sizeof(u64));
     if (need) tc_d2h(ctx, hits, d_hits, need * sizeof(u64));
     tc_sync_check(ctx);
     hit_offs[npat] = need;
+    TC_API_END(ctx)
+}
+
+int tc_fm_locate_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs,
+                     uint64_t npat, uint64_t *d_hit_offs, uint64_t *d_hits, uint64_t *nhits) {
+    TC_API_BEGIN(ctx)
+    if (!fm || !nhits) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const u64 cap = *nhits;
+    *nhits = 0;
+    if (npat == 0) return TC_OK;
+    if (!d_pats || !d_offs || !d_hit_offs || (!d_hits && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (fm->n == 0) {
+        tc_memset_async(ctx, d_hit_offs, 0, (npat + 1) * sizeof(u64));
+        tc_sync_check(ctx);
+        return TC_OK;
+    }
+    if (!fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
+    FmLocateScratch W;
+    Arena dry(nullptr);
+    W.carve(dry, npat);
+    tc_ws_reserve(ctx, dry.off);
+    Arena A(ctx->ws);
+    W.carve(A, npat);
+    const u64 need = fm_locate_device(ctx, fm, W, d_pats, d_offs, npat, d_hit_offs, d_hits, cap);
+    *nhits = need;
+    TC_HIP(ctx, hipMemcpyAsync(d_hit_offs + npat, W.d_tsum + W.tiles, sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
+    if (need > cap) {
+        TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu hit slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
+    }
+    tc_sync_check(ctx);
     TC_API_END(ctx)
 }
 

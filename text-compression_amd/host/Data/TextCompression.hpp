@@ -209,6 +209,38 @@ inline CountResult bytestringFMIndexCountS(const std::vector<std::string> &pats,
 inline CountResult bytestringFMIndexCountP(const std::vector<std::string> &pats, const std::string &input) {
     return bytestringFMIndexCountS(pats, input);
 }
+
+// Not in the reference: an index that is kept between queries, optionally with a sampled suffix array (sa_rate > 1: every
+// sa_rate-th entry is kept and locate walks the LF mapping to the next one; textcomp.h), queried with everything in HBM.
+class Index {
+  public:
+    // text in host memory / text already on the device
+    Index(const std::string &text, uint32_t sa_rate = 1) {
+        Context::check(tc_fm_build_sampled(Context::get(), (const uint8_t *)text.data(), text.size(), sa_rate, &fm_));
+    }
+    Index(const uint8_t *d_text, uint64_t n, uint32_t sa_rate) {
+        Context::check(tc_fm_build_sampled_dev(Context::get(), d_text, n, sa_rate, &fm_));
+    }
+    Index(const Index &) = delete;
+    Index &operator=(const Index &) = delete;
+    ~Index() { tc_fm_free(fm_); }
+    uint32_t saRate() const { return tc_fm_sa_rate(fm_); }
+    // part 0: the whole index, part 1: its locate part alone
+    uint64_t deviceBytes(int part = 0) const { return tc_fm_device_bytes(fm_, part); }
+    // d_pats / d_offs [npat + 1] / d_hit_offs [npat + 1] / d_hits [cap]: device arrays.  Returns the number of hits; when it
+    // exceeds cap nothing was written to d_hits and the caller repeats the call with that capacity.
+    uint64_t locateDev(const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint64_t *d_hit_offs, uint64_t *d_hits,
+                       uint64_t cap) const {
+        uint64_t nh = cap;
+        int rc = tc_fm_locate_dev(Context::get(), fm_, d_pats, d_offs, npat, d_hit_offs, d_hits, &nh);
+        if (rc != TC_ERR_CAPACITY) Context::check(rc);
+        return nh;
+    }
+    const tc_fm *handle() const { return fm_; }
+
+  private:
+    tc_fm *fm_ = nullptr;
+};
 }  // namespace FMIndex
 
 }  // namespace Data

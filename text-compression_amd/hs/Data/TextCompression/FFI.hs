@@ -44,6 +44,17 @@ foreign import ccall safe "tc_fm_locate"
   c_tc_fm_locate :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Ptr Word64 -> Ptr Word64 -> Ptr Word64 -> IO Int32
 foreign import ccall unsafe "tc_fm_info"
   c_tc_fm_info :: Ptr TcFm -> Ptr Word64 -> Ptr Word32 -> Ptr Int16 -> Ptr Word64 -> Ptr Word64 -> IO Int32
+-- the index with a sampled suffix array (sa_rate: a power of two up to 4096; 1 = tc_fm_build) and locate with
+-- patterns and hits in device memory (no counterpart in the reference)
+foreign import ccall safe "tc_fm_build_sampled"
+  c_tc_fm_build_sampled :: Ptr TcCtx -> Ptr Word8 -> Word64 -> Word32 -> Ptr (Ptr TcFm) -> IO Int32
+foreign import ccall safe "tc_fm_build_sampled_dev"
+  c_tc_fm_build_sampled_dev :: Ptr TcCtx -> Ptr Word8 -> Word64 -> Word32 -> Ptr (Ptr TcFm) -> IO Int32
+foreign import ccall unsafe "tc_fm_sa_rate" c_tc_fm_sa_rate :: Ptr TcFm -> Word32
+foreign import ccall unsafe "tc_fm_device_bytes"
+  c_tc_fm_device_bytes :: Ptr TcFm -> Int32 -> Word64
+foreign import ccall safe "tc_fm_locate_dev"
+  c_tc_fm_locate_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Ptr Word64 -> Ptr Word64 -> Ptr Word64 -> IO Int32
 -- stored / shipped form (no counterpart in the reference): one record, or any length cut into records
 foreign import ccall unsafe "tc_container_bound"
   c_tc_container_bound :: Word64 -> Word32 -> Word64

@@ -344,29 +344,69 @@ class Context:
         return out[:got.value].tobytes()
 
     # ----------------------------------------------------------- FM-index
-    def fm_build(self, text):
-        return FMIndexHandle(self, text)
+    def fm_build(self, text, sa_rate=1):
+        """sa_rate > 1 (a power of two up to TC_FM_MAX_SA_RATE): keep every sa_rate-th suffix-array entry only
+        (tc_fm_build_sampled); locate answers the same hits by walking the LF mapping"""
+        return FMIndexHandle(self, text, sa_rate=sa_rate)
 
-    def fm_build_dev(self, d_text):
-        """index of a text that already lies in HBM (a torch uint8 tensor on this context's device): tc_fm_build_dev"""
+    def fm_build_dev(self, d_text, sa_rate=1):
+        """index of a text that already lies in HBM (a torch uint8 tensor on this context's device): tc_fm_build_dev /
+        tc_fm_build_sampled_dev"""
         h = C.c_void_p()
-        self._check(self.lib.tc_fm_build_dev(self.handle, C.c_void_p(d_text.data_ptr()) if d_text.numel() else None, d_text.numel(), C.byref(h)))
+        p = C.c_void_p(d_text.data_ptr()) if d_text.numel() else None
+        if sa_rate == 1:
+            self._check(self.lib.tc_fm_build_dev(self.handle, p, d_text.numel(), C.byref(h)))
+        else:
+            self._check(self.lib.tc_fm_build_sampled_dev(self.handle, p, d_text.numel(), int(sa_rate), C.byref(h)))
         return FMIndexHandle(self, None, _handle=h, _n=d_text.numel())
 
 
 class FMIndexHandle:
     """`tc_fm`: the device-resident FM-index of one text."""
 
-    def __init__(self, ctx, text, _handle=None, _n=0):
+    def __init__(self, ctx, text, _handle=None, _n=0, sa_rate=1):
         self._ctx = ctx
         if _handle is not None:      # an index that arrived from another GPU (textcomp.fmshard)
             self._h, self.n = _handle, _n
             return
         t = _u8(text)
         h = C.c_void_p()
-        ctx._check(ctx.lib.tc_fm_build(ctx.handle, _ptr(t) if len(t) else None, len(t), C.byref(h)))
+        if sa_rate == 1:
+            ctx._check(ctx.lib.tc_fm_build(ctx.handle, _ptr(t) if len(t) else None, len(t), C.byref(h)))
+        else:
+            ctx._check(ctx.lib.tc_fm_build_sampled(ctx.handle, _ptr(t) if len(t) else None, len(t), int(sa_rate), C.byref(h)))
         self._h = h
         self.n = len(t)
+
+    @property
+    def sa_rate(self):
+        """1: full suffix array; k > 1: every k-th entry kept; 0: no locate part (count-only import, empty index)"""
+        return int(self._ctx.lib.tc_fm_sa_rate(self._h))
+
+    def device_bytes(self, part=0):
+        """device bytes the index holds: part 0 = everything, 1 = the locate part alone"""
+        return int(self._ctx.lib.tc_fm_device_bytes(self._h, int(part)))
+
+    def locate_dev(self, d_pats, d_offs, npat, cap=None):
+        """patterns resident on the device (as count_dev) -> (hit_offs uint64-as-int64 tensor [npat + 1], hits tensor
+        [total], 1-based positions in SA order), both on the device: tc_fm_locate_dev"""
+        import torch
+        ctx = self._ctx
+        hoffs = torch.zeros(npat + 1, dtype=torch.int64, device=d_pats.device)
+        if npat == 0:
+            return hoffs, torch.zeros(0, dtype=torch.int64, device=d_pats.device)
+        cap = max(int(cap) if cap is not None else 2 * npat, 1)
+        for _ in range(2):
+            hits = torch.empty(cap, dtype=torch.int64, device=d_pats.device)
+            torch.cuda.synchronize()
+            nh = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_locate_dev(ctx.handle, self._h, C.c_void_p(d_pats.data_ptr()), C.c_void_p(d_offs.data_ptr()),
+                                          npat, C.c_void_p(hoffs.data_ptr()), C.c_void_p(hits.data_ptr()), C.byref(nh))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nh.value), 1)
+        ctx._check(rc)
+        return hoffs, hits[:int(nh.value)]
 
     def export_dev(self, with_locate=False):
         """The index as one device byte string (torch uint8 tensor) -- what a broadcast moves."""

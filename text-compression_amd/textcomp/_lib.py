@@ -14,6 +14,7 @@ TC_CONTAINER_HEADER = 640
 TC_MAX_SIGMA = 257
 TC_MAX_ROUNDS = 40
 TC_CODING_PACKED, TC_CODING_HUFFMAN = 0, 1
+TC_FM_MAX_SA_RATE = 4096
 
 ERR_NAMES = {-1: "TC_ERR_ARG", -2: "TC_ERR_CAPACITY", -3: "TC_ERR_MALFORMED", -4: "TC_ERR_HIP",
              -5: "TC_ERR_OOM", -6: "TC_ERR_INTERNAL", -7: "TC_ERR_NCCL"}
@@ -97,10 +98,15 @@ SYMBOLS = [
     ("tc_decode_stream", _INT, [_P, _P, _U64, _P, _PU64]),
     ("tc_fm_build", _INT, [_P, _P, _U64, C.POINTER(_P)]),
     ("tc_fm_build_dev", _INT, [_P, _P, _U64, C.POINTER(_P)]),
+    ("tc_fm_build_sampled", _INT, [_P, _P, _U64, _U32, C.POINTER(_P)]),
+    ("tc_fm_build_sampled_dev", _INT, [_P, _P, _U64, _U32, C.POINTER(_P)]),
+    ("tc_fm_sa_rate", _U32, [_P]),
+    ("tc_fm_device_bytes", _U64, [_P, _INT]),
     ("tc_fm_free", None, [_P]),
     ("tc_fm_count", _INT, [_P, _P, _P, _P, _U64, _P]),
     ("tc_fm_count_dev", _INT, [_P, _P, _P, _P, _U64, _P]),
     ("tc_fm_locate", _INT, [_P, _P, _P, _P, _U64, _P, _P, _PU64]),
+    ("tc_fm_locate_dev", _INT, [_P, _P, _P, _P, _U64, _P, _P, _PU64]),
     ("tc_fm_info", _INT, [_P, _PU64, _PU32, _P, _P, _PU64]),
     ("tc_comm_unique_id", _INT, [_P, _P]),
     ("tc_comm_create", _INT, [_P, _P, _INT, _INT, C.POINTER(_P)]),
