@@ -18,6 +18,7 @@ import pytest
 import classgen
 import huffman_format as H
 import oracle as O
+from huffman_cases import checksum64 as _checksum64, header as _header, resealed as _resealed, set_coding as _set
 
 pytestmark = pytest.mark.gpu
 
@@ -60,10 +61,6 @@ def _oracle_block(name):
     return _ORACLE[name]
 
 
-def _set(ctx, coding):
-    assert ctx.lib.tc_ctx_set_container_coding(ctx.handle, coding) == 0
-
-
 def _dev(text):
     import torch
     if len(text) == 0:
@@ -85,12 +82,6 @@ def _encode_dev(ctx, text, coding):
     finally:
         _set(ctx, PACKED)
     return buf[:used].cpu().numpy().tobytes(), buf, used
-
-
-def _header(blob):
-    magic, n, prim, nruns, nesc, body, csum, sigma, fmt = struct.unpack_from("<8s6Q2I", blob, 0)
-    assert magic == b"TCBLK01\0"
-    return dict(n=n, primary=prim, nruns=nruns, nesc=nesc, body=body, checksum=csum, sigma=sigma, format=fmt)
 
 
 def _to_block_dev(ctx, d_buf, used, nruns, n):
@@ -365,27 +356,6 @@ def test_two_contexts_two_codings_two_threads(ctx):
 
 
 # ---- 6 ------------------------------------------------------------------------------------------------------------------
-def _checksum64(body):
-    """tests/long/parity_digest.py:28, the numpy restatement of the container checksum"""
-    w = np.frombuffer(body, "<u4").astype(np.uint64)
-    i = np.arange(len(w), dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        z = ((w << np.uint64(32)) | (i & np.uint64(0xFFFFFFFF))) + (i >> np.uint64(32)) * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-        acc = int(z.sum(dtype=np.uint64))
-    return acc ^ ((len(body) * 0x9E3779B97F4A7C15) & ((1 << 64) - 1))
-
-
-def _resealed(blob, body):
-    """the container with another body, sizes and checksum made consistent so that only the body's content is wrong"""
-    b = bytearray(blob[:HDR]) + bytearray(body)
-    struct.pack_into("<Q", b, 40, len(body))
-    struct.pack_into("<Q", b, 48, _checksum64(bytes(body)))
-    return bytes(b)
-
-
 def test_malformed_bodies_are_refused(ctx):
     import torch
     text = TEXTS["acgtn_n65541"]
