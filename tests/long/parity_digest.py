@@ -3,7 +3,7 @@ restatement of BWT/Internal.hs:110-134, MTF/Internal.hs:128-175 and the RLE of t
 encodes the benchmark record itself -- seed 0xC3, n = 2^30 (BASELINE configs[2]) -- and the 16 MiB
 record of configs[1], and writes a DIGEST of the result to tests/golden/c3_digest.json: primary,
 sigma, final MTF list, number of runs and position-dependent 64-bit checksums of the last column,
-run_count[] and run_value[] (the function of checksum64_kernel in csrc/textcomp.hip, restated in
+run_count[] and run_value[] (the function of checksum64_kernel in csrc/tc_container_host.hpp, restated in
 numpy below).  tests/test_gpu_fullsize.py asserts that the device produces the same digest, which
 closes the gap between "round trip exact at 1 GiB" and "bit-exact against the oracle at 1 GiB".
 

@@ -90,10 +90,17 @@ def _texts():
 
 
 TEXTS = _texts()
+# TC_MTF_RLE=0 (read on every call) turns the one-kernel MTF + RLE off: a small alphabet then goes through rle_nib_kernel,
+# which shares its header and its seal with the one-kernel path.  The small shapes, on both sides of the 32 768-symbol tile
+# edge and the 32-nibble unit edge, with escape counts of 0 and >= 5, and one alphabet that falls through to the two-step way.
+NO_MTF_RLE = ["acgtn_n1", "acgtn_n17", "acgtn_n8193", "acgtn_n32769", "acgtn_n65541", "runs_1_to_6", "unary_tile", "sigma7"]
 
 
-@pytest.mark.parametrize("name", list(TEXTS), ids=list(TEXTS))
-def test_fused_container_is_the_two_step_container_and_the_oracles(ctx, name):
+@pytest.mark.parametrize("name,mtf_rle", [(k, None) for k in TEXTS] + [(k, "0") for k in NO_MTF_RLE],
+                         ids=list(TEXTS) + [k + "-mtf_rle0" for k in NO_MTF_RLE])
+def test_fused_container_is_the_two_step_container_and_the_oracles(ctx, monkeypatch, name, mtf_rle):
+    if mtf_rle is not None:
+        monkeypatch.setenv("TC_MTF_RLE", mtf_rle)
     text = TEXTS[name]
     fused, two, d_a, used = _both_ways(ctx, text)
     assert fused == two
@@ -124,7 +131,7 @@ def test_fused_container_is_the_two_step_container_and_the_oracles(ctx, name):
     assert d_out[:n].cpu().numpy().tobytes() == text.tobytes()
 
 
-def test_fused_container_empty_and_capacity(ctx):
+def test_fused_container_empty_and_capacity(ctx, monkeypatch):
     import torch
     buf = torch.zeros(4096, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
@@ -143,6 +150,12 @@ def test_fused_container_empty_and_capacity(ctx):
     used = C.c_uint64(100)
     assert ctx.lib.tc_encode_container_dev(ctx.handle, C.c_void_p(t.data_ptr()), 200000, C.c_void_p(small.data_ptr()), C.byref(used)) == -2
     assert ctx.lib.tc_encode_container_dev(ctx.handle, C.c_void_p(t.data_ptr()), 200000, C.c_void_p(small.data_ptr() + 4), C.byref(used)) == -1
+    # the too-small buffer again, by the way of rle_nib_kernel: the size it reports is enough (big holds the same bytes)
+    monkeypatch.setenv("TC_MTF_RLE", "0")
+    used = C.c_uint64(640 + 1000)
+    rc = ctx.lib.tc_encode_container_dev(ctx.handle, C.c_void_p(t.data_ptr()), 200000, C.c_void_p(small.data_ptr()), C.byref(used))
+    assert rc == -2 and 640 + 60000 < used.value <= need + 64
+    assert ctx.encode_container_dev(t.data_ptr(), 200000, big.data_ptr(), used.value) == need
 
 
 @pytest.mark.parametrize("n", [1 << 24, 1 << 28])

@@ -96,6 +96,17 @@ struct Arena {
 };
 
 void tc_ws_reserve(tc_ctx *ctx, size_t bytes);
+// The size-then-carve idiom: fn(Arena &, bool dry) runs dry to size its need, the workspace is reserved, then fn runs
+// on the workspace behind its first `base` bytes (the caller's own).  The reserve may move the workspace, so the
+// Arena fn carves from for real is made after it, and no pointer carved before this call outlives it.
+template <class F>
+static inline void tc_ws_plan(tc_ctx *ctx, size_t base, F &&fn) {
+    Arena dry(nullptr);
+    fn(dry, true);
+    tc_ws_reserve(ctx, base + dry.off);
+    Arena A(ctx->ws + base);
+    fn(A, false);
+}
 // co-resident grid for persistent kernels: CUs x blocks_per_cu (TC_GRID_SCALE_PCT env scales it)
 u32 tc_persistent_grid(tc_ctx *ctx, int blocks_per_cu);
 // same, capped by what the occupancy query admits for this kernel/block size

@@ -1215,11 +1215,7 @@ static void decode_device(tc_ctx *ctx, const tc_block *blk, u8 *d_text) {
         hi = A.off > hi ? A.off : hi;
         A.off = hi;
     };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    plan(A, false);
+    tc_ws_plan(ctx, 0, plan);
     tc_sync_check(ctx);
     if (n_out != n)
         TC_FAIL(ctx, TC_ERR_MALFORMED, "block decodes to %llu bytes, header says %llu",

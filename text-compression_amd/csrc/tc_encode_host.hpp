@@ -1546,31 +1546,51 @@ static bool mtf_rle_device(tc_ctx *ctx, Arena &A, BwtAcc acc, u64 N, const u32 *
 }
 
 // --------------------------------------------------------------- fused pipeline
+// The front of a fused encode, dry or for real: carves the last column and the index stream (N + idx_pad
+// elements: what the caller's later stages read behind it), sorts the suffixes between events 0 and 1, and
+// rewinds the arena to behind the two -- the suffix-sort buffers are dead, MTF / RLE scratch overlays them.
+// *end_sa: how far the sort reached (the caller's arena ends no lower).  Returns the accessor of the last column.
+static BwtAcc encode_sa_stage(tc_ctx *ctx, Arena &A, bool dry, const u8 *d_text, u64 n, u64 idx_pad, u16 **d_idx,
+                              u64 *primary, u32 *counts257, size_t *end_sa) {
+    const u64 N = n + 1;
+    u32 counts[256];
+    u8 *d_L = A.get<u8>(N + 16);
+    *d_idx = A.get<u16>(N + idx_pad);
+    const size_t mark = A.off;
+    if (!dry) TC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    sa_build(ctx, A, d_text, n, nullptr, d_L, primary, counts, dry);
+    *end_sa = A.off;
+    A.off = mark;
+    if (!dry) {
+        TC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        counts257[0] = 1;
+        for (int b = 0; b < 256; b++) counts257[1 + b] = counts[b];
+    }
+    return BwtAcc{d_L, (i64)*primary};
+}
+// the stage times of a fused encode, from events 0 .. 3 (recorded, and the stream synchronised)
+static void encode_stage_times(tc_ctx *ctx) {
+    tc_stats &st = ctx->stats;
+    (void)hipEventElapsedTime(&st.ms_sa, ctx->ev[0], ctx->ev[1]);
+    (void)hipEventElapsedTime(&st.ms_mtf, ctx->ev[1], ctx->ev[2]);
+    (void)hipEventElapsedTime(&st.ms_rle, ctx->ev[2], ctx->ev[3]);
+    (void)hipEventElapsedTime(&st.ms_total, ctx->ev[0], ctx->ev[3]);
+    st.ms_bwt = 0;  // the last column is produced inside the suffix-sort kernels
+}
+
 // bytestringToBWT -> bytestringBWTToMTFB -> runs of the index stream.
 static void encode_device(tc_ctx *ctx, const u8 *d_text, u64 n, tc_block *out, u64 cap) {
     const u64 N = n + 1;
     ctx->stats = tc_stats{};
     ctx->stats.n = n; ctx->stats.N = N;
-    u8 *d_L = nullptr;
-    u16 *d_idx = nullptr;
     u64 primary = 0, total = 0;
-    u32 counts[256], counts257[257];
+    u32 counts257[257];
     u32 sigma = 0;
     hipStream_t s = ctx->stream;
-    auto plan = [&](Arena &A, bool dry) {
-        d_L = A.get<u8>(N + 16);
-        d_idx = A.get<u16>(N);
-        size_t mark = A.off;
-        if (!dry) TC_HIP(ctx, hipEventRecord(ctx->ev[0], s));
-        sa_build(ctx, A, d_text, n, nullptr, d_L, &primary, counts, dry);
-        size_t end_sa = A.off;
-        A.off = mark;  // the suffix-sort buffers are dead: MTF / RLE scratch overlays them
-        if (!dry) {
-            TC_HIP(ctx, hipEventRecord(ctx->ev[1], s));
-            counts257[0] = 1;
-            for (int b = 0; b < 256; b++) counts257[1 + b] = counts[b];
-        }
-        BwtAcc acc{d_L, (i64)primary};
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool dry) {
+        u16 *d_idx = nullptr;
+        size_t end_sa = 0;
+        BwtAcc acc = encode_sa_stage(ctx, A, dry, d_text, n, 0, &d_idx, &primary, counts257, &end_sa);
         // small alphabets: the index stream between the two stages is one byte per symbol (the
         // same buffer, half used)
         bool idx8 = false;
@@ -1592,21 +1612,11 @@ static void encode_device(tc_ctx *ctx, const u8 *d_text, u64 n, tc_block *out, u
         }
         if (!dry) TC_HIP(ctx, hipEventRecord(ctx->ev[3], s));
         if (A.off < end_sa) A.off = end_sa;
-    };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    plan(A, false);
+    });
     tc_sync_check(ctx);
     out->n = n; out->primary = primary; out->sigma = sigma; out->nruns = total;
-    tc_stats &st = ctx->stats;
-    st.runs = total;
-    (void)hipEventElapsedTime(&st.ms_sa, ctx->ev[0], ctx->ev[1]);
-    (void)hipEventElapsedTime(&st.ms_mtf, ctx->ev[1], ctx->ev[2]);
-    (void)hipEventElapsedTime(&st.ms_rle, ctx->ev[2], ctx->ev[3]);
-    (void)hipEventElapsedTime(&st.ms_total, ctx->ev[0], ctx->ev[3]);
-    st.ms_bwt = 0;  // the last column is produced inside the suffix-sort kernels
+    ctx->stats.runs = total;
+    encode_stage_times(ctx);
     if (total > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu run slots, have %llu",
                              (unsigned long long)total, (unsigned long long)cap);
 }

@@ -540,11 +540,7 @@ static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 
         };
         ctx->stats = tc_stats{};
         ctx->stats.n = n; ctx->stats.N = N;
-        Arena dry(nullptr);
-        plan(dry, true);
-        tc_ws_reserve(ctx, dry.off);
-        Arena A(ctx->ws);
-        plan(A, false);
+        tc_ws_plan(ctx, 0, plan);
         // C[c] = #symbols of text.'$' smaller than c ('$' = Nothing counts once)
         u32 tab[768];
         const u32 sig = fm_make_tab(fm->counts, tab, fm->sym_of_code);

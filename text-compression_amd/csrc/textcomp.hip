@@ -9,6 +9,7 @@
 #include "tc_fm_host.hpp"
 #include "tc_pack.hpp"
 #include "tc_huff.hpp"
+#include "tc_container_host.hpp"
 #include "tc_comm.hpp"
 #include "textcomp_debug.h"
 
@@ -260,7 +261,7 @@ static void bwt_host(tc_ctx *ctx, const u8 *text, u64 n, u8 *L, u32 *sa, u64 *pr
     Arena dry(nullptr);
     plan(dry, true, d_text, d_L, d_sa);
     tc_ws_reserve(ctx, dry.off);
-    // carve input first, upload, then run
+    // carve input first, upload, then run (the upload between the reserve and the run is why this is no tc_ws_plan)
     {
         Arena A0(ctx->ws);
         u8 *t = A0.get<u8>(n + 16);
@@ -287,11 +288,7 @@ static void mtf_host(tc_ctx *ctx, const void *src, size_t src_bytes, bool is_sym
         (void)is_sym;
         mtf_encode_device<Acc>(ctx, A, acc, N, nullptr, d_idx, final_list, sigma, dry);
     };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    plan(A, false);
+    tc_ws_plan(ctx, 0, plan);
     tc_d2h(ctx, idx, d_idx, N * sizeof(u16));
     tc_sync_check(ctx);
 }
@@ -313,11 +310,7 @@ static void rle_host(tc_ctx *ctx, const void *src, size_t src_bytes, u64 N, i64 
         Acc acc = make_acc<Acc>(d_src, primary);
         rle_encode_device<Acc, SymT>(ctx, A, acc, N, d_counts, d_syms, cap, &total, dry);
     };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    plan(A, false);
+    tc_ws_plan(ctx, 0, plan);
     *nruns = total;
     if (total > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu run slots, have %llu",
                              (unsigned long long)total, (unsigned long long)cap);
@@ -434,11 +427,7 @@ static void ibwt_host(tc_ctx *ctx, const void *src, size_t src_bytes, u64 N, i64
         Acc acc = make_acc<Acc>(d_src, primary);
         ibwt_device<Acc>(ctx, A, acc, N, nullptr, d_text, n_out, dry);
     };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    plan(A, false);
+    tc_ws_plan(ctx, 0, plan);
     tc_sync_check(ctx);
     if (*n_out) {
         tc_d2h(ctx, text, d_text, *n_out);
@@ -463,11 +452,7 @@ static void rle_decode_host(tc_ctx *ctx, const u32 *counts, const SymT *syms, u6
         }
         rle_decode_device<SymT>(ctx, A, d_counts, d_syms, nruns, has_nothing, d_out, cap, &total, dry);
     };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    plan(A, false);
+    tc_ws_plan(ctx, 0, plan);
     *N = total;
     if (total > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu output slots, have %llu",
                              (unsigned long long)total, (unsigned long long)cap);
@@ -755,11 +740,7 @@ int tc_bwt_encode_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint8_t *d
     if (!d_text || !d_L) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
     ctx->stats = tc_stats{};
     ctx->stats.n = n; ctx->stats.N = n + 1;
-    Arena dry(nullptr);
-    sa_build(ctx, dry, d_text, n, nullptr, d_L, primary, nullptr, true);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    sa_build(ctx, A, d_text, n, nullptr, d_L, primary, nullptr, false);
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool dry) { sa_build(ctx, A, d_text, n, nullptr, d_L, primary, nullptr, dry); });
     tc_sync_check(ctx);
     TC_API_END(ctx)
 }
@@ -851,7 +832,6 @@ int tc_encode_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, tc_block *out)
 }
 
 
-u64 container_bound_any(u64 n);
 // ================================================== host buffers in and out (the path every Haskell caller takes)
 // bytestringToBWT and friends hand over a host ByteString (reference BWT.hs:68-70, RLE.hs:83-85).  Until round 3 the
 // host entry points paid a hipMalloc / hipFree per buffer per call and one blocking copy of a pageable buffer each
@@ -1094,11 +1074,7 @@ int tc_mtf_decode(tc_ctx *ctx, const uint16_t *idx, uint64_t N, const int16_t *l
         if (!dry) tc_h2d(ctx, d_idx, idx, N * sizeof(u16));
         mtf_decode_device(ctx, A, d_idx, N, list, nlist, d_sym, dry);
     };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    plan(A, false);
+    tc_ws_plan(ctx, 0, plan);
     tc_d2h(ctx, sym, d_sym, N * sizeof(i16));
     tc_sync_check(ctx);
     TC_API_END(ctx)
@@ -1167,182 +1143,13 @@ int tc_decode(tc_ctx *ctx, const tc_block *blk, uint8_t *text) {
     TC_API_END(ctx)
 }
 
-// ====================================================== encoded-block wire format
+// =============================== encoded-block wire format and container (host side: tc_container_host.hpp)
 uint64_t tc_block_packed_bound(uint64_t nruns, uint32_t sigma) {
     const int fmt = pack_format(sigma);
     // nibble stream: <= 1 byte per run + 16 bytes of padding per packer tile + 4-byte escapes
     if (fmt == 0) return nruns + 16 * ((nruns + PK_TILE - 1) / PK_TILE + 1) + 4 * nruns;
     // bytes + 8-byte alignment + worst-case escape list (every run escaping)
     return (((u64)fmt * nruns + 7) & ~7ull) + 8 * nruns + 8;
-}
-
-// ws_base: bytes at the start of the context's workspace that belong to the caller (the packer's scratch is
-// carved behind them; the caller has reserved block_pack_scratch() bytes there, so the workspace never moves)
-static size_t block_pack_scratch(u64 nruns) {
-    return (((size_t)(nruns / PR_TILE + nruns / PK_TILE + 8) * sizeof(u64) + 255) & ~(size_t)255) +
-           (((size_t)(nruns + 8) * sizeof(u32) + 255) & ~(size_t)255) + 512;
-}
-// the same for a context whose containers are Huffman-coded: the Huffman writer's scratch, or -- when the record falls
-// back to the packing -- the packer's, one after the other in the same place
-static size_t huff_scratch(u64 nruns) {
-    const size_t nchunks = (size_t)(nruns / HF_K + 1);
-    return (((size_t)HF_HIST_WORDS * sizeof(u32) + 255) & ~(size_t)255) + (((nchunks + 4) * sizeof(u32) + 255) & ~(size_t)255) +
-           (((nchunks + 2) * sizeof(u64) + 255) & ~(size_t)255);
-}
-static size_t container_scratch(const tc_ctx *ctx, u64 nruns) {
-    const size_t p = block_pack_scratch(nruns);
-    if (ctx->coding != TC_CODING_HUFFMAN) return p;
-    const size_t h = huff_scratch(nruns);
-    return p > h ? p : h;
-}
-static void block_pack_device(tc_ctx *ctx, const tc_block *blk, uint8_t *d_packed, uint64_t *packed_bytes,
-                              uint64_t *nesc, size_t ws_base = 0) {
-    if (!blk || !packed_bytes || !nesc) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    const u64 nruns = blk->nruns;
-    const u64 cap = *packed_bytes;
-    *packed_bytes = 0; *nesc = 0;
-    if (nruns == 0) return;
-    if (!d_packed || !blk->run_count || !blk->run_value) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    if (nruns > (u64)TC_MAX_N + 2) TC_FAIL(ctx, TC_ERR_ARG, "too many runs");
-    const int fmt = pack_format(blk->sigma);
-    if (fmt == 0) {
-        if ((uintptr_t)d_packed & 15) TC_FAIL(ctx, TC_ERR_ARG, "packed buffer must be 16-byte aligned");
-        const u32 ntiles = tc_cdiv(nruns, PK_TILE);
-        u64 *status = nullptr;
-        u32 *esc = nullptr;
-        // escape scratch: sized for the capacity the caller offers (an escape costs 4 bytes there)
-        const u64 esc_cap = cap / 4 < nruns ? cap / 4 : nruns;
-        auto carve = [&](Arena &A) {
-            status = A.get<u64>((size_t)ntiles + 2);
-            esc = A.get<u32>(esc_cap + 4);
-        };
-        Arena dry(nullptr);
-        carve(dry);
-        tc_ws_reserve(ctx, ws_base + dry.off);
-        Arena A(ctx->ws + ws_base);
-        carve(A);
-        tc_memset_async(ctx, status, 0, ((size_t)ntiles + 2) * sizeof(u64));
-        {   // tiles meet inside 16-byte units and complete them by atomicOr: the body must start out zero
-            const u64 most = ((2 * nruns + 31) / 32 + 1) * 16;     // at most two nibbles per run
-            tc_memset_async(ctx, d_packed, 0, most < (cap & ~15ull) ? most : (cap & ~15ull));
-        }
-        PackNibArgs a;
-        a.cnt = blk->run_count; a.val = blk->run_value; a.nruns = nruns;
-        a.out = d_packed; a.cap_units = cap / 16;
-        a.esc = esc; a.esc_cap = esc_cap;
-        a.status = status; a.ticket = reinterpret_cast<u32 *>(status + ntiles); a.err = ctx->d_err;
-        a.ntiles = ntiles;
-        u32 grid = tc_persistent_grid_for(ctx, pack_nib_kernel, PK_NT, 4);
-        if (grid > ntiles) grid = ntiles;
-        pack_nib_kernel<<<grid, PK_NT, 0, ctx->stream>>>(a);
-        TC_LAUNCH_CHECK(ctx);
-        tc_d2h(ctx, &ctx->h_scalars[14], status + (ntiles - 1), sizeof(u64));
-        tc_sync_check(ctx);
-        const u64 tot = LB_VALUE(ctx->h_scalars[14]);
-        const u64 body = (((tot >> NIB_LB_SHIFT) + 31) / 32) * 16, ne = NIB_LB_ESC(tot);
-        *nesc = ne;
-        *packed_bytes = body + 4 * ne;
-        if (*packed_bytes > cap || ne > esc_cap)
-            TC_FAIL(ctx, TC_ERR_CAPACITY, "packed runs need %llu bytes", (unsigned long long)*packed_bytes);
-        if (ne) {
-            TC_HIP(ctx, hipMemcpyAsync(d_packed + body, esc, 4 * ne, hipMemcpyDeviceToDevice, ctx->stream));
-            TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        return;
-    }
-    const int bpr = fmt;
-    const u64 body = ((u64)bpr * nruns + 7) & ~7ull;
-    if (body > cap) {
-        *packed_bytes = body;
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "packed runs need at least %llu bytes", (unsigned long long)body);
-    }
-    const u64 esc_cap = (cap - body) / 8;
-    u32 *esc = reinterpret_cast<u32 *>(d_packed + body);
-    const u32 tiles = tc_cdiv(nruns, PR_TILE);
-    u64 *tcnt = nullptr;
-    {
-        auto carve = [&](Arena &A) { tcnt = A.get<u64>((size_t)tiles + 2); };
-        Arena dry(nullptr);
-        carve(dry);
-        tc_ws_reserve(ctx, ws_base + dry.off);
-        Arena A(ctx->ws + ws_base);
-        carve(A);
-    }
-    if (body >= 8) tc_memset_async(ctx, d_packed + body - 8, 0, 8);   // the alignment padding is part of the bytes
-    pack_runs_count_kernel<<<tiles, 256, 0, ctx->stream>>>(blk->run_count, nruns, bpr, tcnt);
-    TC_LAUNCH_CHECK(ctx);
-    scan64_spine_kernel<<<1, 1024, 0, ctx->stream>>>(tcnt, tiles);
-    TC_LAUNCH_CHECK(ctx);
-    pack_runs_kernel<<<tiles, 256, 0, ctx->stream>>>(blk->run_count, blk->run_value, nruns, bpr, d_packed,
-                                                    esc, tcnt, esc_cap);
-    TC_LAUNCH_CHECK(ctx);
-    tc_d2h(ctx, &ctx->h_scalars[14], tcnt + tiles, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *nesc = ctx->h_scalars[14];
-    *packed_bytes = body + 8 * *nesc;
-    if (*nesc > esc_cap)
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "packed runs need %llu bytes", (unsigned long long)*packed_bytes);
-}
-
-static void block_unpack_device(tc_ctx *ctx, const uint8_t *d_packed, uint64_t packed_bytes, uint64_t nruns,
-                                uint32_t sigma, uint64_t nesc, tc_block *blk) {
-    if (!blk || blk->nruns < nruns) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    if (nruns == 0) { blk->nruns = 0; return; }
-    if (!d_packed || !blk->run_count || !blk->run_value) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    const int fmt = pack_format(sigma);
-    if (fmt == 0) {
-        if ((uintptr_t)d_packed & 15) TC_FAIL(ctx, TC_ERR_ARG, "packed buffer must be 16-byte aligned");
-        if (packed_bytes < 4 * nesc || ((packed_bytes - 4 * nesc) & 15) || nesc > nruns)
-            TC_FAIL(ctx, TC_ERR_MALFORMED, "packed block: %llu bytes do not hold a nibble body and %llu escapes",
-                    (unsigned long long)packed_bytes, (unsigned long long)nesc);
-        const u64 body = packed_bytes - 4 * nesc, units = body / 16;
-        if (units > (u64)nruns + (nruns + PK_TILE - 1) / PK_TILE + 1)  // > 1 byte per run + padding
-            TC_FAIL(ctx, TC_ERR_MALFORMED, "packed block: body too long for %llu runs", (unsigned long long)nruns);
-        const u32 ntiles = tc_cdiv(units, UP_TILE_UNITS);
-        u64 *status = nullptr;
-        auto carve = [&](Arena &A) { status = A.get<u64>((size_t)ntiles + 2); };
-        Arena dry(nullptr);
-        carve(dry);
-        tc_ws_reserve(ctx, dry.off);
-        Arena A(ctx->ws);
-        carve(A);
-        tc_memset_async(ctx, status, 0, ((size_t)ntiles + 2) * sizeof(u64));
-        UnpackNibArgs a;
-        a.body = d_packed; a.units = units;
-        a.esc = reinterpret_cast<const u32 *>(d_packed + body); a.nesc = nesc; a.nruns = nruns;
-        a.cnt = blk->run_count; a.val = blk->run_value;
-        a.status = status; a.ticket = reinterpret_cast<u32 *>(status + ntiles); a.err = ctx->d_err;
-        a.ntiles = ntiles;
-        u32 grid = tc_persistent_grid_for(ctx, unpack_nib_kernel, UP_NT, 4);
-        if (grid > ntiles) grid = ntiles;
-        unpack_nib_kernel<<<grid, UP_NT, 0, ctx->stream>>>(a);
-        TC_LAUNCH_CHECK(ctx);
-        tc_d2h(ctx, &ctx->h_scalars[14], status + (ntiles - 1), sizeof(u64));
-        tc_sync_check(ctx);
-        const u64 tot = LB_VALUE(ctx->h_scalars[14]);
-        if ((tot >> 31) != nruns || (tot & 0x7fffffffull) != nesc)
-            TC_FAIL(ctx, TC_ERR_MALFORMED, "packed block holds %llu runs / %llu escapes, header says %llu / %llu",
-                    (unsigned long long)(tot >> 31), (unsigned long long)(tot & 0x7fffffffull),
-                    (unsigned long long)nruns, (unsigned long long)nesc);
-        blk->nruns = nruns;
-        blk->sigma = sigma;
-        return;
-    }
-    const int bpr = fmt;
-    const u64 body = ((u64)bpr * nruns + 7) & ~7ull;
-    if (packed_bytes < body + 8 * nesc) TC_FAIL(ctx, TC_ERR_MALFORMED, "packed block too short");
-    u32 grid = tc_cdiv(nruns, 256 * 8);
-    if (grid > 8192) grid = 8192;
-    unpack_runs_kernel<<<grid, 256, 0, ctx->stream>>>(d_packed, nruns, bpr, blk->run_count, blk->run_value);
-    TC_LAUNCH_CHECK(ctx);
-    if (nesc) {
-        unpack_esc_kernel<<<tc_cdiv(nesc, 256), 256, 0, ctx->stream>>>(
-            reinterpret_cast<const u32 *>(d_packed + body), nesc, nruns, blk->run_count);
-        TC_LAUNCH_CHECK(ctx);
-    }
-    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    blk->nruns = nruns;
-    blk->sigma = sigma;
 }
 
 int tc_block_pack_dev(tc_ctx *ctx, const tc_block *blk, uint8_t *d_packed, uint64_t *packed_bytes,
@@ -1359,528 +1166,8 @@ int tc_block_unpack_dev(tc_ctx *ctx, const uint8_t *d_packed, uint64_t packed_by
     TC_API_END(ctx)
 }
 
-// ====================================================== encoded-block container
-// header (TC_CONTAINER_HEADER bytes, little-endian) + packed runs; SURVEY 8f-4
-struct ContainerHeader {
-    char magic[8];       // "TCBLK01\0"
-    u64 n, primary, nruns, nesc, body_bytes, checksum;
-    u32 sigma, format;
-    i16 final_list[TC_MAX_SIGMA];
-};
-static_assert(sizeof(ContainerHeader) <= TC_CONTAINER_HEADER, "container header layout");
-static const char kContainerMagic[8] = {'T', 'C', 'B', 'L', 'K', '0', '1', 0};
-
-// the sum a thread of a grid of 256-thread workgroups contributes: word i weighs in by a mix of (word, i); four loads
-// in flight per thread (one per loop turn left the memory latency exposed)
-__device__ __forceinline__ u64 checksum64_term(u32 word, u64 i) {
-    u64 z = ((u64)word << 32 | (u32)i) + (i >> 32) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ u64 checksum64_partial(const u32 *__restrict__ w, u64 nwords) {
-    const u64 stride = (u64)gridDim.x * 256;
-    u64 i = (u64)blockIdx.x * 256 + threadIdx.x, acc = 0;
-    for (; i + 3 * stride < nwords; i += 4 * stride) {
-        const u32 a = w[i], b = w[i + stride], c = w[i + 2 * stride], d = w[i + 3 * stride];
-        acc += checksum64_term(a, i) + checksum64_term(b, i + stride) + checksum64_term(c, i + 2 * stride) + checksum64_term(d, i + 3 * stride);
-    }
-    for (; i < nwords; i += stride) acc += checksum64_term(w[i], i);
-    return acc;
-}
-// position-dependent 64-bit checksum of a byte range (16-byte aligned, length a multiple of 4)
-__global__ __launch_bounds__(256) void checksum64_kernel(const u32 *__restrict__ w, u64 nwords, u64 *out) {
-    u64 acc = checksum64_partial(w, nwords);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if (lane_id() == 0 && acc) atomicAdd((unsigned long long *)out, (unsigned long long)acc);
-}
-static u64 checksum64_device(tc_ctx *ctx, const u8 *d_p, u64 bytes) {
-    u64 *d_sum = ctx->d_scalars + 16;
-    tc_memset_async(ctx, d_sum, 0, sizeof(u64));
-    const u64 nwords = bytes / 4;
-    if (nwords) {
-        u32 grid = tc_cdiv(nwords, 256 * 16);
-        if (grid > 4096) grid = 4096;
-        checksum64_kernel<<<grid, 256, 0, ctx->stream>>>(reinterpret_cast<const u32 *>(d_p), nwords, d_sum);
-        TC_LAUNCH_CHECK(ctx);
-    }
-    tc_d2h(ctx, &ctx->h_scalars[16], d_sum, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return ctx->h_scalars[16] ^ (bytes * 0x9E3779B97F4A7C15ull);
-}
-
-// ---- the Huffman body (format 3; tc_huff.hpp, layout in include/textcomp.h) ------------------------------------------
-// Writes blk's runs as a Huffman body into d_body (*body_bytes: in capacity, out bytes used) and returns true -- or
-// returns false, nothing of value written, when the record is to be packed instead: the Huffman body would not be
-// strictly smaller than the packed one (whose size the histogram pass has summed from the counts), or a run has no
-// token (count 0, value >= sigma).  Two host synchronisations of its own: the histogram, and the payload size.
-static bool huff_write_device(tc_ctx *ctx, const tc_block *blk, u8 *d_body, u64 *body_bytes, size_t ws_base) {
-    const u64 nruns = blk->nruns, cap = *body_bytes;
-    const u32 sigma = blk->sigma;
-    if (nruns == 0 || sigma == 0) return false;
-    if (!blk->run_count || !blk->run_value) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    if (nruns > (u64)TC_MAX_N + 2) TC_FAIL(ctx, TC_ERR_ARG, "too many runs");
-    const u32 nsyms = sigma + 2;
-    const u32 nchunks = tc_cdiv(nruns, HF_K);
-    u32 *hist = nullptr, *dirbits = nullptr;
-    u64 *offs = nullptr;
-    auto carve = [&](Arena &A) {
-        hist = A.get<u32>(HF_HIST_WORDS);
-        dirbits = A.get<u32>((size_t)nchunks + 4);
-        offs = A.get<u64>((size_t)nchunks + 2);
-    };
-    Arena dry(nullptr);
-    carve(dry);
-    tc_ws_reserve(ctx, ws_base + dry.off);
-    Arena A(ctx->ws + ws_base);
-    carve(A);
-    hipStream_t s = ctx->stream;
-    tc_memset_async(ctx, hist, 0, HF_HIST_WORDS * sizeof(u32));
-    u32 grid = tc_persistent_grid(ctx, 8);
-    {
-        HuffHistArgs a;
-        a.cnt = blk->run_count; a.val = blk->run_value; a.nruns = nruns; a.sigma = sigma; a.hist = hist;
-        const u32 g = tc_cdiv(nruns, HF_NT * 4);
-        huff_hist_kernel<<<g < grid ? g : grid, HF_NT, 0, s>>>(a);
-        TC_LAUNCH_CHECK(ctx);
-    }
-    u32 h_hist[HF_HIST_WORDS];
-    tc_d2h(ctx, h_hist, hist, sizeof h_hist);
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    u64 tot[HF_TOT_WORDS / 2];
-    memcpy(tot, h_hist + 264, sizeof tot);
-    if (tot[4]) return false;   // a run without a token: such a block is packed
-    const int fmt = pack_format(sigma);
-    const u64 packed = fmt == 0 ? ((tot[0] + 31) / 32) * 16 + 4 * tot[1]
-                                : (((u64)fmt * nruns + 7) & ~7ull) + 8 * (fmt == 1 ? tot[2] : tot[3]);
-    const u64 fixed = hf_fixed_bytes(nsyms, nchunks);
-    if (fixed + 16 >= packed) return false;   // head, lengths and directory alone outweigh the packed body
-    u8 len[HF_MAXSYM + 1];
-    huff_build_lengths(h_hist, nsyms, len);
-    HuffEncArgs e;
-    huff_assign_codes(len, nsyms, &e.codes);
-    e.cnt = blk->run_count; e.val = blk->run_value; e.nruns = nruns; e.sigma = sigma; e.nchunks = nchunks;
-    e.dirbits = dirbits; e.offs = offs; e.payload = nullptr; e.payload_words = 0;
-    if (grid > nchunks) grid = nchunks;
-    huff_encode_kernel<false><<<grid, HF_NT, 0, s>>>(e);
-    TC_LAUNCH_CHECK(ctx);
-    huff_dir_scan_kernel<<<1, HF_SCAN_NT, 0, s>>>(dirbits, nchunks, offs);
-    TC_LAUNCH_CHECK(ctx);
-    tc_d2h(ctx, &ctx->h_scalars[14], offs + nchunks, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 words = ctx->h_scalars[14];
-    const u64 body = fixed + hf_pad16(4 * words);
-    if (body >= packed) return false;
-    *body_bytes = body;
-    if (body > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "container body needs %llu bytes", (unsigned long long)body);
-    if (!d_body) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    // head and lengths (through the pinned header staging, which is idle until the container's header is written)
-    const u64 lens_off = 16, dir_off = 16 + hf_pad16(nsyms), pay_off = fixed;
-    u8 *stage = ctx->h_hdr;
-    memset(stage, 0, (size_t)dir_off);
-    const u32 head[4] = {HF_K, nchunks, nsyms, HF_LMAX};
-    memcpy(stage, head, 16);
-    memcpy(stage + lens_off, len, nsyms);
-    tc_h2d(ctx, d_body, stage, (size_t)dir_off);
-    tc_memset_async(ctx, d_body + body - 16, 0, 16);                 // the payload's padding
-    tc_memset_async(ctx, d_body + pay_off - 16, 0, 16);             // the directory's padding
-    TC_HIP(ctx, hipMemcpyAsync(d_body + dir_off, dirbits, 4 * (size_t)nchunks, hipMemcpyDeviceToDevice, s));
-    e.payload = reinterpret_cast<u32 *>(d_body + pay_off);
-    e.payload_words = words;
-    huff_encode_kernel<true><<<grid, HF_NT, 0, s>>>(e);
-    TC_LAUNCH_CHECK(ctx);
-    return true;
-}
-
-// Inverse: validates head, lengths and directory, then fills blk->run_count / run_value (device, capacity
-// blk->nruns >= nruns).  Anything that is not a body of exactly nruns runs is TC_ERR_MALFORMED.
-static void huff_read_device(tc_ctx *ctx, const u8 *d_body, u64 body_bytes, u64 nruns, u32 sigma, tc_block *blk) {
-    if (!blk || blk->nruns < nruns) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    if (nruns == 0 || sigma == 0 || sigma > TC_MAX_SIGMA) TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body without runs");
-    if (!d_body || !blk->run_count || !blk->run_value) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    const u32 nsyms = sigma + 2;
-    const u64 dir_off = 16 + hf_pad16(nsyms);
-    if (body_bytes < dir_off || (body_bytes & 15)) TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body too short");
-    hipStream_t s = ctx->stream;
-    u8 fix[16 + ((HF_MAXSYM + 15) & ~15)];
-    tc_d2h(ctx, fix, d_body, (size_t)dir_off);
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    u32 head[4];
-    memcpy(head, fix, 16);
-    const u32 K = head[0], nchunks = head[1], lmax = head[3];
-    if (K == 0 || (K & (K - 1)) || head[2] != nsyms || lmax < 1 || lmax > HF_LMAX ||
-        (u64)nchunks != (nruns + K - 1) / K)
-        TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body: bad head (K %u, chunks %u, symbols %u, longest code %u)", K, nchunks,
-                head[2], lmax);
-    u64 kraft = 0;   // in units of 2^-lmax
-    for (u32 i = 0; i < nsyms; i++) {
-        const u32 l = fix[16 + i];
-        if (l > lmax) TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body: code length %u above %u", l, lmax);
-        if (l) kraft += 1ull << (lmax - l);
-    }
-    if (kraft > (1ull << lmax)) TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body: code lengths are no prefix code");
-    const u64 fixed = hf_fixed_bytes(nsyms, nchunks);
-    if (fixed > body_bytes) TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body: directory longer than the body");
-    const u64 payload_words = (body_bytes - fixed) / 4;
-    u64 *offs = nullptr;
-    auto carve = [&](Arena &A) { offs = A.get<u64>((size_t)nchunks + 2); };
-    Arena dry(nullptr);
-    carve(dry);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    carve(A);
-    const u32 *dirbits = reinterpret_cast<const u32 *>(d_body + dir_off);
-    huff_dir_scan_kernel<<<1, HF_SCAN_NT, 0, s>>>(dirbits, nchunks, offs);
-    TC_LAUNCH_CHECK(ctx);
-    tc_d2h(ctx, &ctx->h_scalars[14], offs + nchunks, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 words = ctx->h_scalars[14];
-    if (((words + 3) & ~3ull) != payload_words)
-        TC_FAIL(ctx, TC_ERR_MALFORMED, "Huffman body: directory sums to %llu words, payload has %llu",
-                (unsigned long long)words, (unsigned long long)payload_words);
-    HuffDecArgs a;
-    a.len = d_body + 16; a.dirbits = dirbits; a.offs = offs;
-    a.payload = reinterpret_cast<const u32 *>(d_body + fixed); a.payload_words = payload_words;
-    a.nruns = nruns; a.K = K; a.nchunks = nchunks; a.sigma = sigma; a.lmax = lmax;
-    a.cnt = blk->run_count; a.val = blk->run_value; a.err = ctx->d_err;
-    u32 grid = tc_persistent_grid(ctx, 8);
-    const u32 g = tc_cdiv(nchunks, HF_NT);
-    huff_decode_kernel<<<g < grid ? g : grid, HF_NT, 0, s>>>(a);
-    TC_LAUNCH_CHECK(ctx);
-    tc_sync_check(ctx);
-    blk->nruns = nruns;
-    blk->sigma = sigma;
-}
-
 uint64_t tc_container_bound(uint64_t nruns, uint32_t sigma) {
     return TC_CONTAINER_HEADER + tc_block_packed_bound(nruns, sigma);
-}
-
-static void container_write_device(tc_ctx *ctx, const tc_block *blk, u8 *d_out, u64 *bytes, size_t ws_base = 0) {
-    if (!blk || !bytes) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    const u64 cap = *bytes;
-    *bytes = 0;
-    if (!d_out || ((uintptr_t)d_out & 15)) TC_FAIL(ctx, TC_ERR_ARG, "container buffer must be 16-byte aligned");
-    if (blk->sigma > TC_MAX_SIGMA) TC_FAIL(ctx, TC_ERR_ARG, "bad block");
-    if (cap < TC_CONTAINER_HEADER) {
-        *bytes = tc_container_bound(blk->nruns, blk->sigma);
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "container needs at least %llu bytes", (unsigned long long)*bytes);
-    }
-    ContainerHeader h;
-    memset(&h, 0, sizeof h);
-    memcpy(h.magic, kContainerMagic, 8);
-    h.n = blk->n; h.primary = blk->primary; h.nruns = blk->nruns; h.sigma = blk->sigma;
-    h.format = (u32)pack_format(blk->sigma);
-    for (u32 i = 0; i < blk->sigma; i++) h.final_list[i] = blk->final_list[i];
-    u64 body = cap - TC_CONTAINER_HEADER, nesc = 0;
-    try {
-        if (ctx->coding == TC_CODING_HUFFMAN && huff_write_device(ctx, blk, d_out + TC_CONTAINER_HEADER, &body, ws_base)) {
-            h.format = HF_FORMAT;
-        } else {
-            body = cap - TC_CONTAINER_HEADER;
-            block_pack_device(ctx, blk, d_out + TC_CONTAINER_HEADER, &body, &nesc, ws_base);
-        }
-    } catch (const TcFail &f) {
-        if (f.code == TC_ERR_CAPACITY) *bytes = TC_CONTAINER_HEADER + body;
-        throw;
-    }
-    h.nesc = nesc; h.body_bytes = body;
-    h.checksum = checksum64_device(ctx, d_out + TC_CONTAINER_HEADER, body);
-    u8 hdr[TC_CONTAINER_HEADER];
-    memset(hdr, 0, sizeof hdr);
-    memcpy(hdr, &h, sizeof h);
-    tc_h2d(ctx, d_out, hdr, TC_CONTAINER_HEADER);
-    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *bytes = TC_CONTAINER_HEADER + body;
-}
-
-// parses + validates the header (host copy); returns it
-static ContainerHeader container_header(tc_ctx *ctx, const u8 *d_in, u64 bytes) {
-    if (!d_in || ((uintptr_t)d_in & 15)) TC_FAIL(ctx, TC_ERR_ARG, "container buffer must be 16-byte aligned");
-    if (bytes < TC_CONTAINER_HEADER) TC_FAIL(ctx, TC_ERR_MALFORMED, "container shorter than its header");
-    u8 hdr[TC_CONTAINER_HEADER];
-    tc_d2h(ctx, hdr, d_in, TC_CONTAINER_HEADER);
-    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ContainerHeader h;
-    memcpy(&h, hdr, sizeof h);
-    if (memcmp(h.magic, kContainerMagic, 8) != 0) TC_FAIL(ctx, TC_ERR_MALFORMED, "not a textcomp container");
-    if (h.n > TC_MAX_N || h.sigma > TC_MAX_SIGMA || h.nruns > (u64)TC_MAX_N + 2 || h.nesc > h.nruns ||
-        (h.format != (u32)pack_format(h.sigma) && !(h.format == HF_FORMAT && h.nesc == 0)) || h.body_bytes != bytes - TC_CONTAINER_HEADER ||
-        (h.n > 0 && (h.primary > h.n || h.nruns == 0)))
-        TC_FAIL(ctx, TC_ERR_MALFORMED, "container header is inconsistent");
-    return h;
-}
-
-static void container_read_device(tc_ctx *ctx, const u8 *d_in, u64 bytes, tc_block *blk) {
-    if (!blk) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    const ContainerHeader h = container_header(ctx, d_in, bytes);
-    if (blk->nruns < h.nruns) {
-        blk->nruns = h.nruns;
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "block needs %llu run slots", (unsigned long long)h.nruns);
-    }
-    if (checksum64_device(ctx, d_in + TC_CONTAINER_HEADER, h.body_bytes) != h.checksum)
-        TC_FAIL(ctx, TC_ERR_MALFORMED, "container checksum mismatch");
-    if (h.format == HF_FORMAT) huff_read_device(ctx, d_in + TC_CONTAINER_HEADER, h.body_bytes, h.nruns, h.sigma, blk);
-    else block_unpack_device(ctx, d_in + TC_CONTAINER_HEADER, h.body_bytes, h.nruns, h.sigma, h.nesc, blk);
-    blk->n = h.n; blk->primary = h.primary; blk->sigma = h.sigma; blk->nruns = h.nruns;
-    for (u32 i = 0; i < h.sigma; i++) blk->final_list[i] = h.final_list[i];
-}
-
-// ---- text -> container on the device, the runs never leaving the chip for a small alphabet -----------------
-// What the multi-GPU step ships is the container, not the run arrays: for sigma <= 6 (an ACGTN record) the RLE
-// stage writes the container's nibble stream itself (rle_nib_kernel, tc_pack.hpp) and three small kernels seal
-// the container on the device -- escape list behind the body, checksum, header fields -- so the call has one
-// host synchronisation of its own (the sizes it returns).  Larger alphabets take the two-step way (run arrays
-// in the workspace, then the byte packers).  The bytes are those of tc_encode_dev + tc_block_to_container_dev.
-__global__ __launch_bounds__(256) void nib_escapes_kernel(const u64 *__restrict__ totals, const u32 *__restrict__ esc,
-                                                          u8 *__restrict__ body, u64 cap_bytes, u64 esc_cap) {
-    const u64 units = (totals[1] + 31) >> 5;
-    u64 nesc = totals[2];
-    if (nesc > esc_cap) nesc = esc_cap;
-    u32 *dst = reinterpret_cast<u32 *>(body + 16 * units);
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < nesc; i += (u64)gridDim.x * 256)
-        if (16 * units + 4 * (i + 1) <= cap_bytes) dst[i] = esc[i];
-}
-// checksum64_kernel over a body whose length is known on the device only
-__global__ __launch_bounds__(256) void checksum64_dyn_kernel(const u32 *__restrict__ w, const u64 *__restrict__ totals,
-                                                             u64 cap_bytes, u64 *out) {
-    u64 nwords = 4 * ((totals[1] + 31) >> 5) + totals[2];
-    if (nwords > cap_bytes / 4) nwords = cap_bytes / 4;
-    u64 acc = checksum64_partial(w, nwords);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if (lane_id() == 0 && acc) atomicAdd((unsigned long long *)out, (unsigned long long)acc);
-}
-// header fields that only the device knows: nruns @24, nesc @32, body_bytes @40, checksum @48 (ContainerHeader)
-__global__ void container_seal_kernel(u8 *hdr, const u64 *totals, const u64 *sum, u64 *result) {
-    const u64 nruns = totals[0], nesc = totals[2], body = 16 * ((totals[1] + 31) >> 5) + 4 * nesc;
-    u64 *h = reinterpret_cast<u64 *>(hdr);
-    h[3] = nruns; h[4] = nesc; h[5] = body;
-    h[6] = *sum ^ (body * 0x9E3779B97F4A7C15ull);
-    result[0] = nruns; result[1] = nesc; result[2] = body;
-}
-
-static void encode_container_device(tc_ctx *ctx, const u8 *d_text, u64 n, u8 *d_out, u64 *bytes) {
-    const u64 cap = *bytes;
-    *bytes = 0;
-    if (!d_out || ((uintptr_t)d_out & 15)) TC_FAIL(ctx, TC_ERR_ARG, "container buffer must be 16-byte aligned");
-    if (cap < TC_CONTAINER_HEADER) {
-        *bytes = tc_container_bound(n + 2, TC_MAX_SIGMA);
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "container needs at least %d bytes", TC_CONTAINER_HEADER);
-    }
-    if (n == 0) {   // empty in, empty out: a header with no runs
-        tc_block e;
-        memset(&e, 0, sizeof e);
-        *bytes = cap;
-        container_write_device(ctx, &e, d_out, bytes, 0);
-        return;
-    }
-    const u64 N = n + 1;
-    ctx->stats = tc_stats{};
-    ctx->stats.n = n; ctx->stats.N = N;
-    u8 *d_L = nullptr;
-    u16 *d_idx = nullptr;
-    u64 primary = 0;
-    u32 counts[256], counts257[257];
-    u32 sigma = 0;
-    i16 final_list[TC_MAX_SIGMA];
-    hipStream_t s = ctx->stream;
-    static_assert(RN_TILE == MTF_TILE, "one tile count for the nibble-stream kernels");
-    const u32 ntiles = tc_cdiv(N, RN_TILE);
-    const u64 esc_cap = N / 5 + 16;
-    bool fused = false;
-    // a Huffman-coded container is written from the run arrays (as sigma > 6 is): neither fused nibble path is taken
-    const bool huff = ctx->coding == TC_CODING_HUFFMAN;
-    tc_block blk;
-    memset(&blk, 0, sizeof blk);
-    size_t pack_base = 0;
-    u64 *status = nullptr;
-    auto plan = [&](Arena &A, bool dry) {
-        d_L = A.get<u8>(N + 16);
-        d_idx = A.get<u16>(N + 16);
-        size_t mark = A.off;
-        if (!dry) TC_HIP(ctx, hipEventRecord(ctx->ev[0], s));
-        sa_build(ctx, A, d_text, n, nullptr, d_L, &primary, counts, dry);
-        size_t end_sa = A.off;
-        A.off = mark;
-        if (!dry) {
-            TC_HIP(ctx, hipEventRecord(ctx->ev[1], s));
-            counts257[0] = 1;
-            for (int b = 0; b < 256; b++) counts257[1 + b] = counts[b];
-        }
-        BwtAcc acc{d_L, (i64)primary};
-        bool idx8 = false;
-        // a record over <= 6 symbols: MTF, RLE and the wire format in ONE kernel (tc_pack.hpp, mtf_rle_kernel<true>);
-        // its scratch first (the dry run does not know sigma yet)
-        u64 *fstatus = A.get<u64>(2 * (size_t)ntiles + 32);
-        u32 *fesc = A.get<u32>(esc_cap);
-        auto write_header = [&]() {   // what the host knows of the header; the seal kernel fills in the rest
-            ContainerHeader h;
-            memset(&h, 0, sizeof h);
-            memcpy(h.magic, kContainerMagic, 8);
-            h.n = n; h.primary = primary; h.sigma = sigma; h.format = (u32)pack_format(sigma);
-            for (u32 i = 0; i < sigma; i++) h.final_list[i] = final_list[i];
-            memset(ctx->h_hdr, 0, TC_CONTAINER_HEADER);
-            memcpy(ctx->h_hdr, &h, sizeof h);
-            tc_h2d(ctx, d_out, ctx->h_hdr, TC_CONTAINER_HEADER);
-        };
-        auto seal = [&](u64 *totals, u32 *esc_list) {
-            u8 *body = d_out + TC_CONTAINER_HEADER;
-            const u64 body_cap = cap - TC_CONTAINER_HEADER;
-            u64 *sum = totals + 4, *result = totals + 5;
-            nib_escapes_kernel<<<64, 256, 0, s>>>(totals, esc_list, body, body_cap, esc_cap);
-            TC_LAUNCH_CHECK(ctx);
-            checksum64_dyn_kernel<<<4096, 256, 0, s>>>(reinterpret_cast<const u32 *>(body), totals, body_cap, sum);
-            TC_LAUNCH_CHECK(ctx);
-            container_seal_kernel<<<1, 1, 0, s>>>(d_out, totals, sum, result);
-            TC_LAUNCH_CHECK(ctx);
-            TC_HIP(ctx, hipEventRecord(ctx->ev[3], s));
-            tc_d2h(ctx, &ctx->h_scalars[20], result, 3 * sizeof(u64));
-        };
-        bool one_kernel = false;
-        if (!dry && !huff && env_int("TC_MTF_RLE", 1) != 0 && env_int("TC_MTF_FORCE_GENERAL", 0) == 0 && N + 64 < (1ull << 32)) {
-            Alphabet al;
-            al.build(counts257);
-            if (al.sigma <= PK_NIB_SIGMA) {
-                u8 *body = d_out + TC_CONTAINER_HEADER;
-                const u64 body_cap = cap - TC_CONTAINER_HEADER;
-                const u64 most = ((N + 31) / 32 + 1) * 16;       // at most one nibble per symbol
-                tc_memset_async(ctx, fstatus, 0, (2 * (size_t)ntiles + 32) * sizeof(u64));
-                tc_memset_async(ctx, body, 0, most < (body_cap & ~15ull) ? most : (body_cap & ~15ull));
-                MtfRleArgs a;
-                memset(&a, 0, sizeof a);
-                for (int v = 0; v < 257; v++) a.lut.v[v] = (u8)al.code_of_sym[v];
-                a.acc = acc; a.N = N; a.sigma = al.sigma;
-                a.status_a = fstatus; a.status_b = fstatus + ntiles;
-                a.ticket = reinterpret_cast<u32 *>(fstatus + 2 * (size_t)ntiles);
-                a.flag = reinterpret_cast<u32 *>(fstatus + 2 * (size_t)ntiles + 1);
-                a.totals = fstatus + 2 * (size_t)ntiles + 8;
-                a.scalars = ctx->d_scalars; a.err = ctx->d_err; a.ntiles = ntiles;
-                a.out = body; a.cap_units = body_cap / 16; a.esc = fesc; a.esc_cap = esc_cap;
-                mtf_rle_kernel<true><<<ntiles, MTF_NT, 0, s>>>(a);
-                TC_LAUNCH_CHECK(ctx);
-                u64 *d_final = fstatus + 2 * (size_t)ntiles + 2;
-                mtf_nib_final_kernel<BwtAcc><<<1, 64, 0, s>>>(acc, N, a.lut, al.sigma, d_final, a.flag);
-                TC_LAUNCH_CHECK(ctx);
-                tc_d2h(ctx, &ctx->h_scalars[15], a.flag, sizeof(u32));
-                tc_d2h(ctx, &ctx->h_scalars[8], d_final, sizeof(u64));
-                TC_HIP(ctx, hipStreamSynchronize(s));
-                if ((u32)ctx->h_scalars[15] == 0) {
-                    const u64 perm = ctx->h_scalars[8];
-                    sigma = al.sigma;
-                    for (u32 i = 0; i < sigma; i++) final_list[i] = al.sym_of_code[(perm >> (4 * i)) & 15];
-                    TC_HIP(ctx, hipEventRecord(ctx->ev[2], s));
-                    write_header();
-                    seal(a.totals, fesc);
-                    one_kernel = true;
-                    fused = true;
-                } else {
-                    ctx->mtf_fastin_failed = 1;
-                }
-            }
-        }
-        if (!one_kernel)
-        mtf_encode_device<BwtAcc>(ctx, A, acc, N, dry ? nullptr : counts257, d_idx, final_list, &sigma, dry,
-                                  reinterpret_cast<u8 *>(d_idx), &idx8);
-        if (!dry && !one_kernel) TC_HIP(ctx, hipEventRecord(ctx->ev[2], s));
-        // scratch of both ways (the dry run does not know sigma yet)
-        status = A.get<u64>(2 * (size_t)ntiles + 32);
-        u32 *esc = A.get<u32>(esc_cap);
-        u32 *r_cnt = A.get<u32>(N + 2);
-        u16 *r_val = A.get<u16>(N + 2);
-        size_t rle_mark = A.off;
-        if (dry) {
-            U16Acc iacc{d_idx};
-            u64 t = 0;
-            rle_encode_device<U16Acc, u16>(ctx, A, iacc, N, r_cnt, r_val, N + 2, &t, true);
-            pack_base = A.off;
-            (void)A.get<u8>(container_scratch(ctx, N + 2));
-            if (A.off < end_sa) A.off = end_sa;
-            return;
-        }
-        if (one_kernel) {
-            if (A.off < end_sa) A.off = end_sa;
-            return;
-        }
-        fused = idx8 && sigma <= PK_NIB_SIGMA && !huff;
-        if (fused) {
-            tc_memset_async(ctx, status, 0, (2 * (size_t)ntiles + 32) * sizeof(u64));
-            u8 *body = d_out + TC_CONTAINER_HEADER;
-            const u64 body_cap = cap - TC_CONTAINER_HEADER;
-            const u64 most = ((N + 31) / 32 + 1) * 16;       // at most one nibble per symbol
-            tc_memset_async(ctx, body, 0, most < (body_cap & ~15ull) ? most : (body_cap & ~15ull));
-            // what the host knows of the header goes first; the seal kernel fills in the rest
-            ContainerHeader h;
-            memset(&h, 0, sizeof h);
-            memcpy(h.magic, kContainerMagic, 8);
-            h.n = n; h.primary = primary; h.sigma = sigma; h.format = (u32)pack_format(sigma);
-            for (u32 i = 0; i < sigma; i++) h.final_list[i] = final_list[i];
-            memset(ctx->h_hdr, 0, TC_CONTAINER_HEADER);
-            memcpy(ctx->h_hdr, &h, sizeof h);
-            tc_h2d(ctx, d_out, ctx->h_hdr, TC_CONTAINER_HEADER);
-            RleNibArgs a;
-            a.src = reinterpret_cast<const u8 *>(d_idx); a.N = N;
-            a.out = body; a.cap_units = body_cap / 16;
-            a.esc = esc; a.esc_cap = esc_cap;
-            a.status_a = status; a.status_b = status + ntiles;
-            a.ticket = reinterpret_cast<u32 *>(status + 2 * (size_t)ntiles);
-            a.totals = status + 2 * (size_t)ntiles + 8;
-            a.err = ctx->d_err; a.ntiles = ntiles;
-            a.diag = env_int("TC_RLE_DIAG", 0);
-            u32 grid = tc_persistent_grid_for(ctx, rle_nib_kernel, RN_NT, 8);
-            if (grid > ntiles) grid = ntiles;
-            rle_nib_kernel<<<grid, RN_NT, 0, s>>>(a);
-            TC_LAUNCH_CHECK(ctx);
-            u64 *sum = a.totals + 4, *result = a.totals + 5;
-            nib_escapes_kernel<<<64, 256, 0, s>>>(a.totals, esc, body, body_cap, esc_cap);
-            TC_LAUNCH_CHECK(ctx);
-            checksum64_dyn_kernel<<<4096, 256, 0, s>>>(reinterpret_cast<const u32 *>(body), a.totals, body_cap, sum);
-            TC_LAUNCH_CHECK(ctx);
-            container_seal_kernel<<<1, 1, 0, s>>>(d_out, a.totals, sum, result);
-            TC_LAUNCH_CHECK(ctx);
-            TC_HIP(ctx, hipEventRecord(ctx->ev[3], s));
-            tc_d2h(ctx, &ctx->h_scalars[20], result, 3 * sizeof(u64));
-        } else {
-            u64 total = 0;
-            A.off = rle_mark;
-            if (idx8) {
-                U8Acc iacc{reinterpret_cast<const u8 *>(d_idx)};
-                rle_encode_device<U8Acc, u16>(ctx, A, iacc, N, r_cnt, r_val, N + 2, &total, false, sigma <= 16);
-            } else {
-                U16Acc iacc{d_idx};
-                rle_encode_device<U16Acc, u16>(ctx, A, iacc, N, r_cnt, r_val, N + 2, &total, false);
-            }
-            TC_HIP(ctx, hipEventRecord(ctx->ev[3], s));
-            blk.n = n; blk.primary = primary; blk.sigma = sigma; blk.nruns = total;
-            blk.run_count = r_cnt; blk.run_value = r_val;
-            for (u32 i = 0; i < sigma; i++) blk.final_list[i] = final_list[i];
-        }
-        if (A.off < end_sa) A.off = end_sa;
-    };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    plan(A, false);
-    tc_sync_check(ctx);
-    tc_stats &st = ctx->stats;
-    (void)hipEventElapsedTime(&st.ms_sa, ctx->ev[0], ctx->ev[1]);
-    (void)hipEventElapsedTime(&st.ms_mtf, ctx->ev[1], ctx->ev[2]);
-    (void)hipEventElapsedTime(&st.ms_rle, ctx->ev[2], ctx->ev[3]);
-    (void)hipEventElapsedTime(&st.ms_total, ctx->ev[0], ctx->ev[3]);
-    st.ms_bwt = 0;
-    if (fused) {
-        const u64 nruns = ctx->h_scalars[20], nesc = ctx->h_scalars[21], body = ctx->h_scalars[22];
-        st.runs = nruns;
-        *bytes = TC_CONTAINER_HEADER + body;
-        if (*bytes > cap || nesc > esc_cap)
-            TC_FAIL(ctx, TC_ERR_CAPACITY, "container needs %llu bytes", (unsigned long long)*bytes);
-        return;
-    }
-    st.runs = blk.nruns;
-    *bytes = cap;
-    container_write_device(ctx, &blk, d_out, bytes, pack_base);
 }
 
 int tc_encode_container_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint8_t *d_out, uint64_t *bytes) {
@@ -1906,9 +1193,7 @@ int tc_container_info(tc_ctx *ctx, const uint8_t *container, uint64_t bytes, uin
     if (!ctx) return TC_ERR_ARG;
     try {
         if (!container || bytes < TC_CONTAINER_HEADER) TC_FAIL(ctx, TC_ERR_MALFORMED, "container shorter than its header");
-        ContainerHeader h;
-        memcpy(&h, container, sizeof h);
-        if (memcmp(h.magic, kContainerMagic, 8) != 0) TC_FAIL(ctx, TC_ERR_MALFORMED, "not a textcomp container");
+        const ContainerHeader h = container_header_parse(ctx, container, bytes, HDR_MAGIC);
         if (n) *n = h.n;
         if (nruns) *nruns = h.nruns;
         return TC_OK;
@@ -1922,9 +1207,7 @@ int tc_container_coding(tc_ctx *ctx, const uint8_t *container, uint64_t bytes, i
     try {
         if (!coding) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
         if (!container || bytes < TC_CONTAINER_HEADER) TC_FAIL(ctx, TC_ERR_MALFORMED, "container shorter than its header");
-        ContainerHeader h;
-        memcpy(&h, container, sizeof h);
-        if (memcmp(h.magic, kContainerMagic, 8) != 0) TC_FAIL(ctx, TC_ERR_MALFORMED, "not a textcomp container");
+        const ContainerHeader h = container_header_parse(ctx, container, bytes, HDR_MAGIC);
         if (h.format == HF_FORMAT) *coding = TC_CODING_HUFFMAN;
         else if (h.sigma <= TC_MAX_SIGMA && h.format == (u32)pack_format(h.sigma)) *coding = TC_CODING_PACKED;
         else TC_FAIL(ctx, TC_ERR_MALFORMED, "container header names no known body format");
@@ -1967,10 +1250,7 @@ int tc_decode_container(tc_ctx *ctx, const uint8_t *container, uint64_t bytes, u
     TC_API_BEGIN(ctx)
     if (!container || !n_out) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
     if (bytes < TC_CONTAINER_HEADER) TC_FAIL(ctx, TC_ERR_MALFORMED, "container shorter than its header");
-    ContainerHeader h0;
-    memcpy(&h0, container, sizeof h0);
-    if (memcmp(h0.magic, kContainerMagic, 8) != 0) TC_FAIL(ctx, TC_ERR_MALFORMED, "not a textcomp container");
-    if (h0.n > TC_MAX_N || h0.nruns > (u64)TC_MAX_N + 2) TC_FAIL(ctx, TC_ERR_MALFORMED, "container header is inconsistent");
+    const ContainerHeader h0 = container_header_parse(ctx, container, bytes, HDR_BOUNDS);
     if (h0.n && !text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
     u8 *d_in = hp_dev(ctx, 0, bytes + 16);
     u8 *d_text = hp_dev(ctx, 1, h0.n + 16);
@@ -1996,36 +1276,6 @@ int tc_decode_container(tc_ctx *ctx, const uint8_t *container, uint64_t bytes, u
 // BWT -> MTF -> RLE block, as bzip2 does with its blocks), written as containers back to back.
 // The device works on record k while one helper thread copies record k+1 in and another copies
 // container k-1 out, each on its own stream.
-struct CopyJob {
-    std::thread th;
-    hipError_t err = hipSuccess;
-    void start(int device, hipStream_t s, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
-        err = hipSuccess;
-        if (!bytes) return;
-        th = std::thread([this, device, s, dst, src, bytes, kind] {
-            hipError_t e = hipSetDevice(device);
-            if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, kind, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            err = e;
-        });
-    }
-    hipError_t join() {
-        if (th.joinable()) th.join();
-        return err;
-    }
-    ~CopyJob() { (void)join(); }
-};
-
-static u64 stream_blocks(u64 n, u64 block) { return n ? (n + block - 1) / block : 1; }
-u64 container_bound_any(u64 n) {
-    u64 b = 0;
-    for (u32 sg : {6u, 16u, 257u}) {
-        const u64 v = tc_container_bound(n + 2, sg);
-        if (v > b) b = v;
-    }
-    return b;
-}
-
 uint64_t tc_stream_bound(uint64_t n, uint64_t block_bytes) {
     if (block_bytes == 0) block_bytes = TC_STREAM_BLOCK_DEFAULT;
     if (block_bytes > TC_MAX_N) block_bytes = TC_MAX_N;
@@ -2107,33 +1357,6 @@ int tc_encode_stream(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t bloc
     if (s_out) (void)hipStreamDestroy(s_out);
     if (rc != TC_OK) throw TcFail{rc};
     TC_API_END(ctx)
-}
-
-// walks the containers of a stream in HOST memory: offsets, total text length, largest record
-struct StreamIndex {
-    std::vector<u64> off, len, n, nruns;
-    u64 n_total = 0, n_max = 0, len_max = 0, nruns_max = 0;
-};
-static StreamIndex stream_index(tc_ctx *ctx, const u8 *stream, u64 bytes) {
-    StreamIndex ix;
-    if (!stream || bytes < TC_CONTAINER_HEADER) TC_FAIL(ctx, TC_ERR_MALFORMED, "stream shorter than one container header");
-    u64 off = 0;
-    while (off < bytes) {
-        if (bytes - off < TC_CONTAINER_HEADER) TC_FAIL(ctx, TC_ERR_MALFORMED, "stream ends inside a container header");
-        ContainerHeader h;
-        memcpy(&h, stream + off, sizeof h);
-        if (memcmp(h.magic, kContainerMagic, 8) != 0) TC_FAIL(ctx, TC_ERR_MALFORMED, "not a textcomp container");
-        if (h.n > TC_MAX_N || h.nruns > (u64)TC_MAX_N + 2 || h.body_bytes > bytes - off - TC_CONTAINER_HEADER)
-            TC_FAIL(ctx, TC_ERR_MALFORMED, "container header is inconsistent");
-        const u64 len = TC_CONTAINER_HEADER + h.body_bytes;
-        ix.off.push_back(off); ix.len.push_back(len); ix.n.push_back(h.n); ix.nruns.push_back(h.nruns);
-        ix.n_total += h.n;
-        if (h.n > ix.n_max) ix.n_max = h.n;
-        if (len > ix.len_max) ix.len_max = len;
-        if (h.nruns > ix.nruns_max) ix.nruns_max = h.nruns;
-        off += len;
-    }
-    return ix;
 }
 
 int tc_stream_info(tc_ctx *ctx, const uint8_t *stream, uint64_t bytes, uint64_t *n_total, uint64_t *nblocks) {
@@ -2505,16 +1728,11 @@ int tc_fm_count(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_
     u8 *d_pats = nullptr;
     u64 *d_offs = nullptr;
     i64 *d_out = nullptr;
-    Arena dry(nullptr);
-    auto carve = [&](Arena &A) {
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
         d_pats = A.get<u8>(total + 16);
         d_offs = A.get<u64>(npat + 1);
         d_out = A.get<i64>(npat);
-    };
-    carve(dry);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    carve(A);
+    });
     tc_h2d(ctx, d_pats, pats, total);
     tc_h2d(ctx, d_offs, offs, (npat + 1) * sizeof(u64));
     fm_count_device(ctx, fm, d_pats, d_offs, npat, d_out, nullptr);
@@ -2591,18 +1809,14 @@ int tc_fm_locate(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64
     u8 *d_pats = nullptr;
     u64 *d_offs = nullptr, *d_hoffs = nullptr, *d_hits = nullptr;
     FmLocateScratch W;
-    auto carve = [&](Arena &A) {
+    auto carve = [&](Arena &A, bool) {
         d_pats = A.get<u8>(total + 16);
         d_offs = A.get<u64>(npat + 1);
         W.carve(A, npat);
         d_hoffs = A.get<u64>(npat + 1);
         d_hits = A.get<u64>(cap + 1);
     };
-    Arena dry(nullptr);
-    carve(dry);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    carve(A);
+    tc_ws_plan(ctx, 0, carve);
     tc_h2d(ctx, d_pats, pats, total);
     tc_h2d(ctx, d_offs, offs, (npat + 1) * sizeof(u64));
     const u64 need = fm_locate_device(ctx, fm, W, d_pats, d_offs, npat, d_hoffs, d_hits, cap);
@@ -2631,11 +1845,7 @@ int tc_fm_locate_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const 
     }
     if (!fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
     FmLocateScratch W;
-    Arena dry(nullptr);
-    W.carve(dry, npat);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    W.carve(A, npat);
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) { W.carve(A, npat); });
     const u64 need = fm_locate_device(ctx, fm, W, d_pats, d_offs, npat, d_hit_offs, d_hits, cap);
     *nhits = need;
     TC_HIP(ctx, hipMemcpyAsync(d_hit_offs + npat, W.d_tsum + W.tiles, sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
@@ -2839,15 +2049,11 @@ int tc_dbg_scatter_bench(tc_ctx *ctx, uint64_t n, uint32_t bins, uint32_t xrun, 
     const u64 m = (u64)ntiles * 4096;
     u64 *k0 = nullptr, *k1 = nullptr;
     u32 *v0 = nullptr, *v1 = nullptr;
-    auto carve = [&](Arena &A) {
+    auto carve = [&](Arena &A, bool) {
         k0 = A.get<u64>(m); k1 = A.get<u64>(m);
         v0 = A.get<u32>(m); v1 = A.get<u32>(m);
     };
-    Arena dry(nullptr);
-    carve(dry);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    carve(A);
+    tc_ws_plan(ctx, 0, carve);
     hipStream_t s = ctx->stream;
     tc_memset_async(ctx, k0, 1, m * 8);
     tc_memset_async(ctx, v0, 1, m * 4);
@@ -2911,7 +2117,7 @@ int tc_dbg_sort_bench(tc_ctx *ctx, uint64_t n, int key_bits, int iters, int chec
     RadixBuffers b;
     u64 *src = nullptr;
     u32 *bad = nullptr;
-    auto carve = [&](Arena &A) {
+    auto carve = [&](Arena &A, bool) {
         src = A.get<u64>(n);
         b.keys = A.get<u64>(n); b.keys_alt = A.get<u64>(n);
         b.vals = A.get<u32>(n); b.vals_alt = A.get<u32>(n);
@@ -2919,11 +2125,7 @@ int tc_dbg_sort_bench(tc_ctx *ctx, uint64_t n, int key_bits, int iters, int chec
         b.status = A.get<u64>(radix_status_words(n));
         bad = A.get<u32>(64);
     };
-    Arena dry(nullptr);
-    carve(dry);
-    tc_ws_reserve(ctx, dry.off);
-    Arena A(ctx->ws);
-    carve(A);
+    tc_ws_plan(ctx, 0, carve);
     hipStream_t s = ctx->stream;
     dbg_random_keys_kernel<<<4096, 256, 0, s>>>(src, n, 0x5EEDull, key_bits);
     TC_LAUNCH_CHECK(ctx);
