@@ -29,7 +29,8 @@
  *     number of ctxs on the index's device may query one tc_fm at the same
  *     time; tc_fm_free must not overlap a query of that index.  The same holds
  *     for tc_fm_locate_dev and for a sampled index (tc_fm_build_sampled): the
- *     walk's scratch and its error flag belong to the calling ctx.
+ *     walk's scratch and its error flag belong to the calling ctx; and for
+ *     tc_fm_extract / tc_fm_extract_dev on an index with text samples.
  *   - `*_dev` entry points take DEVICE pointers for the bulk arrays (the
  *     benchmark path: inputs and outputs resident in HBM); scalar outputs are
  *     host words.  All calls return after the ctx stream has drained.
@@ -348,9 +349,23 @@ int tc_fm_build_sampled(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t s
 int tc_fm_build_sampled_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t sa_rate, tc_fm **out);
 /* sa_rate of an index (1: full suffix array; 0: no locate part -- a count-only import, the empty index, NULL) */
 uint32_t tc_fm_sa_rate(const tc_fm *fm);
-/* device bytes the index holds: part 0 = everything, part 1 = the locate part alone (L + SA, or L + marks + samples);
- * the sizes asked of the allocator, without its rounding.  0 for the empty index or any other part. */
+/* device bytes the index holds: part 0 = everything, part 1 = the locate part alone (L + SA, or L + marks + samples),
+ * part 2 = the extract part alone (the text samples of tc_fm_build_self: 4 * (n / text_rate + 1); 0 without them; part 0
+ * includes it); the sizes asked of the allocator, without its rounding.  0 for the empty index or any other part. */
 uint64_t tc_fm_device_bytes(const tc_fm *fm, int part);
+/* The same index with TEXT SAMPLES as well, so that it can answer what stands at a text position (extract) and the text
+ * need not be kept beside it (an addition to the reference's surface).  Beside its locate part (sa_rate as in
+ * tc_fm_build_sampled; 1 = the full suffix array) the index keeps, for every text_rate-th text position, the ROW of the
+ * suffix that starts there:
+ *   isa      uint32 isa[n / text_rate + 1]: isa[k] = the row j with SA[j] = k * text_rate -- 4 / text_rate bytes per text
+ *            byte.  The empty suffix (position n) needs no sample: it is row 0 in every index this library builds.
+ * text_rate: a power of two, 1 .. TC_FM_MAX_SA_RATE, independent of sa_rate.  Anything else in either rate: TC_ERR_ARG
+ * (*out = NULL).  n = 0 gives the empty index (tc_fm_text_rate 0).  count and locate are those of the index
+ * tc_fm_build_sampled(sa_rate) makes. */
+int tc_fm_build_self(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, tc_fm **out);
+int tc_fm_build_self_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, tc_fm **out);
+/* text_rate of an index (0: no text samples -- any other build call, an import without them, the empty index, NULL) */
+uint32_t tc_fm_text_rate(const tc_fm *fm);
 /* bytestringFMIndexCountS / ...CountP (FMIndex.hs:362-379,411-432) =
  * countFMIndex (FMIndex/Internal.hs:347-438) mapped over the patterns in ONE
  * batched launch; pattern j = pats[offs[j] .. offs[j+1]).  out[j] = count, 0 for
@@ -373,6 +388,27 @@ int tc_fm_locate(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64
  * one of its bounds makes the call answer TC_ERR_MALFORMED; on an index this library built it never does. */
 int tc_fm_locate_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs,
                      uint64_t npat, uint64_t *d_hit_offs, uint64_t *d_hits, uint64_t *nhits);
+/* extract: the text ranges [starts[q], starts[q] + lens[q]) of nq queries, read back from the index.  starts are 1-BASED,
+ * exactly as tc_fm_locate answers positions -- tc_fm_extract(hit, |pattern|) returns the pattern -- and every query must lie
+ * in the text: 1 <= start and start - 1 + len <= n (len = 0 is allowed for start = 1 .. n + 1); ranges are not clamped.
+ * out_offs[nq + 1] (out) delimits each query's bytes inside out[]; *nbytes: in = capacity of out, out = total bytes.
+ * A capacity that is too small: TC_ERR_CAPACITY, *nbytes = the needed total, nothing written to out.  A bad query:
+ * TC_ERR_ARG, nothing written to out.  An index without text samples (tc_fm_text_rate 0; a count-only import is one):
+ * TC_ERR_ARG.  nq = 0: TC_OK.
+ * The unit of work is a (query, text_rate-aligned segment) pair: one lane walks the LF mapping from the sampled position at
+ * or behind the segment's end down to its start, at most text_rate steps of two dependent random reads each (the
+ * last-column byte, then one rank line), so a long range spreads over many lanes and the whole text is n / text_rate + 1
+ * independent walks.  Scratch comes from the calling ctx: any number of ctxs may extract from one tc_fm at once.
+ * On an IMPORTED index the walk reads caller data: it is bounded on any bytes (the step count is fixed by the query, every
+ * row < N, every sample index within the samples, no step from the primary row or from a byte the text does not hold), and
+ * a walk that runs into one of its bounds makes the call answer TC_ERR_MALFORMED (its bytes are zeros); on an index this
+ * library built it never does. */
+int tc_fm_extract(tc_ctx *ctx, const tc_fm *fm, const uint64_t *starts, const uint64_t *lens, uint64_t nq,
+                  uint64_t *out_offs, uint8_t *out, uint64_t *nbytes);
+/* tc_fm_extract with everything in HBM: d_starts, d_lens [nq], d_out_offs [nq + 1] and d_out [*nbytes] are device arrays;
+ * nbytes is a host word.  tc_fm_extract is this call between a copy in and a copy out. */
+int tc_fm_extract_dev(tc_ctx *ctx, const tc_fm *fm, const uint64_t *d_starts, const uint64_t *d_lens, uint64_t nq,
+                      uint64_t *d_out_offs, uint8_t *d_out, uint64_t *nbytes);
 /* seqToCc / seqFromFMIndex views for the Haskell shim: present symbols (sorted,
  * Nothing first) with C[c]; and L / primary. */
 int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, uint64_t *c_val,
@@ -382,10 +418,13 @@ int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, ui
  * the index is broadcast once): the index as ONE device byte string (header, C / code tables, rank
  * bit-vectors; with_locate != 0 adds the last column and the suffix array that tc_fm_locate needs -- of a sampled index
  * the last column, the marks and the samples, and the header's formerly reserved word carries sa_rate; a full index
- * writes 0 there, its export is byte for byte what it was -- ) and
+ * writes 0 there, its export is byte for byte what it was; an index with text samples (tc_fm_build_self) ships them
+ * behind the locate part, 256-byte aligned like every part, and its header's with_locate word is 1 | text_rate << 8, while
+ * an index without them writes 1 as ever; with_locate == 0 ships neither -- ) and
  * back.  The caller moves the bytes (RCCL broadcast); tc_fm_import_dev checks the header
  * (TC_ERR_MALFORMED; for a sampled index also: the rate, the sizes that follow from N and the rate, and that the marks hold
- * exactly one bit per sample) and copies out of d_in, which may be released afterwards.  An index imported
+ * exactly one bit per sample; for text samples: the rate, the size that follows from n and the rate, that position 0 is
+ * sampled at the primary row and that every sample is a row) and copies out of d_in, which may be released afterwards.  An index imported
  * without the locate part answers tc_fm_count only (tc_fm_locate: TC_ERR_ARG).  Buffers 16-byte
  * aligned.  *bytes: in = capacity, out = bytes used (TC_ERR_CAPACITY: bytes needed).  The byte string is BUILD-SPECIFIC
  * (it carries a format version: "TCFMI02" since round 3; an export of another version is refused with a message that

@@ -1,4 +1,4 @@
-// tc_fm_host.hpp -- FM-index: build, batched count, locate.
+// tc_fm_host.hpp -- FM-index: build, batched count, locate, extract.
 //
 // Replaces (reference FMIndex/Internal.hs) seqToCc :275-316 (C[c], there derived
 // from an O(n^2) rotation matrix, BWT/Internal.hs:209-241; here a byte histogram),
@@ -50,6 +50,11 @@ struct tc_fm {
     u64 *d_marks = nullptr;   // [lines][8]
     u32 *d_samples = nullptr; // [nsamples]
     u64 nsamples = 0;
+    // the extract part (tc_fm_build_self; independent of sa_rate): text_rate k >= 1 keeps the ROW of every k-th text position,
+    // d_isa[i] = the row j with SA[j] = i * k, i = 0 .. floor(n / k) -- 4 / k bytes per text byte.  text_rate 0: none.
+    u32 text_rate = 0;
+    u32 *d_isa = nullptr;     // [nisa]
+    u64 nisa = 0;             // n / text_rate + 1
 };
 
 #ifdef __HIPCC__
@@ -457,6 +462,141 @@ __global__ __launch_bounds__(256) void fm_locate_walk_kernel(const u64 *__restri
     hits[h] = bad ? 0 : pos + 1;
 }
 
+// ---- extract: text ranges read back from the index -----------------------------------------------------------------
+// The text samples (the opposite direction of the locate samples): isa[k] = the row j with SA[j] = k * rate, for
+// k = 0 .. floor(n / rate).  One pass over the suffix array -- the index's own for a full index, the copy in the workspace
+// for a sampled one, where fm_marks_kernel reads it -- scatters the rows whose suffix starts at a multiple of the rate.
+// Every multiple of the rate up to n is the start of exactly one suffix, so every entry is written exactly once.  The
+// empty suffix (position n) is row 0 in every suffix array sa_build makes -- Nothing sorts first: tab[256 + c] = C[c]
+// starts at 1 for that row (fm_make_tab) -- so the walk that starts at the end of the text needs no sample; when n is a
+// multiple of the rate the scatter stores that 0 at isa[n / rate] like any other entry.
+__global__ __launch_bounds__(256) void fm_isa_kernel(const u32 *__restrict__ sa, u64 N, u32 rate, u32 rate_log2, u64 nisa,
+                                                     u32 *__restrict__ isa) {
+    for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < N; j += (u64)gridDim.x * 256) {
+        const u32 v = sa[j];
+        const u64 k = v >> rate_log2;
+        if ((v & (rate - 1)) == 0 && k < nisa) isa[k] = (u32)j;
+    }
+}
+
+// import check of the text samples: res[0] = the largest sample (every one must be < N), res[1] = isa[0] (must be the
+// primary row, the row of SA = 0); res zeroed before
+__global__ __launch_bounds__(256) void fm_isa_max_kernel(const u32 *__restrict__ isa, u64 nisa, u32 *__restrict__ res) {
+    u32 m = 0;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < nisa; i += (u64)gridDim.x * 256) m = isa[i] > m ? isa[i] : m;
+    for (int d = 32; d >= 1; d >>= 1) {
+        const u32 o = __shfl_xor(m, d, 64);
+        m = o > m ? o : m;
+    }
+    if (lane_id() == 0 && m) atomicMax(res, m);
+    if (blockIdx.x == 0 && threadIdx.x == 0) res[1] = isa[0];
+}
+
+// One lane per query (start, len), start 1-based as locate answers positions: a = start - 1, e = a + len must satisfy
+// start >= 1 and e <= n (tested without overflow).  qlen[q] = len and qsegs[q] = the number of rate-aligned segments
+// [k * rate, (k + 1) * rate) that [a, e) touches, both 0 for a bad query, which also raises *bad; two exclusive scans of
+// them give the output offsets and the segment offsets.
+__global__ __launch_bounds__(256) void fm_extract_plan_kernel(const u64 *__restrict__ starts, const u64 *__restrict__ lens,
+                                                              u64 nq, u64 n, u32 rate_log2, u64 *__restrict__ qlen,
+                                                              u64 *__restrict__ qsegs, u32 *__restrict__ bad) {
+    const u64 q = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq) return;
+    const u64 a = starts[q] - 1, len = lens[q];
+    u64 l = 0, sg = 0;
+    if (a > n || len > n - a) {     // (start = 0 wraps to 2^64 - 1 > n)
+        atomicOr(bad, 1u);
+    } else if (len) {
+        l = len;
+        sg = ((a + len - 1) >> rate_log2) - (a >> rate_log2) + 1;
+    }
+    qlen[q] = l;
+    qsegs[q] = sg;
+}
+
+// One lane per (query, segment): segment k of a query [a, e) is the text [max(a, k * rate), min(e, (k + 1) * rate)), read
+// by an LF walk from the anchor q = min((k + 1) * rate, n), whose row is isa[k + 1] (row 0 for q = n):
+//   for p = q - 1 down to max(a, k * rate): byte = L[row]; if p < e: out[out_offs[query] + p - a] = byte; row = LF(row)
+// with LF(row) = C[code(byte)] + Occ(code, row), the step of fm_locate_walk_kernel: L[row] = T[SA[row] - 1] and
+// SA[LF(row)] = SA[row] - 1.  The step count is fixed by the arguments (<= rate), the last byte of a segment needs no step
+// behind it, and only a query's last segment reads bytes it does not emit (q - e < rate of them).  A step is two dependent
+// random reads: the L byte, then the rank line of (code, row) -- one fewer than a locate step, which also reads the marks
+// line.
+// item -> query: the largest query index whose segment offset is <= the item (a search in the scanned offsets; queries
+// without segments share their successor's offset and are skipped by it).
+// Bytes arrive in descending address order: they are gathered in a 64-bit register and stored as one word when the walk
+// crosses an aligned 8-byte boundary of the output, the two ragged ends of the lane's range by byte stores.  Neighbouring
+// segments of a query belong to other lanes: nothing is written outside the lane's own range.
+// The index may be imported, i.e. caller data: every row is kept < N and the sample index < nisa, a byte without a code
+// stops the walk and so does a step FROM the primary row (its L byte is a placeholder 0; a correct walk reaches that row
+// only behind its last step, at p = 0, and never reads its byte).  A lane that runs into one of these raises FM_ERR_WALK (the
+// call answers TC_ERR_MALFORMED) and fills its range with zeros.
+__device__ __forceinline__ void fm_extract_flush(u8 *base, u64 acc, u32 cnt) {   // base[j] = byte j of acc, j < cnt
+    for (u32 j = 0; j < cnt; j++) base[j] = (u8)(acc >> (8 * j));
+}
+__global__ __launch_bounds__(256) void fm_extract_walk_kernel(const u64 *__restrict__ bits, u64 lines,
+                                                              const u32 *__restrict__ tab, u32 sigma,
+                                                              const u8 *__restrict__ L, const u32 *__restrict__ isa,
+                                                              u64 nisa, u64 N, u64 primary, u32 rate_log2,
+                                                              const u64 *__restrict__ starts, const u64 *__restrict__ lens,
+                                                              const u64 *__restrict__ seg_offs,
+                                                              const u64 *__restrict__ out_offs, u64 nq, u64 nsegs,
+                                                              u8 *__restrict__ out, u32 *__restrict__ err) {
+    __shared__ u32 s_tab[512];
+    for (int i = threadIdx.x; i < 512; i += 256) s_tab[i] = tab[i];
+    __syncthreads();
+    const u64 item = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (item >= nsegs) return;
+    u64 lo_q = 0, hi_q = nq;            // seg_offs[lo_q] <= item < seg_offs[hi_q] (seg_offs[0] = 0, seg_offs[nq] = nsegs)
+    while (hi_q - lo_q > 1) {
+        const u64 mid = lo_q + ((hi_q - lo_q) >> 1);
+        if (seg_offs[mid] <= item) lo_q = mid; else hi_q = mid;
+    }
+    const u64 n = N - 1;
+    const u64 a = starts[lo_q] - 1, e = a + lens[lo_q];
+    const u64 k = (a >> rate_log2) + (item - seg_offs[lo_q]);
+    const u64 seg_lo = k << rate_log2, seg_hi = (k + 1) << rate_log2;
+    const u64 lo = a > seg_lo ? a : seg_lo;
+    const u64 anchor = seg_hi < n ? seg_hi : n;
+    const u64 top = e < anchor ? e : anchor;        // this lane emits [lo, top)
+    u8 *const o = out + out_offs[lo_q] - a;         // o + p: where text position p goes
+    bool bad = false;
+    u64 row = 0;
+    if (anchor != n) {
+        if (k + 1 < nisa) row = isa[k + 1]; else bad = true;
+        if (row >= N) { bad = true; row = 0; }
+    }
+    u64 acc = 0;
+    u32 cnt = 0;
+    if (!bad && lo < anchor) {
+        for (u64 p = anchor - 1;; p--) {
+            if (row == primary) { bad = true; break; }
+            const u32 byte = L[row];
+            const u32 c = s_tab[byte];
+            if (c >= sigma) { bad = true; break; }
+            if (p < top) {
+                u8 *const ad = o + p;
+                acc = (acc << 8) | byte;
+                cnt++;
+                if (((uintptr_t)ad & 7) == 0) {
+                    if (cnt == 8) *reinterpret_cast<u64 *>(ad) = acc;
+                    else fm_extract_flush(ad, acc, cnt);
+                    cnt = 0;
+                }
+            }
+            if (p == lo) break;
+            const u64 nr = (u64)s_tab[256 + c] + fm_occ(bits, lines, c, row);
+            if (nr >= N) { bad = true; break; }
+            row = nr;
+        }
+    }
+    if (bad) {
+        atomicOr(err, FM_ERR_WALK);
+        for (u64 p = lo; p < top; p++) o[p] = 0;
+    } else if (cnt) {
+        fm_extract_flush(o + lo, acc, cnt);
+    }
+}
+
 #endif  // __HIPCC__
 
 // code of byte / C[code] / count[code] from the byte histogram; returns the number of present byte values
@@ -484,6 +624,7 @@ static void fm_release(tc_fm *fm) {
     if (fm->d_sa) (void)hipFree(fm->d_sa);
     if (fm->d_marks) (void)hipFree(fm->d_marks);
     if (fm->d_samples) (void)hipFree(fm->d_samples);
+    if (fm->d_isa) (void)hipFree(fm->d_isa);
     if (fm->d_bits) (void)hipFree(fm->d_bits);
     if (fm->bits2_chunks) tc_chunked_free(fm->bits2_chunks);
     else if (fm->d_bits2) (void)hipFree(fm->d_bits2);
@@ -510,7 +651,10 @@ static void fm_alloc_bits2(tc_ctx *ctx, tc_fm *fm, size_t bytes) {
 // text_host or text_dev (a text already in HBM is used where it lies: no copy at all)
 // sa_rate 1: the index owns the full suffix array.  sa_rate k > 1: the suffix array lives in the context's workspace for the
 // duration of the call (the same peak: the 4 N bytes are carved there instead of allocated) and the index keeps marks + samples.
-static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 *text_dev = nullptr, u32 sa_rate = 1) {
+// text_rate k >= 1: the index also keeps the text samples (d_isa), scattered from the same suffix array before it goes.
+static inline u32 fm_log2(u32 v) { return 31u - (u32)__builtin_clz(v); }   // v: a power of two
+static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 *text_dev = nullptr, u32 sa_rate = 1,
+                              u32 text_rate = 0) {
     tc_fm *fm = new tc_fm();
     fm->device = ctx->device;
     fm->n = n;
@@ -576,6 +720,15 @@ static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 
             TC_LAUNCH_CHECK(ctx);
             fm_samples_kernel<<<tc_cdiv(fm->lines, 4), 256, 0, s>>>(d_sa, N, fm->lines, fm->d_marks, fm->nsamples,
                                                                    fm->d_samples);
+            TC_LAUNCH_CHECK(ctx);
+        }
+        if (text_rate) {
+            fm->text_rate = text_rate;
+            fm->nisa = n / text_rate + 1;
+            TC_HIP(ctx, hipMalloc((void **)&fm->d_isa, (size_t)fm->nisa * sizeof(u32)));
+            u32 grid = tc_cdiv(N, 256 * 8);
+            if (grid > 8192) grid = 8192;
+            fm_isa_kernel<<<grid, 256, 0, s>>>(d_sa, N, text_rate, fm_log2(text_rate), fm->nisa, fm->d_isa);
             TC_LAUNCH_CHECK(ctx);
         }
         tc_sync_check(ctx);

@@ -1506,15 +1506,50 @@ int tc_fm_build_sampled_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint
     TC_API_END(ctx)
 }
 
+int tc_fm_build_self(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, tc_fm **out) {
+    TC_API_BEGIN(ctx)
+    if (out) *out = nullptr;
+    if (!out || n > TC_MAX_N || !fm_rate_ok(sa_rate) || !fm_rate_ok(text_rate))
+        TC_FAIL(ctx, TC_ERR_ARG, "bad argument (sa_rate, text_rate: powers of two, 1 .. %d)", TC_FM_MAX_SA_RATE);
+    if (n == 0) {
+        tc_fm *fm = new tc_fm();
+        fm->device = ctx->device;
+        *out = fm;
+        return TC_OK;
+    }
+    if (!text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    *out = fm_build_device(ctx, text, n, nullptr, sa_rate, text_rate);
+    TC_API_END(ctx)
+}
+
+int tc_fm_build_self_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, tc_fm **out) {
+    TC_API_BEGIN(ctx)
+    if (out) *out = nullptr;
+    if (!out || n > TC_MAX_N || !fm_rate_ok(sa_rate) || !fm_rate_ok(text_rate))
+        TC_FAIL(ctx, TC_ERR_ARG, "bad argument (sa_rate, text_rate: powers of two, 1 .. %d)", TC_FM_MAX_SA_RATE);
+    if (n == 0) {
+        tc_fm *fm = new tc_fm();
+        fm->device = ctx->device;
+        *out = fm;
+        return TC_OK;
+    }
+    if (!d_text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    *out = fm_build_device(ctx, nullptr, n, d_text, sa_rate, text_rate);
+    TC_API_END(ctx)
+}
+
 uint32_t tc_fm_sa_rate(const tc_fm *fm) { return fm ? fm->sa_rate : 0; }
+uint32_t tc_fm_text_rate(const tc_fm *fm) { return fm ? fm->text_rate : 0; }
 
 uint64_t tc_fm_device_bytes(const tc_fm *fm, int part) {
-    if (!fm || fm->n == 0 || (part != 0 && part != 1)) return 0;
+    if (!fm || fm->n == 0 || part < 0 || part > 2) return 0;
+    const u64 ext = fm->text_rate ? fm->nisa * sizeof(u32) : 0;
+    if (part == 2) return ext;
     u64 loc = 0;
     if (fm->sa_rate == 1) loc = (fm->N + 16) + fm->N * sizeof(u32);
     else if (fm->sa_rate > 1) loc = (fm->N + 16) + fm->lines * 64 + fm->nsamples * sizeof(u32);
     if (part == 1) return loc;
-    u64 b = loc + 768 * sizeof(u32) + (u64)fm->sigma_bytes * fm->lines * 64;
+    u64 b = loc + ext + 768 * sizeof(u32) + (u64)fm->sigma_bytes * fm->lines * 64;
     if (fm->d_bits2) b += (u64)fm->sigma_bytes * fm->sigma_bytes * fm->lines * 64 + FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32);
     return b;
 }
@@ -1525,7 +1560,8 @@ void tc_fm_free(tc_fm *fm) { fm_release(fm); }
 struct FmWire {
     char magic[8];   // "TCFMI02\0"
     u64 n, N, primary, lines, bytes;
-    u32 sigma_bytes, with_locate;
+    u32 sigma_bytes, with_locate;   // with_locate: bit 0 = the locate part follows; bits 8.. = text_rate of the text samples
+                                    // that follow the locate part (0: none -- an index without them writes 0 or 1 as ever)
     u32 with_pairs, sa_rate;    // 1: the pair vectors (sigma_bytes^2 of them) follow the per-byte vectors.  sa_rate (the word was
                                 // reserved = 0 before sampled indexes): 0 or 1 = the locate part is L + the full suffix array;
                                 // k > 1 = L + marks + samples (a full index writes 0: its export is what it always was)
@@ -1542,6 +1578,7 @@ static u64 fm_wire_bytes(const tc_fm *fm, int with_locate) {
     if (with_locate && fm->sa_rate > 1)
         b += fm_wire_align(fm->N + 16) + fm_wire_align(fm->lines * 64) + fm_wire_align(fm->nsamples * sizeof(u32));
     else if (with_locate) b += fm_wire_align(fm->N + 16) + fm_wire_align(fm->N * sizeof(u32));
+    if (with_locate && fm->text_rate) b += fm_wire_align(fm->nisa * sizeof(u32));
     return b;
 }
 
@@ -1557,7 +1594,7 @@ int tc_fm_export_dev(tc_ctx *ctx, const tc_fm *fm, int with_locate, uint8_t *d_o
     FmWire h = {};
     memcpy(h.magic, kFmMagic, 8);
     h.n = fm->n; h.N = fm->N; h.primary = fm->primary; h.lines = fm->lines; h.bytes = need;
-    h.sigma_bytes = fm->sigma_bytes; h.with_locate = (fm->n && with_locate) ? 1u : 0u;
+    h.sigma_bytes = fm->sigma_bytes; h.with_locate = (fm->n && with_locate) ? (1u | fm->text_rate << 8) : 0u;
     h.with_pairs = fm->d_bits2 ? 1u : 0u;
     h.sa_rate = (h.with_locate && fm->sa_rate > 1) ? fm->sa_rate : 0u;
     memcpy(h.counts, fm->counts, sizeof h.counts);
@@ -1580,9 +1617,13 @@ int tc_fm_export_dev(tc_ctx *ctx, const tc_fm *fm, int with_locate, uint8_t *d_o
                 TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_marks, fm->lines * 64, hipMemcpyDeviceToDevice, s));
                 o += fm_wire_align(fm->lines * 64);
                 TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_samples, fm->nsamples * sizeof(u32), hipMemcpyDeviceToDevice, s));
+                o += fm_wire_align(fm->nsamples * sizeof(u32));
             } else {
                 TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_sa, fm->N * sizeof(u32), hipMemcpyDeviceToDevice, s));
+                o += fm_wire_align(fm->N * sizeof(u32));
             }
+            if (fm->text_rate)
+                TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_isa, fm->nisa * sizeof(u32), hipMemcpyDeviceToDevice, s));
         }
     }
     TC_HIP(ctx, hipStreamSynchronize(s));   // h is a stack object
@@ -1620,9 +1661,15 @@ int tc_fm_import_dev(tc_ctx *ctx, const uint8_t *d_in, uint64_t bytes, tc_fm **o
         TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: header is inconsistent");
     // the sampling rate rides in the word that was reserved: 0 or 1 = full suffix array; otherwise a power of two within range,
     // and only where there is a locate part
+    // the text samples' rate rides above bit 7 of the with_locate word: 0 = none; otherwise a power of two within range, and
+    // only behind a locate part
+    const bool wire_locate = (h.with_locate & 0xffu) != 0;
+    const u32 wire_text_rate = h.with_locate >> 8;
     const bool wire_sampled = h.sa_rate > 1;
-    if (wire_sampled && (!fm_rate_ok(h.sa_rate) || !h.with_locate || !h.n))
+    if (wire_sampled && (!fm_rate_ok(h.sa_rate) || !wire_locate || !h.n))
         TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: bad suffix-array sampling rate %u", h.sa_rate);
+    if (wire_text_rate && (!fm_rate_ok(wire_text_rate) || (h.with_locate & 0xffu) != 1 || !h.n))
+        TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: bad text sampling rate %u", wire_text_rate);
     tc_fm *fm = new tc_fm();
     fm->device = ctx->device;
     fm->n = h.n; fm->N = h.N; fm->primary = h.primary; fm->lines = h.lines; fm->sigma_bytes = h.sigma_bytes;
@@ -1636,8 +1683,12 @@ int tc_fm_import_dev(tc_ctx *ctx, const uint8_t *d_in, uint64_t bytes, tc_fm **o
             if (wire_sampled) {
                 fm->nsamples = fm->n / h.sa_rate + 1;
                 need += fm_wire_align(fm->N + 16) + fm_wire_align(fm->lines * 64) + fm_wire_align(fm->nsamples * sizeof(u32));
-            } else if (h.with_locate) {
+            } else if (wire_locate) {
                 need += fm_wire_align(fm->N + 16) + fm_wire_align(fm->N * sizeof(u32));
+            }
+            if (wire_text_rate) {
+                fm->nisa = fm->n / wire_text_rate + 1;
+                need += fm_wire_align(fm->nisa * sizeof(u32));
             }
             if (need != h.bytes) TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: size mismatch");
             u32 tab[768];
@@ -1680,14 +1731,35 @@ int tc_fm_import_dev(tc_ctx *ctx, const uint8_t *d_in, uint64_t bytes, tc_fm **o
                 if (ctx->h_scalars[10] != fm->nsamples)
                     TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: %llu rows are marked as sampled, %llu samples follow",
                             (unsigned long long)ctx->h_scalars[10], (unsigned long long)fm->nsamples);
+                o += fm_wire_align(fm->nsamples * sizeof(u32));
                 fm->sa_rate = h.sa_rate;
-            } else if (h.with_locate) {
+            } else if (wire_locate) {
                 TC_HIP(ctx, hipMalloc((void **)&fm->d_L, fm->N + 16));
                 TC_HIP(ctx, hipMalloc((void **)&fm->d_sa, fm->N * sizeof(u32)));
                 TC_HIP(ctx, hipMemcpyAsync(fm->d_L, d_in + o, fm->N, hipMemcpyDeviceToDevice, s));
                 o += fm_wire_align(fm->N + 16);
                 TC_HIP(ctx, hipMemcpyAsync(fm->d_sa, d_in + o, fm->N * sizeof(u32), hipMemcpyDeviceToDevice, s));
+                o += fm_wire_align(fm->N * sizeof(u32));
                 fm->sa_rate = 1;
+            }
+            if (wire_text_rate) {
+                TC_HIP(ctx, hipMalloc((void **)&fm->d_isa, fm->nisa * sizeof(u32)));
+                TC_HIP(ctx, hipMemcpyAsync(fm->d_isa, d_in + o, fm->nisa * sizeof(u32), hipMemcpyDeviceToDevice, s));
+                // what only the device can check: every sample is a row, and position 0 is the primary row's (the walk bounds
+                // everything else)
+                u32 *d_res = reinterpret_cast<u32 *>(ctx->d_scalars + 10);
+                TC_HIP(ctx, hipMemsetAsync(d_res, 0, sizeof(u64), s));
+                u32 grid = tc_cdiv(fm->nisa, 256 * 16);
+                if (grid > 4096) grid = 4096;
+                fm_isa_max_kernel<<<grid, 256, 0, s>>>(fm->d_isa, fm->nisa, d_res);
+                TC_LAUNCH_CHECK(ctx);
+                TC_HIP(ctx, hipMemcpyAsync(&ctx->h_scalars[10], d_res, sizeof(u64), hipMemcpyDeviceToHost, s));
+                TC_HIP(ctx, hipStreamSynchronize(s));
+                const u64 isa_max = ctx->h_scalars[10] & 0xffffffffu, isa0 = ctx->h_scalars[10] >> 32;
+                if (isa_max >= fm->N || isa0 != fm->primary)
+                    TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: text samples out of range (largest row %llu of %llu, position 0 at row %llu, primary row %llu)",
+                            (unsigned long long)isa_max, (unsigned long long)fm->N, (unsigned long long)isa0, (unsigned long long)fm->primary);
+                fm->text_rate = wire_text_rate;
             }
             TC_HIP(ctx, hipStreamSynchronize(s));
         }
@@ -1853,6 +1925,118 @@ int tc_fm_locate_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const 
         TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu hit slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
     }
+    tc_sync_check(ctx);
+    TC_API_END(ctx)
+}
+
+// scratch of one extract batch besides queries and results
+struct FmExtractScratch {
+    u64 *d_len = nullptr, *d_segs = nullptr, *d_soffs = nullptr, *d_tsum_b = nullptr, *d_tsum_s = nullptr;
+    u32 *d_bad = nullptr;
+    u64 tiles = 0;
+    void carve(Arena &A, u64 nq) {
+        tiles = tc_cdiv(nq, SCAN_TILE);
+        d_len = A.get<u64>(nq);
+        d_segs = A.get<u64>(nq);
+        d_soffs = A.get<u64>(nq + 1);
+        d_tsum_b = A.get<u64>(tiles + 2);
+        d_tsum_s = A.get<u64>(tiles + 2);
+        d_bad = A.get<u32>(2);
+    }
+};
+
+// everything on the device: the plan (validation, byte and segment counts, their scans: d_out_offs[0 .. nq], the last entry
+// the total), then -- after the host has seen the flag and the totals -- the walks.  Returns the byte total; a bad query is
+// TC_ERR_ARG, and then, as with a total above cap, nothing is written to d_out.  The caller synchronises (tc_sync_check:
+// the walk's bounds raise the device error word).
+static u64 fm_extract_device(tc_ctx *ctx, const tc_fm *fm, const FmExtractScratch &W, const u64 *d_starts, const u64 *d_lens,
+                             u64 nq, u64 *d_out_offs, u8 *d_out, u64 cap) {
+    hipStream_t s = ctx->stream;
+    const u64 tiles = W.tiles;
+    const u32 lg = fm_log2(fm->text_rate);
+    TC_HIP(ctx, hipMemsetAsync(W.d_bad, 0, 2 * sizeof(u32), s));
+    fm_extract_plan_kernel<<<tc_cdiv(nq, 256), 256, 0, s>>>(d_starts, d_lens, nq, fm->n, lg, W.d_len, W.d_segs, W.d_bad);
+    TC_LAUNCH_CHECK(ctx);
+    const u64 *in[2] = {W.d_len, W.d_segs};
+    u64 *tsum[2] = {W.d_tsum_b, W.d_tsum_s}, *outp[2] = {d_out_offs, W.d_soffs};
+    for (int i = 0; i < 2; i++) {
+        scan64_reduce_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(in[i], nq, tsum[i]);
+        TC_LAUNCH_CHECK(ctx);
+        scan64_spine_kernel<<<1, 1024, 0, s>>>(tsum[i], tiles);
+        TC_LAUNCH_CHECK(ctx);
+        scan64_down_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(in[i], nq, tsum[i], outp[i]);
+        TC_LAUNCH_CHECK(ctx);
+    }
+    TC_HIP(ctx, hipMemcpyAsync(d_out_offs + nq, W.d_tsum_b + tiles, sizeof(u64), hipMemcpyDeviceToDevice, s));
+    tc_d2h(ctx, &ctx->h_scalars[9], W.d_tsum_b + tiles, sizeof(u64));
+    tc_d2h(ctx, &ctx->h_scalars[8], W.d_tsum_s + tiles, sizeof(u64));
+    tc_d2h(ctx, &ctx->h_scalars[10], W.d_bad, sizeof(u32));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    const u64 need = ctx->h_scalars[9], nsegs = ctx->h_scalars[8];
+    if ((u32)ctx->h_scalars[10])
+        TC_FAIL(ctx, TC_ERR_ARG, "extract: a query lies outside the text (start is 1-based: 1 <= start, start - 1 + len <= %llu)",
+                (unsigned long long)fm->n);
+    if (need > cap || nsegs == 0) return need;
+    fm_extract_walk_kernel<<<tc_cdiv(nsegs, 256), 256, 0, s>>>(fm->d_bits, fm->lines, fm->d_tab, fm->sigma_bytes, fm->d_L,
+                                                             fm->d_isa, fm->nisa, fm->N, fm->primary, lg, d_starts, d_lens,
+                                                             W.d_soffs, d_out_offs, nq, nsegs, d_out, ctx->d_err);
+    TC_LAUNCH_CHECK(ctx);
+    return need;
+}
+
+int tc_fm_extract_dev(tc_ctx *ctx, const tc_fm *fm, const uint64_t *d_starts, const uint64_t *d_lens, uint64_t nq,
+                      uint64_t *d_out_offs, uint8_t *d_out, uint64_t *nbytes) {
+    TC_API_BEGIN(ctx)
+    if (!fm || !nbytes) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const u64 cap = *nbytes;
+    *nbytes = 0;
+    if (nq == 0) {
+        if (d_out_offs) {
+            tc_memset_async(ctx, d_out_offs, 0, sizeof(u64));
+            tc_sync_check(ctx);
+        }
+        return TC_OK;
+    }
+    if (!fm->text_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index holds no text samples (build it with tc_fm_build_self; an import without the locate part has none)");
+    if (!d_starts || !d_lens || !d_out_offs || (!d_out && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    FmExtractScratch W;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) { W.carve(A, nq); });
+    const u64 need = fm_extract_device(ctx, fm, W, d_starts, d_lens, nq, d_out_offs, d_out, cap);
+    *nbytes = need;
+    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)cap);
+    tc_sync_check(ctx);
+    TC_API_END(ctx)
+}
+
+int tc_fm_extract(tc_ctx *ctx, const tc_fm *fm, const uint64_t *starts, const uint64_t *lens, uint64_t nq,
+                  uint64_t *out_offs, uint8_t *out, uint64_t *nbytes) {
+    TC_API_BEGIN(ctx)
+    if (!fm || !nbytes) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const u64 cap = *nbytes;
+    *nbytes = 0;
+    if (nq == 0) {
+        if (out_offs) out_offs[0] = 0;
+        return TC_OK;
+    }
+    if (!fm->text_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index holds no text samples (build it with tc_fm_build_self; an import without the locate part has none)");
+    if (!starts || !lens || !out_offs || (!out && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    u64 *d_starts = nullptr, *d_lens = nullptr, *d_offs = nullptr;
+    u8 *d_out = nullptr;
+    FmExtractScratch W;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+        d_starts = A.get<u64>(nq);
+        d_lens = A.get<u64>(nq);
+        d_offs = A.get<u64>(nq + 1);
+        W.carve(A, nq);
+        d_out = A.get<u8>(cap + 16);
+    });
+    tc_h2d(ctx, d_starts, starts, nq * sizeof(u64));
+    tc_h2d(ctx, d_lens, lens, nq * sizeof(u64));
+    const u64 need = fm_extract_device(ctx, fm, W, d_starts, d_lens, nq, d_offs, d_out, cap);
+    *nbytes = need;
+    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)cap);
+    tc_d2h(ctx, out_offs, d_offs, (nq + 1) * sizeof(u64));
+    if (need) tc_d2h(ctx, out, d_out, need);
     tc_sync_check(ctx);
     TC_API_END(ctx)
 }

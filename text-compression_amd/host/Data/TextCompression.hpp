@@ -221,11 +221,19 @@ class Index {
     Index(const uint8_t *d_text, uint64_t n, uint32_t sa_rate) {
         Context::check(tc_fm_build_sampled_dev(Context::get(), d_text, n, sa_rate, &fm_));
     }
+    // with text samples (text_rate: a power of two >= 1): the index can read text ranges back (extract / extractDev)
+    Index(const std::string &text, uint32_t sa_rate, uint32_t text_rate) {
+        Context::check(tc_fm_build_self(Context::get(), (const uint8_t *)text.data(), text.size(), sa_rate, text_rate, &fm_));
+    }
+    Index(const uint8_t *d_text, uint64_t n, uint32_t sa_rate, uint32_t text_rate) {
+        Context::check(tc_fm_build_self_dev(Context::get(), d_text, n, sa_rate, text_rate, &fm_));
+    }
     Index(const Index &) = delete;
     Index &operator=(const Index &) = delete;
     ~Index() { tc_fm_free(fm_); }
     uint32_t saRate() const { return tc_fm_sa_rate(fm_); }
-    // part 0: the whole index, part 1: its locate part alone
+    uint32_t textRate() const { return tc_fm_text_rate(fm_); }
+    // part 0: the whole index, part 1: its locate part alone, part 2: its extract part alone
     uint64_t deviceBytes(int part = 0) const { return tc_fm_device_bytes(fm_, part); }
     // d_pats / d_offs [npat + 1] / d_hit_offs [npat + 1] / d_hits [cap]: device arrays.  Returns the number of hits; when it
     // exceeds cap nothing was written to d_hits and the caller repeats the call with that capacity.
@@ -235,6 +243,29 @@ class Index {
         int rc = tc_fm_locate_dev(Context::get(), fm_, d_pats, d_offs, npat, d_hit_offs, d_hits, &nh);
         if (rc != TC_ERR_CAPACITY) Context::check(rc);
         return nh;
+    }
+    // the text ranges [starts[q], starts[q] + lens[q]), starts 1-based as locate answers positions; one string per query
+    std::vector<std::string> extract(const std::vector<uint64_t> &starts, const std::vector<uint64_t> &lens) const {
+        std::vector<std::string> res(starts.size());
+        if (starts.empty() || lens.size() != starts.size()) return res;
+        uint64_t total = 0;
+        for (uint64_t l : lens) total += l;
+        std::vector<uint64_t> offs(starts.size() + 1);
+        std::string flat(total, '\0');
+        uint64_t nb = total;
+        Context::check(tc_fm_extract(Context::get(), fm_, starts.data(), lens.data(), starts.size(), offs.data(),
+                                     (uint8_t *)&flat[0], &nb));
+        for (size_t q = 0; q < starts.size(); q++) res[q] = flat.substr(offs[q], offs[q + 1] - offs[q]);
+        return res;
+    }
+    // d_starts / d_lens [nq] / d_out_offs [nq + 1] / d_out [cap]: device arrays.  Returns the number of bytes; when it
+    // exceeds cap nothing was written to d_out and the caller repeats the call with that capacity.
+    uint64_t extractDev(const uint64_t *d_starts, const uint64_t *d_lens, uint64_t nq, uint64_t *d_out_offs, uint8_t *d_out,
+                        uint64_t cap) const {
+        uint64_t nb = cap;
+        int rc = tc_fm_extract_dev(Context::get(), fm_, d_starts, d_lens, nq, d_out_offs, d_out, &nb);
+        if (rc != TC_ERR_CAPACITY) Context::check(rc);
+        return nb;
     }
     const tc_fm *handle() const { return fm_; }
 

@@ -55,6 +55,17 @@ foreign import ccall unsafe "tc_fm_device_bytes"
   c_tc_fm_device_bytes :: Ptr TcFm -> Int32 -> Word64
 foreign import ccall safe "tc_fm_locate_dev"
   c_tc_fm_locate_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Ptr Word64 -> Ptr Word64 -> Ptr Word64 -> IO Int32
+-- the index with text samples (text_rate: a power of two up to 4096) and extract: the text ranges (1-based start, length)
+-- read back from the index (no counterpart in the reference)
+foreign import ccall safe "tc_fm_build_self"
+  c_tc_fm_build_self :: Ptr TcCtx -> Ptr Word8 -> Word64 -> Word32 -> Word32 -> Ptr (Ptr TcFm) -> IO Int32
+foreign import ccall safe "tc_fm_build_self_dev"
+  c_tc_fm_build_self_dev :: Ptr TcCtx -> Ptr Word8 -> Word64 -> Word32 -> Word32 -> Ptr (Ptr TcFm) -> IO Int32
+foreign import ccall unsafe "tc_fm_text_rate" c_tc_fm_text_rate :: Ptr TcFm -> Word32
+foreign import ccall safe "tc_fm_extract"
+  c_tc_fm_extract :: Ptr TcCtx -> Ptr TcFm -> Ptr Word64 -> Ptr Word64 -> Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
+foreign import ccall safe "tc_fm_extract_dev"
+  c_tc_fm_extract_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word64 -> Ptr Word64 -> Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
 -- stored / shipped form (no counterpart in the reference): one record, or any length cut into records
 foreign import ccall unsafe "tc_container_bound"
   c_tc_container_bound :: Word64 -> Word32 -> Word64

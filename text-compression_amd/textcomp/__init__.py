@@ -344,17 +344,21 @@ class Context:
         return out[:got.value].tobytes()
 
     # ----------------------------------------------------------- FM-index
-    def fm_build(self, text, sa_rate=1):
+    def fm_build(self, text, sa_rate=1, text_rate=0):
         """sa_rate > 1 (a power of two up to TC_FM_MAX_SA_RATE): keep every sa_rate-th suffix-array entry only
-        (tc_fm_build_sampled); locate answers the same hits by walking the LF mapping"""
-        return FMIndexHandle(self, text, sa_rate=sa_rate)
+        (tc_fm_build_sampled); locate answers the same hits by walking the LF mapping.  text_rate > 0 (a power of two
+        up to TC_FM_MAX_SA_RATE): also keep the row of every text_rate-th text position (tc_fm_build_self), so that
+        extract can read text ranges back from the index"""
+        return FMIndexHandle(self, text, sa_rate=sa_rate, text_rate=text_rate)
 
-    def fm_build_dev(self, d_text, sa_rate=1):
+    def fm_build_dev(self, d_text, sa_rate=1, text_rate=0):
         """index of a text that already lies in HBM (a torch uint8 tensor on this context's device): tc_fm_build_dev /
-        tc_fm_build_sampled_dev"""
+        tc_fm_build_sampled_dev / tc_fm_build_self_dev"""
         h = C.c_void_p()
         p = C.c_void_p(d_text.data_ptr()) if d_text.numel() else None
-        if sa_rate == 1:
+        if text_rate:
+            self._check(self.lib.tc_fm_build_self_dev(self.handle, p, d_text.numel(), int(sa_rate), int(text_rate), C.byref(h)))
+        elif sa_rate == 1:
             self._check(self.lib.tc_fm_build_dev(self.handle, p, d_text.numel(), C.byref(h)))
         else:
             self._check(self.lib.tc_fm_build_sampled_dev(self.handle, p, d_text.numel(), int(sa_rate), C.byref(h)))
@@ -364,14 +368,16 @@ class Context:
 class FMIndexHandle:
     """`tc_fm`: the device-resident FM-index of one text."""
 
-    def __init__(self, ctx, text, _handle=None, _n=0, sa_rate=1):
+    def __init__(self, ctx, text, _handle=None, _n=0, sa_rate=1, text_rate=0):
         self._ctx = ctx
         if _handle is not None:      # an index that arrived from another GPU (textcomp.fmshard)
             self._h, self.n = _handle, _n
             return
         t = _u8(text)
         h = C.c_void_p()
-        if sa_rate == 1:
+        if text_rate:
+            ctx._check(ctx.lib.tc_fm_build_self(ctx.handle, _ptr(t) if len(t) else None, len(t), int(sa_rate), int(text_rate), C.byref(h)))
+        elif sa_rate == 1:
             ctx._check(ctx.lib.tc_fm_build(ctx.handle, _ptr(t) if len(t) else None, len(t), C.byref(h)))
         else:
             ctx._check(ctx.lib.tc_fm_build_sampled(ctx.handle, _ptr(t) if len(t) else None, len(t), int(sa_rate), C.byref(h)))
@@ -383,9 +389,61 @@ class FMIndexHandle:
         """1: full suffix array; k > 1: every k-th entry kept; 0: no locate part (count-only import, empty index)"""
         return int(self._ctx.lib.tc_fm_sa_rate(self._h))
 
+    @property
+    def text_rate(self):
+        """k >= 1: the row of every k-th text position is kept (extract works); 0: no text samples"""
+        return int(self._ctx.lib.tc_fm_text_rate(self._h))
+
     def device_bytes(self, part=0):
-        """device bytes the index holds: part 0 = everything, 1 = the locate part alone"""
+        """device bytes the index holds: part 0 = everything, 1 = the locate part alone, 2 = the extract part alone"""
         return int(self._ctx.lib.tc_fm_device_bytes(self._h, int(part)))
+
+    def extract(self, starts, lens):
+        """text ranges read back from the index: starts are 1-based (what locate answers), -> list of bytes, one per
+        query, equal to text[start - 1 : start - 1 + len]: tc_fm_extract"""
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        ln = np.ascontiguousarray(lens, dtype=np.uint64)
+        if st.shape != ln.shape or st.ndim != 1:
+            raise ValueError("starts and lens must be two sequences of one length")
+        nq = len(st)
+        if nq == 0:
+            return []
+        ctx = self._ctx
+        offs = np.empty(nq + 1, np.uint64)
+        cap = 1 << 16
+        while True:
+            out = np.empty(max(cap, 1), np.uint8)
+            nb = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_extract(ctx.handle, self._h, _ptr(st), _ptr(ln), nq, _ptr(offs), _ptr(out), C.byref(nb))
+            if rc == _lib.TC_ERR_CAPACITY and int(nb.value) > cap:
+                cap = int(nb.value)
+                continue
+            ctx._check(rc)
+            break
+        blob = out[:int(nb.value)].tobytes()
+        return [blob[int(offs[i]):int(offs[i + 1])] for i in range(nq)]
+
+    def extract_dev(self, d_starts, d_lens, nq, cap=None):
+        """queries resident on the device (two uint64/int64 tensors [nq], starts 1-based) -> (offs int64 tensor
+        [nq + 1], bytes uint8 tensor [total]), both on the device: tc_fm_extract_dev"""
+        import torch
+        ctx = self._ctx
+        dev = d_starts.device
+        offs = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        if nq == 0:
+            return offs, torch.zeros(0, dtype=torch.uint8, device=dev)
+        cap = max(int(cap) if cap is not None else 128 * nq, 1)
+        for _ in range(2):
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            nb = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_extract_dev(ctx.handle, self._h, C.c_void_p(d_starts.data_ptr()), C.c_void_p(d_lens.data_ptr()),
+                                           nq, C.c_void_p(offs.data_ptr()), C.c_void_p(out.data_ptr()), C.byref(nb))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nb.value), 1)
+        ctx._check(rc)
+        return offs, out[:int(nb.value)]
 
     def locate_dev(self, d_pats, d_offs, npat, cap=None):
         """patterns resident on the device (as count_dev) -> (hit_offs uint64-as-int64 tensor [npat + 1], hits tensor

@@ -101,12 +101,17 @@ SYMBOLS = [
     ("tc_fm_build_sampled", _INT, [_P, _P, _U64, _U32, C.POINTER(_P)]),
     ("tc_fm_build_sampled_dev", _INT, [_P, _P, _U64, _U32, C.POINTER(_P)]),
     ("tc_fm_sa_rate", _U32, [_P]),
+    ("tc_fm_build_self", _INT, [_P, _P, _U64, _U32, _U32, C.POINTER(_P)]),
+    ("tc_fm_build_self_dev", _INT, [_P, _P, _U64, _U32, _U32, C.POINTER(_P)]),
+    ("tc_fm_text_rate", _U32, [_P]),
     ("tc_fm_device_bytes", _U64, [_P, _INT]),
     ("tc_fm_free", None, [_P]),
     ("tc_fm_count", _INT, [_P, _P, _P, _P, _U64, _P]),
     ("tc_fm_count_dev", _INT, [_P, _P, _P, _P, _U64, _P]),
     ("tc_fm_locate", _INT, [_P, _P, _P, _P, _U64, _P, _P, _PU64]),
     ("tc_fm_locate_dev", _INT, [_P, _P, _P, _P, _U64, _P, _P, _PU64]),
+    ("tc_fm_extract", _INT, [_P, _P, _P, _P, _U64, _P, _P, _PU64]),
+    ("tc_fm_extract_dev", _INT, [_P, _P, _P, _P, _U64, _P, _P, _PU64]),
     ("tc_fm_info", _INT, [_P, _PU64, _PU32, _P, _P, _PU64]),
     ("tc_comm_unique_id", _INT, [_P, _P]),
     ("tc_comm_create", _INT, [_P, _P, _INT, _INT, C.POINTER(_P)]),
