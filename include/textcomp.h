@@ -409,6 +409,44 @@ int tc_fm_extract(tc_ctx *ctx, const tc_fm *fm, const uint64_t *starts, const ui
  * nbytes is a host word.  tc_fm_extract is this call between a copy in and a copy out. */
 int tc_fm_extract_dev(tc_ctx *ctx, const tc_fm *fm, const uint64_t *d_starts, const uint64_t *d_lens, uint64_t nq,
                       uint64_t *d_out_offs, uint8_t *d_out, uint64_t *nbytes);
+/* Search with mismatches: count and locate within Hamming distance k (an addition to the reference's surface, as the
+ * sampled locate and extract are).  Patterns as in tc_fm_count: pattern j = pats[offs[j] .. offs[j+1]), result order =
+ * pattern order.
+ * COUNT.  For pattern p of length m, out[j] is the number of text positions i, 0 <= i <= n - m, with
+ * Hamming(T[i .. i+m), p) <= k.  Substitutions only: there are no insertions or deletions.  A match never runs over the
+ * end of the text.  m = 0 gives 0, as tc_fm_count answers Nothing.  m > n gives 0.  m <= k gives n - m + 1.
+ * BYTES THAT DO NOT OCCUR IN THE TEXT.  A pattern byte that does not occur in the text can only be a mismatch.  This is a
+ * deliberate departure from tc_fm_count: that call stops its loop at such a byte, as the reference does (quirk Q10), and
+ * answers for the suffix of the pattern read so far.  Consequence: tc_fm_count_mm(k = 0) equals tc_fm_count for every
+ * non-empty pattern all of whose bytes occur in the text, and is 0 where a byte does not.
+ * LOCATE.  Positions are 1-based, as in tc_fm_locate.  hit_mm[h] is the Hamming distance of hit h; hit_mm may be NULL.
+ * hit_offs[npat + 1], *nhits (in = capacity, out = total) and TC_ERR_CAPACITY (the needed total is set, nothing is written
+ * to hits or hit_mm) behave exactly as in tc_fm_locate.  Every position appears once: distinct variant strings have
+ * disjoint suffix-array intervals, and the enumeration visits each variant once.  The order inside one pattern's hits is
+ * the kernel's enumeration order: it is deterministic, and identical across the host and _dev entry points and across a
+ * full and a sampled index of the same text; it is not otherwise specified (in particular it is neither position order
+ * nor distance order).
+ * ERRORS AND EDGES.  k > TC_FM_MAX_MISMATCH: TC_ERR_ARG.  A null index or null buffers: TC_ERR_ARG.  npat = 0: TC_OK.  The
+ * empty index answers zeros.  An index imported without its locate part answers tc_fm_count_mm, and TC_ERR_ARG for
+ * tc_fm_locate_mm, as with the exact calls.
+ * The _dev forms take everything in HBM (d_hit_offs [npat + 1], d_hits [*nhits], d_hit_mm [*nhits] or NULL; nhits is a host
+ * word); the host forms are those calls between a copy in and a copy out.  Scratch comes from the calling ctx: any number
+ * of ctxs may search one tc_fm at once.
+ * Cost: a bounded depth-first enumeration of the strings within distance k of the pattern that occur in the text, one lane
+ * per pattern, one dependent random 64-byte line per node visited; a node with budget left offers every byte value of the
+ * text as a substitute, so a search costs about (live nodes with budget left) x sigma lines and grows steeply with k and
+ * with the alphabet.  locate runs the enumeration twice (sizes, then hits).  On an IMPORTED index the
+ * search reads caller data: it is bounded on any bytes (intervals that leave [1, N] count as empty), and the walk of a
+ * sampled index answers TC_ERR_MALFORMED as in tc_fm_locate_dev. */
+#define TC_FM_MAX_MISMATCH 3
+int tc_fm_count_mm(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat, uint32_t k,
+                   int64_t *out);
+int tc_fm_count_mm_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint32_t k,
+                       int64_t *d_out);
+int tc_fm_locate_mm(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat, uint32_t k,
+                    uint64_t *hit_offs, uint64_t *hits, uint8_t *hit_mm, uint64_t *nhits);
+int tc_fm_locate_mm_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint32_t k,
+                        uint64_t *d_hit_offs, uint64_t *d_hits, uint8_t *d_hit_mm, uint64_t *nhits);
 /* seqToCc / seqFromFMIndex views for the Haskell shim: present symbols (sorted,
  * Nothing first) with C[c]; and L / primary. */
 int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, uint64_t *c_val,

@@ -1,0 +1,449 @@
+"""FM-index search with mismatches (tc_fm_count_mm / tc_fm_locate_mm and their _dev forms) against the brute-force
+reference of tests/mismatch_ref.py: every case is checked exactly, on the smallest shapes at which the kernel can go wrong
+(rank-line boundaries, every alphabet class, bytes the text does not hold, the length edges, a full frame stack, a
+divergent batch), through the host and the device entry points, on a full and on a sampled index."""
+import ctypes as C
+import os
+import subprocess
+import sys
+import threading
+import traceback
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if __name__ == "__main__":      # the child of test_two_contexts_search_one_index
+    for _p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "text-compression_amd")):
+        if _p not in sys.path:
+            sys.path.insert(0, _p)
+
+import mismatch_ref as R
+
+pytestmark = pytest.mark.gpu
+
+LENGTHS = (1, 2, 3, 4, 8, 17, 32)
+SAMPLED_RATES = (4, 4096)       # 4096 exceeds every n here: every walk ends at the primary row
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import textcomp
+    c = textcomp.Context(0)
+    yield c
+    c.close()
+
+
+# ------------------------------------------------------------------------------------------------ helpers
+def _text(seed, n, alphabet):
+    rng = np.random.default_rng(seed)
+    a = np.frombuffer(bytes(alphabet), np.uint8)
+    return a[rng.integers(0, len(a), n)].tobytes()
+
+
+def _patterns(seed, tb, alphabet, lengths=LENGTHS):
+    """per length: substrings of the text with 0 .. 3 planted substitutions, and two random strings"""
+    rng = np.random.default_rng(seed)
+    a = np.frombuffer(bytes(alphabet), np.uint8)
+    n, pats = len(tb), []
+    for m in lengths:
+        if m > n:
+            continue
+        for planted in range(4):
+            o = int(rng.integers(0, n - m + 1))
+            p = bytearray(tb[o:o + m])
+            for j in rng.choice(m, size=min(planted, m), replace=False):
+                p[int(j)] = int(a[rng.integers(0, len(a))])
+            pats.append(bytes(p))
+        for _ in range(2):
+            pats.append(a[rng.integers(0, len(a), m)].tobytes())
+    return pats
+
+
+def _dev_patterns(pats):
+    import torch
+    from textcomp import FMIndexHandle
+    flat, offs = FMIndexHandle._pack(pats)
+    return torch.from_numpy(flat).cuda(), torch.from_numpy(offs.astype(np.int64)).cuda()
+
+
+def _locate_flat(fm, pats, k):
+    """tc_fm_locate_mm -> (hit_offs, hits, hit_mm) as raw numpy arrays"""
+    from textcomp import FMIndexHandle
+    ctx = fm._ctx
+    flat, offs = FMIndexHandle._pack(pats)
+    hoffs = np.zeros(len(pats) + 1, np.uint64)
+    cap = 1 << 12
+    for _ in range(2):
+        hits, mm, nh = np.empty(cap, np.uint64), np.empty(cap, np.uint8), C.c_uint64(cap)
+        rc = ctx.lib.tc_fm_locate_mm(ctx.handle, fm._h, flat.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                                     len(pats), k, hoffs.ctypes.data_as(C.c_void_p), hits.ctypes.data_as(C.c_void_p),
+                                     mm.ctypes.data_as(C.c_void_p), C.byref(nh))
+        if rc != -2:
+            break
+        cap = int(nh.value)
+    ctx._check(rc)
+    return hoffs, hits[:nh.value], mm[:nh.value]
+
+
+def _locate_flat_dev(fm, pats, k):
+    d_flat, d_offs = _dev_patterns(pats)
+    hoffs, hits, mm = fm.locate_mm_dev(d_flat, d_offs, len(pats), k)
+    return hoffs.cpu().numpy().astype(np.uint64), hits.cpu().numpy().astype(np.uint64), mm.cpu().numpy()
+
+
+def _count_dev(fm, pats, k):
+    d_flat, d_offs = _dev_patterns(pats)
+    return fm.count_mm_dev(d_flat, d_offs, len(pats), k).cpu().numpy()
+
+
+def _check_against_reference(tb, pats, k, cnt, hoffs, hits, mm):
+    assert hoffs[0] == 0 and hoffs[-1] == len(hits) == len(mm)
+    assert np.array_equal(np.diff(hoffs.astype(np.int64)), cnt)           # sum(hit_offs diffs) == count_mm, per pattern
+    for i, p in enumerate(pats):
+        want_pos, want_mm = R.hits(tb, p, k)
+        a, b = int(hoffs[i]), int(hoffs[i + 1])
+        got_pos, got_mm = R.sorted_pairs(hits[a:b], mm[a:b])
+        assert cnt[i] == len(want_pos), (len(tb), k, p)
+        assert np.array_equal(got_pos, want_pos) and np.array_equal(got_mm, want_mm), (len(tb), k, p)
+    print("n=%d k=%d: %d patterns, %d hits, all as the reference" % (len(tb), k, len(pats), len(hits)))
+
+
+def _four_ways(ctx, tb, pats, ks, ways="all"):
+    """count_mm and locate_mm through the host and the _dev entry, on a full and on the sampled indexes: equal as raw
+    arrays, and equal to the reference once sorted per pattern"""
+    full = ctx.fm_build(tb)
+    sampled = [ctx.fm_build(tb, sa_rate=r) for r in SAMPLED_RATES]
+    try:
+        for k in ks:
+            cnt = full.count_mm(pats, k)
+            hoffs, hits, mm = _locate_flat(full, pats, k)
+            _check_against_reference(tb, pats, k, cnt, hoffs, hits, mm)
+            if ways != "all":
+                continue
+            assert np.array_equal(_count_dev(full, pats, k), cnt)
+            for got in [_locate_flat_dev(full, pats, k)] + [f(s, pats, k) for s in sampled for f in (_locate_flat, _locate_flat_dev)]:
+                assert np.array_equal(got[0], hoffs) and np.array_equal(got[1], hits) and np.array_equal(got[2], mm), k
+            for s in sampled:
+                assert np.array_equal(s.count_mm(pats, k), cnt) and np.array_equal(_count_dev(s, pats, k), cnt)
+    finally:
+        full.close()
+        for s in sampled:
+            s.close()
+
+
+# ------------------------------------------------------------------------------------------------ 1: rank-line boundaries
+@pytest.mark.parametrize("n", [1, 2, 446, 447, 448, 449, 895, 896, 897, 4096])
+def test_rank_line_boundaries(ctx, n):
+    """FM_LINE_BITS = 448: N = n + 1 rows on either side of one and of two lines"""
+    tb = _text(0x3300 + n, n, b"ACGT")
+    _four_ways(ctx, tb, _patterns(0x3400 + n, tb, b"ACGT"), (0, 1, 2, 3))
+
+
+# ------------------------------------------------------------------------------------------------ 2: alphabets
+def test_unary_text(ctx):
+    """sigma = 1: no substitute exists; a pattern of another letter can only be mismatches"""
+    tb = b"A" * 500
+    pats = [b"A", b"AAAA", b"A" * 32, b"C", b"AC", b"CAAC", b"ACCCA", b"A" * 15 + b"CC" + b"A" * 15, b"CCCC"]
+    _four_ways(ctx, tb, pats, (0, 1, 2, 3))
+
+
+@pytest.mark.parametrize("alphabet", [b"AC", b"ACGT", b"ACGTN"])
+def test_small_alphabets_take_pair_steps(ctx, alphabet):
+    """sigma = 2, 4, 5: the index has pair vectors and the exact tail takes pair steps"""
+    tb = _text(0x3500, 1500, alphabet)
+    _four_ways(ctx, tb, _patterns(0x3501, tb, alphabet), (0, 1, 2, 3))
+
+
+def test_sigma_5_and_6_from_one_seed(ctx):
+    """the same text but for one byte: with five byte values the exact tail takes pair steps, with six it cannot -- a
+    difference between the two isolates the pair tail (both are checked against the reference)"""
+    t5 = _text(0x3500, 1500, b"ACGTN")
+    t6 = bytearray(t5)
+    t6[777] = ord("X")
+    pats = _patterns(0x3501, t5, b"ACGTN")
+    _four_ways(ctx, t5, pats, (0, 1, 2, 3))
+    _four_ways(ctx, bytes(t6), pats, (0, 1, 2, 3))
+
+
+def test_full_byte_alphabet(ctx):
+    """sigma = 256, n = 4096: every byte value is a substitute.  A node with budget left costs 256 lookups, so k = 3 (about
+    10^6 lookups per lane whatever the pattern) is checked through one entry path and k <= 2 through all of them"""
+    rng = np.random.default_rng(0x3600)
+    t = np.concatenate([np.arange(256, dtype=np.uint8), rng.integers(0, 256, 4096 - 256).astype(np.uint8)])
+    rng.shuffle(t)
+    tb = t.tobytes()
+    pats = _patterns(0x3601, tb, bytes(range(256)), lengths=(1, 2, 3, 8, 32))
+    _four_ways(ctx, tb, pats, (0, 1, 2))
+    _four_ways(ctx, tb, pats[:8] + pats[-6:], (3,), ways="host")
+
+
+# ------------------------------------------------------------------------------------------------ 3: absent bytes
+def test_bytes_the_text_does_not_hold(ctx):
+    """a pattern byte that does not occur in the text can only be a mismatch -- unlike tc_fm_count, which stops at it"""
+    tb = _text(0x3700, 1000, b"ACGT")
+    s = tb[300:316]
+    pats = [b"Z" + s[1:], s[:8] + b"Z" + s[9:], s[:-1] + b"Z",              # first, middle, last
+            b"Z" + s[1:7] + b"Z" + s[8:15] + b"Z",                         # three of them
+            b"ZZ" + s[2:12] + b"ZZ",                                       # four: more than any k
+            b"Z", b"ZZ", b"ZZZ", b"ZZZZ", b"ZQ" + s[2:]]
+    _four_ways(ctx, tb, pats, (0, 1, 2, 3))
+    fm = ctx.fm_build(tb)
+    try:
+        exact = fm.count([pats[0], pats[1]])
+        assert exact[0] == R.count(tb, s[1:], 0) > 0      # tc_fm_count answers for the suffix read before the Z ...
+        assert exact[1] == R.count(tb, s[9:], 0) > 0
+        assert fm.count_mm(pats, 0).tolist() == [0] * len(pats)             # ... tc_fm_count_mm(k = 0) answers 0
+        for k in (1, 2, 3):                                                 # more absent bytes than k: nothing
+            got = fm.count_mm([pats[4], b"Z" * (k + 1) + s], k)
+            assert got.tolist() == [0, 0]
+    finally:
+        fm.close()
+
+
+# ------------------------------------------------------------------------------------------------ 4: length edges
+@pytest.mark.parametrize("n", [5, 449])
+def test_length_edges(ctx, n):
+    tb = _text(0x3800 + n, n, b"ACGT")
+    pats = [b"", tb + b"A", tb + tb, tb, tb[:-1] + b"A", b"T" + tb[1:], b"A", b"CG", b"TTT", b"ZZZ", tb[:n - 1], tb[1:]]
+    _four_ways(ctx, tb, pats, (0, 1, 2, 3))
+    fm = ctx.fm_build(tb)
+    try:
+        for k in (1, 2, 3):
+            short = [b"G" * m for m in range(1, k + 1)] + [b"Z" * k]
+            cnt = fm.count_mm(short + [b"", tb + b"A"], k)
+            assert cnt.tolist() == [n - len(p) + 1 for p in short] + [0, 0]          # m <= k: every window is a hit
+            for p, (pos, mm) in zip(short, fm.locate_mm(short, k)):
+                assert sorted(pos.tolist()) == list(range(1, n - len(p) + 2))
+    finally:
+        fm.close()
+
+
+# ------------------------------------------------------------------------------------------------ 5: many survivors
+@pytest.mark.parametrize("tb", [b"ACG" * 450, b"A" * 700 + b"C" * 650], ids=["period3", "two_runs"])
+def test_many_survivors(ctx, tb):
+    """k = 3 on texts where most branches live: the frame stack reaches depth 4 at many nodes"""
+    pats = [tb[0:32], tb[1:33], tb[684:716], tb[690:707], tb[5:13], b"A" * 32, b"ACGACGTCGACGACGAAGACGACG", b"AAAACCCC",
+            b"CCCCAAAA", b"ACGT" * 8, tb[3:20][::-1]]
+    _four_ways(ctx, tb, pats, (3,))
+    fm = ctx.fm_build(tb)
+    try:
+        total = int(fm.count_mm(pats, 3).sum())
+        assert total == sum(R.count(tb, p, 3) for p in pats) and total > 2000
+    finally:
+        fm.close()
+
+
+# ------------------------------------------------------------------------------------------------ 6: divergence
+def test_divergent_batch_keeps_pattern_order(ctx):
+    """257 patterns -- one workgroup and one lane -- of lengths 0 .. 32 mixed, k = 2: result order = pattern order"""
+    tb = _text(0x3900, 4096, b"ACGT")
+    rng = np.random.default_rng(0x3901)
+    pats = []
+    for i in range(257):
+        m = int(rng.integers(0, 33))
+        o = int(rng.integers(0, len(tb) - 32))
+        p = bytearray(tb[o:o + m])
+        if m and i % 3:
+            p[int(rng.integers(0, m))] = ord("ACGT"[i % 4])
+        pats.append(bytes(p))
+    assert {0, 32} <= {len(p) for p in pats}
+    _four_ways(ctx, tb, pats, (2,))
+
+
+# ------------------------------------------------------------------------------------------------ 7: agreement with exact search
+def test_k0_agrees_with_exact_search(ctx):
+    for alphabet, n in ((b"ACGT", 3000), (b"ACGTNX", 3000)):
+        tb = _text(0x3A00 + len(alphabet), n, alphabet)
+        pats = [p for p in _patterns(0x3A01, tb, alphabet) if p]
+        for rate in (1, 4):
+            fm = ctx.fm_build(tb, sa_rate=rate)
+            try:
+                assert np.array_equal(fm.count_mm(pats, 0), fm.count(pats))
+                for (pos, mm), exact in zip(fm.locate_mm(pats, 0), fm.locate(pats)):
+                    assert sorted(pos.tolist()) == sorted(exact.tolist()) and not mm.any()
+            finally:
+                fm.close()
+
+
+# ------------------------------------------------------------------------------------------------ 8: extract round trip
+def test_extract_differs_from_the_pattern_in_hit_mm_bytes(ctx):
+    tb = _text(0x3B00, 2000, b"ACGTN")
+    pats = [p for p in _patterns(0x3B01, tb, b"ACGTN") if len(p) >= 4]
+    fm = ctx.fm_build(tb, sa_rate=4, text_rate=8)
+    try:
+        seen = 0
+        for p, (pos, mm) in zip(pats, fm.locate_mm(pats, 2)):
+            if len(pos) == 0:
+                continue
+            for got, d in zip(fm.extract(pos, np.full(len(pos), len(p), np.uint64)), mm):
+                assert len(got) == len(p) and sum(x != y for x, y in zip(got, p)) == int(d)
+                seen += 1
+        assert seen > 20
+    finally:
+        fm.close()
+
+
+# ------------------------------------------------------------------------------------------------ 9: errors and edges
+def _raw_locate(ctx, fm, pats, k, cap, with_mm=True, fill=0xAB):
+    from textcomp import FMIndexHandle
+    flat, offs = FMIndexHandle._pack(pats)
+    hoffs = np.zeros(len(pats) + 1, np.uint64)
+    hits = np.full(max(cap, 1), fill * 0x0101010101010101, np.uint64)
+    mm = np.full(max(cap, 1), fill, np.uint8)
+    nh = C.c_uint64(cap)
+    rc = ctx.lib.tc_fm_locate_mm(ctx.handle, fm._h if fm is not None else None, flat.ctypes.data_as(C.c_void_p),
+                                 offs.ctypes.data_as(C.c_void_p), len(pats), k, hoffs.ctypes.data_as(C.c_void_p),
+                                 hits.ctypes.data_as(C.c_void_p), mm.ctypes.data_as(C.c_void_p) if with_mm else None, C.byref(nh))
+    return rc, int(nh.value), hoffs, hits, mm
+
+
+def test_errors_and_edges(ctx):
+    import torch
+    import textcomp
+    from textcomp import _lib, FMIndexHandle
+    tb = _text(0x3C00, 900, b"ACGT")
+    pats = [tb[10:22], tb[100:108], b"ACG", b""]
+    d_flat, d_offs = _dev_patterns(pats)
+    for rate in (1, 4):
+        fm = ctx.fm_build(tb, sa_rate=rate)
+        try:
+            # k above the maximum: all four entry points
+            big = _lib.TC_FM_MAX_MISMATCH + 1
+            for call in (lambda: fm.count_mm(pats, big), lambda: fm.locate_mm(pats, big),
+                         lambda: fm.count_mm_dev(d_flat, d_offs, len(pats), big),
+                         lambda: fm.locate_mm_dev(d_flat, d_offs, len(pats), big)):
+                with pytest.raises(textcomp.TcError) as ei:
+                    call()
+                assert ei.value.code == _lib.TC_ERR_ARG
+            # capacity one short: the needed total, nothing written; then exactly enough
+            want_off, want_hits, want_mm = _locate_flat(fm, pats, 2)
+            total = len(want_hits)
+            assert total > 3
+            rc, need, _, hits, mm = _raw_locate(ctx, fm, pats, 2, total - 1)
+            assert rc == _lib.TC_ERR_CAPACITY and need == total
+            assert (hits == 0xABABABABABABABAB).all() and (mm == 0xAB).all()
+            d_hits = torch.full((total,), -7, dtype=torch.int64, device="cuda")
+            d_mm = torch.full((total,), 0xAB, dtype=torch.uint8, device="cuda")
+            d_hoffs = torch.zeros(len(pats) + 1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            nh = C.c_uint64(total - 1)
+            rc = ctx.lib.tc_fm_locate_mm_dev(ctx.handle, fm._h, C.c_void_p(d_flat.data_ptr()), C.c_void_p(d_offs.data_ptr()),
+                                             len(pats), 2, C.c_void_p(d_hoffs.data_ptr()), C.c_void_p(d_hits.data_ptr()),
+                                             C.c_void_p(d_mm.data_ptr()), C.byref(nh))
+            assert rc == _lib.TC_ERR_CAPACITY and nh.value == total
+            assert bool((d_hits == -7).all()) and bool((d_mm == 0xAB).all())
+            rc, need, hoffs, hits, mm = _raw_locate(ctx, fm, pats, 2, total)
+            assert rc == 0 and need == total
+            assert np.array_equal(hoffs, want_off) and np.array_equal(hits, want_hits) and np.array_equal(mm, want_mm)
+            # hit_mm = NULL
+            rc, need, hoffs, hits, mm = _raw_locate(ctx, fm, pats, 2, total, with_mm=False)
+            assert rc == 0 and need == total and np.array_equal(hits, want_hits) and (mm == 0xAB).all()
+            # npat = 0
+            assert len(fm.count_mm([], 1)) == 0 and fm.locate_mm([], 1) == []
+            rc, need, *_ = _raw_locate(ctx, fm, [], 1, 5)
+            assert rc == 0 and need == 0
+            # null index, null buffers
+            rc, *_ = _raw_locate(ctx, None, pats, 1, 5)
+            assert rc == _lib.TC_ERR_ARG
+            out = np.zeros(len(pats), np.int64)
+            flat, offs = FMIndexHandle._pack(pats)
+            assert ctx.lib.tc_fm_count_mm(ctx.handle, fm._h, None, offs.ctypes.data_as(C.c_void_p), len(pats), 1,
+                                          out.ctypes.data_as(C.c_void_p)) == _lib.TC_ERR_ARG
+            assert ctx.lib.tc_fm_count_mm(ctx.handle, fm._h, flat.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                                          len(pats), 1, None) == _lib.TC_ERR_ARG
+            # a count-only import: count works, locate is TC_ERR_ARG
+            imp = FMIndexHandle.import_dev(ctx, fm.export_dev(with_locate=False), n=len(tb))
+            try:
+                assert imp.sa_rate == 0
+                assert np.array_equal(imp.count_mm(pats, 2), fm.count_mm(pats, 2))
+                assert np.array_equal(_count_dev(imp, pats, 2), fm.count_mm(pats, 2))
+                rc, *_ = _raw_locate(ctx, imp, pats, 2, 1 << 10)
+                assert rc == _lib.TC_ERR_ARG
+                with pytest.raises(textcomp.TcError) as ei:
+                    imp.locate_mm_dev(d_flat, d_offs, len(pats), 2)
+                assert ei.value.code == _lib.TC_ERR_ARG
+            finally:
+                imp.close()
+        finally:
+            fm.close()
+    # the empty index answers zeros
+    empty = ctx.fm_build(b"")
+    try:
+        assert empty.count_mm(pats, 3).tolist() == [0] * len(pats)
+        assert _count_dev(empty, pats, 3).tolist() == [0] * len(pats)
+        assert all(len(pos) == 0 and len(mm) == 0 for pos, mm in empty.locate_mm(pats, 3))
+        hoffs, hits, mm = _locate_flat_dev(empty, pats, 3)
+        assert not hoffs.any() and len(hits) == 0
+    finally:
+        empty.close()
+
+
+def test_python_mirrors(ctx):
+    from textcomp import fmindex
+    tb = b"ACGTACGTTACGA"
+    pats = [b"ACGT", b"TTT", b"ZZZZ"]
+    got = fmindex.bytestringFMIndexCountMismatchS(pats, tb, 1, ctx)
+    assert got == [(p, R.count(tb, p, 1) or None) for p in pats]
+    assert fmindex.bytestringFMIndexCountMismatchP(pats, tb, 1, ctx) == got
+    loc = fmindex.bytestringFMIndexLocateMismatchS(pats, tb, 1, ctx)
+    for (p, h), q in zip(loc, pats):
+        pos, mm = R.hits(tb, q, 1)
+        assert p == q and sorted(h) == list(zip(pos.tolist(), mm.tolist()))
+    assert fmindex.bytestringFMIndexLocateMismatchP(pats, tb, 1, ctx) == loc
+    tpats = [p.decode() for p in pats]
+    assert fmindex.textFMIndexCountMismatchS(tpats, tb.decode(), 1, ctx) == [(p, c) for p, (_, c) in zip(tpats, got)]
+    assert fmindex.textFMIndexLocateMismatchP(tpats, tb.decode(), 1, ctx) == [(p, h) for p, (_, h) in zip(tpats, loc)]
+    assert fmindex.bytestringFMIndexCountMismatchS([], tb, 1, ctx) == [] == fmindex.bytestringFMIndexLocateMismatchS(pats, b"", 1, ctx)
+
+
+# ------------------------------------------------------------------------------------------------ 10: concurrency
+def test_two_contexts_search_one_index():
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "shared_mm"], cwd=ROOT, capture_output=True, text=True,
+                       timeout=300)
+    tail = (p.stdout or "")[-3000:] + (p.stderr or "")[-3000:]
+    assert p.returncode == 0 and "ok shared_mm" in p.stdout, tail
+
+
+def _child_shared_mm():
+    """two contexts in two threads search one sampled index at once, each with a small batch of its own"""
+    import textcomp
+    from textcomp import FMIndexHandle
+    n = 1 << 16
+    tb = _text(0x3D00, n, b"ACGT")
+    batches = [_patterns(0x3D01 + b, tb, b"ACGT", lengths=(8, 17, 32)) for b in range(2)]
+    owner = textcomp.Context(0)
+    fm = owner.fm_build(tb, sa_rate=4)
+    ctxs = [textcomp.Context(0), textcomp.Context(0)]
+    serial = [(fm.count_mm(b, 2), _locate_flat(fm, b, 2)) for b in batches]
+    for b, (cnt, (ho, h, mm)) in zip(batches, serial):
+        _check_against_reference(tb, b, 2, cnt, ho, h, mm)
+    errs, start = [], threading.Barrier(2)
+
+    def work(i):
+        try:
+            view = FMIndexHandle(ctxs[i], None, _handle=fm._h, _n=n)   # the owner's index, queried by this context
+            try:
+                start.wait()
+                cnt = view.count_mm(batches[i], 2)
+                got = _locate_flat(view, batches[i], 2)
+                dev = _locate_flat_dev(view, batches[i], 2)
+                assert np.array_equal(cnt, serial[i][0])
+                for a, b, c in zip(got, dev, serial[i][1]):
+                    assert np.array_equal(a, c) and np.array_equal(b, c)
+            finally:
+                view._h = None                                          # not ours to free
+        except Exception:
+            errs.append(traceback.format_exc())
+
+    th = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    for t in th: t.start()
+    for t in th: t.join()
+    assert not errs, "\n".join(errs)
+    for c in ctxs: c.close()
+    fm.close(); owner.close()
+    print("ok shared_mm")
+
+
+if __name__ == "__main__":
+    {"shared_mm": _child_shared_mm}[sys.argv[1]]()

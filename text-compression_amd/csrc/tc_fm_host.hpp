@@ -597,6 +597,8 @@ __global__ __launch_bounds__(256) void fm_extract_walk_kernel(const u64 *__restr
     }
 }
 
+#include "tc_fm_mm.hpp"   // fm_mm_kernel: count / locate within Hamming distance k
+
 #endif  // __HIPCC__
 
 // code of byte / C[code] / count[code] from the byte histogram; returns the number of present byte values
@@ -750,5 +752,24 @@ static void fm_count_device(tc_ctx *ctx, const tc_fm *fm, const u8 *d_pats, cons
         fm_count_kernel<false><<<tc_cdiv(npat, 256), 256, 0, ctx->stream>>>(fm->d_bits, nullptr, fm->lines, fm->d_tab,
                                                                             nullptr, fm->sigma_bytes, d_pats, d_offs,
                                                                             npat, d_out, d_ranges);
+    TC_LAUNCH_CHECK(ctx);
+}
+
+// fm_mm_kernel over a batch.  d_hoffs = null: the count pass (d_out[p] = hits of pattern p within distance k).  Otherwise the
+// fill pass: the same enumeration writes pattern p's hits to d_hits[d_hoffs[p] .. d_hoffs[p + 1]) -- positions on a full
+// index, rows on a sampled one -- and their distances to d_mm (may be null).
+static void fm_mm_device(tc_ctx *ctx, const tc_fm *fm, const u8 *d_pats, const u64 *d_offs, u64 npat, u32 k, i64 *d_out,
+                         const u64 *d_hoffs, u64 *d_hits, u8 *d_mm) {
+    const u32 grid = tc_cdiv(npat, 256);
+    hipStream_t s = ctx->stream;
+#define FM_MM_LAUNCH(P, F)                                                                                                  \
+    fm_mm_kernel<P, F><<<grid, 256, 0, s>>>(fm->d_bits, fm->d_bits2, fm->lines, fm->d_tab, fm->d_tab2, fm->sigma_bytes,      \
+                                            (u32)fm->N, k, d_pats, d_offs, npat, d_out, d_hoffs, fm->d_sa, d_hits, d_mm)
+    if (d_hoffs) {
+        if (fm->d_bits2) FM_MM_LAUNCH(true, true); else FM_MM_LAUNCH(false, true);
+    } else {
+        if (fm->d_bits2) FM_MM_LAUNCH(true, false); else FM_MM_LAUNCH(false, false);
+    }
+#undef FM_MM_LAUNCH
     TC_LAUNCH_CHECK(ctx);
 }

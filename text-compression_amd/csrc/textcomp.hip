@@ -1929,6 +1929,161 @@ int tc_fm_locate_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const 
     TC_API_END(ctx)
 }
 
+// ---- search with mismatches (tc_fm_count_mm / tc_fm_locate_mm; the kernel: tc_fm_mm.hpp) ---------------------------------
+static_assert(TC_FM_MAX_MISMATCH == FM_MM_MAXK, "fm_mm_kernel keeps TC_FM_MAX_MISMATCH frames per lane");
+
+int tc_fm_count_mm_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint32_t k,
+                       int64_t *d_out) {
+    TC_API_BEGIN(ctx)
+    if (!fm) TC_FAIL(ctx, TC_ERR_ARG, "null index");
+    if (k > TC_FM_MAX_MISMATCH) TC_FAIL(ctx, TC_ERR_ARG, "k = %u mismatches (at most %d)", k, TC_FM_MAX_MISMATCH);
+    if (npat == 0) return TC_OK;
+    if (!d_pats || !d_offs || !d_out) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (fm->n == 0) {
+        tc_memset_async(ctx, d_out, 0, npat * sizeof(i64));
+    } else {
+        fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, d_out, nullptr, nullptr, nullptr);
+    }
+    tc_sync_check(ctx);
+    TC_API_END(ctx)
+}
+
+int tc_fm_count_mm(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat, uint32_t k,
+                   int64_t *out) {
+    TC_API_BEGIN(ctx)
+    if (!fm) TC_FAIL(ctx, TC_ERR_ARG, "null index");
+    if (k > TC_FM_MAX_MISMATCH) TC_FAIL(ctx, TC_ERR_ARG, "k = %u mismatches (at most %d)", k, TC_FM_MAX_MISMATCH);
+    if (npat == 0) return TC_OK;
+    if (!pats || !offs || !out) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (fm->n == 0) {
+        memset(out, 0, npat * sizeof(i64));
+        return TC_OK;
+    }
+    const u64 total = offs[npat];
+    u8 *d_pats = nullptr;
+    u64 *d_offs = nullptr;
+    i64 *d_out = nullptr;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+        d_pats = A.get<u8>(total + 16);
+        d_offs = A.get<u64>(npat + 1);
+        d_out = A.get<i64>(npat);
+    });
+    tc_h2d(ctx, d_pats, pats, total);
+    tc_h2d(ctx, d_offs, offs, (npat + 1) * sizeof(u64));
+    fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, d_out, nullptr, nullptr, nullptr);
+    tc_d2h(ctx, out, d_out, npat * sizeof(i64));
+    tc_sync_check(ctx);
+    TC_API_END(ctx)
+}
+
+// scratch of one locate-with-mismatches batch besides patterns and results
+struct FmMmScratch {
+    i64 *d_cnt = nullptr;
+    u64 *d_len = nullptr, *d_tsum = nullptr;
+    u64 tiles = 0;
+    void carve(Arena &A, u64 npat) {
+        tiles = tc_cdiv(npat, SCAN_TILE);
+        d_cnt = A.get<i64>(npat);
+        d_len = A.get<u64>(npat + 1);
+        d_tsum = A.get<u64>(tiles + 2);
+    }
+};
+
+// fm_locate_device for the search with mismatches: the count pass, the scan of the counts (d_hoffs[0 .. npat]; the total is
+// returned), then -- when the total fits -- the fill pass, which repeats the enumeration and writes positions (a full index)
+// or rows that the walk then turns into positions (a sampled one), and the distances to d_mm (may be null).  When the total
+// exceeds cap nothing is written to d_hits or d_mm.  The caller synchronises (tc_sync_check).
+static u64 fm_locate_mm_device(tc_ctx *ctx, const tc_fm *fm, const FmMmScratch &W, const u8 *d_pats, const u64 *d_offs,
+                               u64 npat, u32 k, u64 *d_hoffs, u64 *d_hits, u8 *d_mm, u64 cap) {
+    hipStream_t s = ctx->stream;
+    const u64 tiles = W.tiles;
+    fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, W.d_cnt, nullptr, nullptr, nullptr);
+    fm_cnt_to_u64_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(W.d_cnt, npat, W.d_len);
+    TC_LAUNCH_CHECK(ctx);
+    scan64_reduce_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(W.d_len, npat, W.d_tsum);
+    TC_LAUNCH_CHECK(ctx);
+    scan64_spine_kernel<<<1, 1024, 0, s>>>(W.d_tsum, tiles);
+    TC_LAUNCH_CHECK(ctx);
+    scan64_down_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(W.d_len, npat, W.d_tsum, d_hoffs);
+    TC_LAUNCH_CHECK(ctx);
+    TC_HIP(ctx, hipMemcpyAsync(d_hoffs + npat, W.d_tsum + tiles, sizeof(u64), hipMemcpyDeviceToDevice, s));
+    tc_d2h(ctx, &ctx->h_scalars[9], W.d_tsum + tiles, sizeof(u64));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    const u64 need = ctx->h_scalars[9];
+    if (need > cap || need == 0) return need;
+    fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, nullptr, d_hoffs, d_hits, d_mm);
+    if (fm->sa_rate > 1) {
+        fm_locate_walk_kernel<<<tc_cdiv(need, 256), 256, 0, s>>>(fm->d_bits, fm->d_marks, fm->lines, fm->d_tab, fm->sigma_bytes,
+                                                                fm->d_L, fm->d_samples, fm->nsamples, fm->N, fm->primary,
+                                                                fm->sa_rate, need, d_hits, ctx->d_err);
+        TC_LAUNCH_CHECK(ctx);
+    }
+    return need;
+}
+
+int tc_fm_locate_mm(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat, uint32_t k,
+                    uint64_t *hit_offs, uint64_t *hits, uint8_t *hit_mm, uint64_t *nhits) {
+    TC_API_BEGIN(ctx)
+    if (!fm || !nhits) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const u64 cap = *nhits;
+    *nhits = 0;
+    if (k > TC_FM_MAX_MISMATCH) TC_FAIL(ctx, TC_ERR_ARG, "k = %u mismatches (at most %d)", k, TC_FM_MAX_MISMATCH);
+    if (npat == 0) return TC_OK;
+    if (!pats || !offs || !hit_offs || (!hits && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (fm->n == 0) {
+        memset(hit_offs, 0, (npat + 1) * sizeof(u64));
+        return TC_OK;
+    }
+    if (!fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
+    const u64 total = offs[npat];
+    u8 *d_pats = nullptr, *d_mm = nullptr;
+    u64 *d_offs = nullptr, *d_hoffs = nullptr, *d_hits = nullptr;
+    FmMmScratch W;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+        d_pats = A.get<u8>(total + 16);
+        d_offs = A.get<u64>(npat + 1);
+        W.carve(A, npat);
+        d_hoffs = A.get<u64>(npat + 1);
+        d_hits = A.get<u64>(cap + 1);
+        d_mm = hit_mm ? A.get<u8>(cap + 16) : nullptr;
+    });
+    tc_h2d(ctx, d_pats, pats, total);
+    tc_h2d(ctx, d_offs, offs, (npat + 1) * sizeof(u64));
+    const u64 need = fm_locate_mm_device(ctx, fm, W, d_pats, d_offs, npat, k, d_hoffs, d_hits, d_mm, cap);
+    *nhits = need;
+    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu hit slots, have %llu",
+                            (unsigned long long)need, (unsigned long long)cap);
+    tc_d2h(ctx, hit_offs, d_hoffs, (npat + 1) * sizeof(u64));
+    if (need) tc_d2h(ctx, hits, d_hits, need * sizeof(u64));
+    if (need && hit_mm) tc_d2h(ctx, hit_mm, d_mm, need);
+    tc_sync_check(ctx);
+    TC_API_END(ctx)
+}
+
+int tc_fm_locate_mm_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint32_t k,
+                        uint64_t *d_hit_offs, uint64_t *d_hits, uint8_t *d_hit_mm, uint64_t *nhits) {
+    TC_API_BEGIN(ctx)
+    if (!fm || !nhits) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const u64 cap = *nhits;
+    *nhits = 0;
+    if (k > TC_FM_MAX_MISMATCH) TC_FAIL(ctx, TC_ERR_ARG, "k = %u mismatches (at most %d)", k, TC_FM_MAX_MISMATCH);
+    if (npat == 0) return TC_OK;
+    if (!d_pats || !d_offs || !d_hit_offs || (!d_hits && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (fm->n == 0) {
+        tc_memset_async(ctx, d_hit_offs, 0, (npat + 1) * sizeof(u64));
+        tc_sync_check(ctx);
+        return TC_OK;
+    }
+    if (!fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
+    FmMmScratch W;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) { W.carve(A, npat); });
+    const u64 need = fm_locate_mm_device(ctx, fm, W, d_pats, d_offs, npat, k, d_hit_offs, d_hits, d_hit_mm, cap);
+    *nhits = need;
+    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu hit slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
+    tc_sync_check(ctx);
+    TC_API_END(ctx)
+}
+
 // scratch of one extract batch besides queries and results
 struct FmExtractScratch {
     u64 *d_len = nullptr, *d_segs = nullptr, *d_soffs = nullptr, *d_tsum_b = nullptr, *d_tsum_s = nullptr;

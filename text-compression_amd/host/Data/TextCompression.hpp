@@ -210,6 +210,75 @@ inline CountResult bytestringFMIndexCountP(const std::vector<std::string> &pats,
     return bytestringFMIndexCountS(pats, input);
 }
 
+// Not in the reference: search with mismatches -- the text positions within Hamming distance k of each pattern
+// (substitutions only, k at most TC_FM_MAX_MISMATCH; a pattern byte that does not occur in the text can only be a
+// mismatch; textcomp.h).  The value shapes of the count / locate mirrors: Nothing for no hit.
+namespace detail {
+inline std::string packPatterns(const std::vector<std::string> &pats, std::vector<uint64_t> &offs) {
+    std::string flat;
+    offs.assign(1, 0);
+    for (auto &p : pats) {
+        flat += p;
+        offs.push_back(flat.size());
+    }
+    flat.push_back('\0');
+    return flat;
+}
+}  // namespace detail
+inline CountResult bytestringFMIndexCountMismatchS(const std::vector<std::string> &pats, const std::string &input, uint32_t k) {
+    CountResult out;
+    if (pats.empty() || input.empty()) return out;
+    tc_fm *fm = nullptr;
+    Context::check(tc_fm_build(Context::get(), (const uint8_t *)input.data(), input.size(), &fm));
+    std::vector<uint64_t> offs;
+    const std::string flat = detail::packPatterns(pats, offs);
+    std::vector<int64_t> counts(pats.size());
+    int rc = tc_fm_count_mm(Context::get(), fm, (const uint8_t *)flat.data(), offs.data(), pats.size(), k, counts.data());
+    tc_fm_free(fm);
+    Context::check(rc);
+    for (size_t i = 0; i < pats.size(); i++)
+        out.emplace_back(pats[i], counts[i] ? std::optional<int64_t>(counts[i]) : std::nullopt);
+    return out;
+}
+inline CountResult bytestringFMIndexCountMismatchP(const std::vector<std::string> &pats, const std::string &input, uint32_t k) {
+    return bytestringFMIndexCountMismatchS(pats, input, k);
+}
+// per pattern: (1-based position, mismatches) of every hit, each once, in the device's enumeration order (deterministic, not
+// sorted)
+using LocateMismatchResult = std::vector<std::pair<std::string, std::vector<std::pair<uint64_t, uint8_t>>>>;
+inline LocateMismatchResult bytestringFMIndexLocateMismatchS(const std::vector<std::string> &pats, const std::string &input,
+                                                             uint32_t k) {
+    LocateMismatchResult out;
+    if (pats.empty() || input.empty()) return out;
+    tc_fm *fm = nullptr;
+    Context::check(tc_fm_build(Context::get(), (const uint8_t *)input.data(), input.size(), &fm));
+    std::vector<uint64_t> offs;
+    const std::string flat = detail::packPatterns(pats, offs);
+    std::vector<uint64_t> hoffs(pats.size() + 1), hits(16 * pats.size());
+    std::vector<uint8_t> mm(hits.size());
+    uint64_t nh = hits.size();
+    int rc = tc_fm_locate_mm(Context::get(), fm, (const uint8_t *)flat.data(), offs.data(), pats.size(), k, hoffs.data(),
+                             hits.data(), mm.data(), &nh);
+    if (rc == TC_ERR_CAPACITY) {            // *nhits = the hits needed: once more with room for them
+        hits.resize(nh);
+        mm.resize(nh);
+        rc = tc_fm_locate_mm(Context::get(), fm, (const uint8_t *)flat.data(), offs.data(), pats.size(), k, hoffs.data(),
+                             hits.data(), mm.data(), &nh);
+    }
+    tc_fm_free(fm);
+    Context::check(rc);
+    for (size_t i = 0; i < pats.size(); i++) {
+        std::vector<std::pair<uint64_t, uint8_t>> h;
+        for (uint64_t t = hoffs[i]; t < hoffs[i + 1]; t++) h.emplace_back(hits[t], mm[t]);
+        out.emplace_back(pats[i], std::move(h));
+    }
+    return out;
+}
+inline LocateMismatchResult bytestringFMIndexLocateMismatchP(const std::vector<std::string> &pats, const std::string &input,
+                                                             uint32_t k) {
+    return bytestringFMIndexLocateMismatchS(pats, input, k);
+}
+
 // Not in the reference: an index that is kept between queries, optionally with a sampled suffix array (sa_rate > 1: every
 // sa_rate-th entry is kept and locate walks the LF mapping to the next one; textcomp.h), queried with everything in HBM.
 class Index {

@@ -66,6 +66,16 @@ foreign import ccall safe "tc_fm_extract"
   c_tc_fm_extract :: Ptr TcCtx -> Ptr TcFm -> Ptr Word64 -> Ptr Word64 -> Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
 foreign import ccall safe "tc_fm_extract_dev"
   c_tc_fm_extract_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word64 -> Ptr Word64 -> Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
+-- search with mismatches: count / locate within Hamming distance k (substitutions only, k at most 3; no counterpart in
+-- the reference).  locate also answers each hit's distance (Ptr Word8, may be nullPtr)
+foreign import ccall safe "tc_fm_count_mm"
+  c_tc_fm_count_mm :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Word32 -> Ptr Int64 -> IO Int32
+foreign import ccall safe "tc_fm_count_mm_dev"
+  c_tc_fm_count_mm_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Word32 -> Ptr Int64 -> IO Int32
+foreign import ccall safe "tc_fm_locate_mm"
+  c_tc_fm_locate_mm :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Word32 -> Ptr Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
+foreign import ccall safe "tc_fm_locate_mm_dev"
+  c_tc_fm_locate_mm_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Word32 -> Ptr Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
 -- stored / shipped form (no counterpart in the reference): one record, or any length cut into records
 foreign import ccall unsafe "tc_container_bound"
   c_tc_container_bound :: Word64 -> Word32 -> Word64

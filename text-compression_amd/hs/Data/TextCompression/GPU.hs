@@ -15,6 +15,8 @@ module Data.TextCompression.GPU
   , bytestringToBWTToFMIndexB
   , bytestringFMIndexCountS, bytestringFMIndexCountP
   , bytestringFMIndexLocateS, bytestringFMIndexLocateP
+  , bytestringFMIndexCountMismatchS, bytestringFMIndexCountMismatchP
+  , bytestringFMIndexLocateMismatchS, bytestringFMIndexLocateMismatchP
   ) where
 
 import Control.Concurrent.MVar (MVar, newMVar, modifyMVar_, withMVar)
@@ -264,3 +266,66 @@ bytestringFMIndexLocateP pats input = pure (bytestringFMIndexLocateS pats input)
 -- | FMIndex.hs:411-432: the parListChunk spark pool is the one batched launch above
 bytestringFMIndexCountP :: [BS.ByteString] -> BS.ByteString -> IO (Seq (BS.ByteString, Maybe Int))
 bytestringFMIndexCountP pats input = pure (bytestringFMIndexCountS pats input)
+
+-- | Not in the reference: the text positions within Hamming distance k of each pattern (substitutions only, k at most 3;
+-- a pattern byte that does not occur in the text can only be a mismatch).  One batched device call: tc_fm_count_mm;
+-- 0 stands for Nothing; order preserved
+bytestringFMIndexCountMismatchS :: Int -> [BS.ByteString] -> BS.ByteString -> Seq (BS.ByteString, Maybe Int)
+bytestringFMIndexCountMismatchS k pats input
+  | null pats || BS.null input = DS.Empty
+  | otherwise = unsafePerformIO $ withCtx $ \ctx ->
+      BSU.unsafeUseAsCStringLen input $ \(p, n) -> alloca $ \ph -> do
+        c_tc_fm_build ctx (castPtr p) (fromIntegral n) ph >>= check ctx
+        fm <- peek ph
+        let flat = BS.concat pats `BS.snoc` 0
+            offs = scanl (+) 0 (map (fromIntegral . BS.length) pats)
+        r <- BSU.unsafeUseAsCString flat $ \fp -> withArray offs $ \op ->
+               allocaArray (length pats) $ \out -> do
+                 rc <- c_tc_fm_count_mm ctx fm (castPtr fp) op (fromIntegral (length pats)) (fromIntegral k) out
+                 c_tc_fm_free fm
+                 check ctx rc
+                 peekArray (length pats) out
+        pure . DS.fromList $ [ (q, if c == 0 then Nothing else Just (fromIntegral c)) | (q, c) <- zip pats r ]
+
+bytestringFMIndexCountMismatchP :: Int -> [BS.ByteString] -> BS.ByteString -> IO (Seq (BS.ByteString, Maybe Int))
+bytestringFMIndexCountMismatchP k pats input = pure (bytestringFMIndexCountMismatchS k pats input)
+
+-- | Not in the reference: (1-based position, mismatches) of every hit within Hamming distance k, each once, in the device's
+-- enumeration order (deterministic, not sorted).  One batched device call: tc_fm_locate_mm, as bytestringFMIndexLocateS
+-- calls tc_fm_locate (a first call sizes the buffers).
+bytestringFMIndexLocateMismatchS :: Int -> [BS.ByteString] -> BS.ByteString -> Seq (BS.ByteString, Seq (Int, Int))
+bytestringFMIndexLocateMismatchS k pats input
+  | null pats || BS.null input = DS.Empty
+  | otherwise = unsafePerformIO $ withCtx $ \ctx ->
+      BSU.unsafeUseAsCStringLen input $ \(p, n) -> alloca $ \ph -> do
+        c_tc_fm_build ctx (castPtr p) (fromIntegral n) ph >>= check ctx
+        fm <- peek ph
+        let np   = length pats
+            flat = BS.concat pats `BS.snoc` 0
+            offs = scanl (+) 0 (map (fromIntegral . BS.length) pats)
+            attempt :: Int -> IO (Either Int ([Int], [(Int, Int)]))
+            attempt cap =
+              BSU.unsafeUseAsCString flat $ \fp -> withArray offs $ \op ->
+              allocaArray (np + 1) $ \ho -> allocaArray (max 1 cap) $ \hits -> allocaArray (max 1 cap) $ \mm ->
+              with (fromIntegral cap) $ \nh -> do
+                rc <- c_tc_fm_locate_mm ctx fm (castPtr fp) op (fromIntegral np) (fromIntegral k) ho hits mm nh
+                total <- fromIntegral <$> peek nh
+                if rc == (-2)                                   -- TC_ERR_CAPACITY: *nhits = hits needed
+                  then pure (Left total)
+                  else do
+                    when (rc /= 0) (c_tc_fm_free fm)
+                    check ctx rc
+                    os <- map fromIntegral <$> peekArray (np + 1) ho
+                    hs <- map fromIntegral <$> peekArray total hits
+                    ds <- map fromIntegral <$> peekArray total mm
+                    pure (Right (os, zip hs ds))
+        r1 <- attempt (16 * np)
+        (os, hs) <- case r1 of
+          Right v   -> pure v
+          Left need -> attempt need >>= either (\_ -> c_tc_fm_free fm >> ioError (userError "tc_fm_locate_mm: capacity")) pure
+        c_tc_fm_free fm
+        let slices = [ take (e - a) (drop a hs) | (a, e) <- zip os (tail os) ]
+        pure . DS.fromList $ [ (q, DS.fromList h) | (q, h) <- zip pats slices ]
+
+bytestringFMIndexLocateMismatchP :: Int -> [BS.ByteString] -> BS.ByteString -> IO (Seq (BS.ByteString, Seq (Int, Int)))
+bytestringFMIndexLocateMismatchP k pats input = pure (bytestringFMIndexLocateMismatchS k pats input)

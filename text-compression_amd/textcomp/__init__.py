@@ -497,6 +497,40 @@ class FMIndexHandle:
                                                C.c_void_p(d_offs.data_ptr()), npat, C.c_void_p(out.data_ptr())))
         return out
 
+    def count_mm_dev(self, d_pats, d_offs, npat, k):
+        """count_dev within Hamming distance k (0 .. TC_FM_MAX_MISMATCH; substitutions only) -> int64 tensor:
+        tc_fm_count_mm_dev"""
+        import torch
+        ctx = self._ctx
+        out = torch.zeros(max(npat, 1), dtype=torch.int64, device=d_pats.device)[:npat]
+        torch.cuda.synchronize()
+        ctx._check(ctx.lib.tc_fm_count_mm_dev(ctx.handle, self._h, C.c_void_p(d_pats.data_ptr()), C.c_void_p(d_offs.data_ptr()),
+                                              npat, int(k), C.c_void_p(out.data_ptr())))
+        return out
+
+    def locate_mm_dev(self, d_pats, d_offs, npat, k, cap=None):
+        """locate_dev within Hamming distance k -> (hit_offs int64 tensor [npat + 1], hits int64 tensor [total], 1-based
+        positions in the kernel's enumeration order, mismatches uint8 tensor [total]), all on the device:
+        tc_fm_locate_mm_dev"""
+        import torch
+        ctx = self._ctx
+        dev = d_pats.device
+        hoffs = torch.zeros(npat + 1, dtype=torch.int64, device=dev)
+        cap = max(int(cap) if cap is not None else 2 * npat, 1)
+        for _ in range(2):
+            hits = torch.empty(cap, dtype=torch.int64, device=dev)
+            mm = torch.empty(cap, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            nh = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_locate_mm_dev(ctx.handle, self._h, C.c_void_p(d_pats.data_ptr()), C.c_void_p(d_offs.data_ptr()),
+                                             npat, int(k), C.c_void_p(hoffs.data_ptr()), C.c_void_p(hits.data_ptr()),
+                                             C.c_void_p(mm.data_ptr()), C.byref(nh))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nh.value), 1)
+        ctx._check(rc)
+        return hoffs, hits[:int(nh.value)], mm[:int(nh.value)]
+
     def close(self):
         if getattr(self, "_h", None):
             self._ctx.lib.tc_fm_free(self._h)
@@ -545,6 +579,37 @@ class FMIndexHandle:
             ctx._check(rc)
             break
         return [hits[int(hoffs[i]):int(hoffs[i + 1])].copy() for i in range(len(pats))]
+
+    def count_mm(self, pats, k):
+        """-> int64[npat]: the text positions within Hamming distance k (0 .. TC_FM_MAX_MISMATCH; substitutions only) of
+        each pattern.  A pattern byte that does not occur in the text can only be a mismatch (unlike count, which stops
+        at it): tc_fm_count_mm"""
+        ctx = self._ctx
+        flat, offs = self._pack(pats)
+        out = np.empty(len(pats), np.int64)
+        ctx._check(ctx.lib.tc_fm_count_mm(ctx.handle, self._h, _ptr(flat), _ptr(offs), len(pats), int(k), _ptr(out)))
+        return out
+
+    def locate_mm(self, pats, k):
+        """-> list of (positions uint64 array, mismatches uint8 array) pairs, one per pattern: 1-based positions within
+        Hamming distance k, each once, in the kernel's enumeration order (deterministic, not sorted): tc_fm_locate_mm"""
+        ctx = self._ctx
+        flat, offs = self._pack(pats)
+        hoffs = np.zeros(len(pats) + 1, np.uint64)
+        cap = 1 << 16
+        while True:
+            hits = np.empty(cap, np.uint64)
+            mm = np.empty(cap, np.uint8)
+            nh = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_locate_mm(ctx.handle, self._h, _ptr(flat), _ptr(offs), len(pats), int(k),
+                                         _ptr(hoffs), _ptr(hits), _ptr(mm), C.byref(nh))
+            if rc == _lib.TC_ERR_CAPACITY and int(nh.value) > cap:
+                cap = int(nh.value)
+                continue
+            ctx._check(rc)
+            break
+        return [(hits[int(hoffs[i]):int(hoffs[i + 1])].copy(), mm[int(hoffs[i]):int(hoffs[i + 1])].copy())
+                for i in range(len(pats))]
 
     def info(self):
         ctx = self._ctx

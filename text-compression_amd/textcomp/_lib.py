@@ -15,6 +15,7 @@ TC_MAX_SIGMA = 257
 TC_MAX_ROUNDS = 40
 TC_CODING_PACKED, TC_CODING_HUFFMAN = 0, 1
 TC_FM_MAX_SA_RATE = 4096
+TC_FM_MAX_MISMATCH = 3
 
 ERR_NAMES = {-1: "TC_ERR_ARG", -2: "TC_ERR_CAPACITY", -3: "TC_ERR_MALFORMED", -4: "TC_ERR_HIP",
              -5: "TC_ERR_OOM", -6: "TC_ERR_INTERNAL", -7: "TC_ERR_NCCL"}
@@ -112,6 +113,10 @@ SYMBOLS = [
     ("tc_fm_locate_dev", _INT, [_P, _P, _P, _P, _U64, _P, _P, _PU64]),
     ("tc_fm_extract", _INT, [_P, _P, _P, _P, _U64, _P, _P, _PU64]),
     ("tc_fm_extract_dev", _INT, [_P, _P, _P, _P, _U64, _P, _P, _PU64]),
+    ("tc_fm_count_mm", _INT, [_P, _P, _P, _P, _U64, _U32, _P]),
+    ("tc_fm_count_mm_dev", _INT, [_P, _P, _P, _P, _U64, _U32, _P]),
+    ("tc_fm_locate_mm", _INT, [_P, _P, _P, _P, _U64, _U32, _P, _P, _P, _PU64]),
+    ("tc_fm_locate_mm_dev", _INT, [_P, _P, _P, _P, _U64, _U32, _P, _P, _P, _PU64]),
     ("tc_fm_info", _INT, [_P, _PU64, _PU32, _P, _P, _PU64]),
     ("tc_comm_unique_id", _INT, [_P, _P]),
     ("tc_comm_create", _INT, [_P, _P, _INT, _INT, C.POINTER(_P)]),

@@ -39,6 +39,43 @@ def bytestringFMIndexLocateP(pats, text, ctx=None):
     return bytestringFMIndexLocateS(pats, text, ctx)
 
 
+# ---- search with mismatches (no counterpart in the reference; the value shapes of the count / locate mirrors above) ----
+def bytestringFMIndexCountMismatchS(pats, text, k, ctx=None):
+    """[(pattern, Maybe Int)]: the text positions within Hamming distance k of each pattern (substitutions only, k at
+    most TC_FM_MAX_MISMATCH), Nothing for none.  A pattern byte that does not occur in the text can only be a
+    mismatch.  Empty pattern list or empty input => empty result."""
+    if len(pats) == 0 or len(text) == 0:
+        return []
+    fm = (ctx or default_context()).fm_build(text)
+    try:
+        counts = fm.count_mm(pats, k)
+    finally:
+        fm.close()
+    return [(p, None if c == 0 else int(c)) for p, c in zip(pats, counts)]
+
+
+def bytestringFMIndexCountMismatchP(pats, text, k, ctx=None):
+    """the same values in the same order: the batch is one launch either way"""
+    return bytestringFMIndexCountMismatchS(pats, text, k, ctx)
+
+
+def bytestringFMIndexLocateMismatchS(pats, text, k, ctx=None):
+    """[(pattern, [(position, mismatches)])]: 1-based positions within Hamming distance k, each once, in the device's
+    enumeration order (deterministic, not sorted)."""
+    if len(pats) == 0 or len(text) == 0:
+        return []
+    fm = (ctx or default_context()).fm_build(text)
+    try:
+        hits = fm.locate_mm(pats, k)
+    finally:
+        fm.close()
+    return [(p, [(int(v), int(d)) for v, d in zip(h, mm)]) for p, (h, mm) in zip(pats, hits)]
+
+
+def bytestringFMIndexLocateMismatchP(pats, text, k, ctx=None):
+    return bytestringFMIndexLocateMismatchS(pats, text, k, ctx)
+
+
 # ---- Text instantiations (FMIndex.hs:385-403,436-462,503-530,570-599) ----------------------------
 # The index is built over the UTF-8 bytes, each turned into a Text by decodeUtf8 . BS.singleton
 # (ASCII only, an exception otherwise); patterns are split into characters.  For ASCII input that is
@@ -127,3 +164,27 @@ def bytestringFromBWTFromFMIndexB(fmi, ctx=None):
     if len(cc) == 0 or len(occck) == 0 or len(sa) == 0:
         return b""
     return _bwt.bytestringFromByteStringBWT([x for _, _, x in occck[0][1]], ctx)
+
+
+def textFMIndexCountMismatchS(pats, text, k, ctx=None):
+    """bytestringFMIndexCountMismatchS over the UTF-8 bytes (ASCII only, as the other text... variants)."""
+    if len(pats) == 0 or len(text) == 0:
+        return []
+    res = bytestringFMIndexCountMismatchS([p.encode("utf-8") for p in pats], _ascii_bytes(text), k, ctx)
+    return [(p, c) for p, (_, c) in zip(pats, res)]
+
+
+def textFMIndexCountMismatchP(pats, text, k, ctx=None):
+    return textFMIndexCountMismatchS(pats, text, k, ctx)
+
+
+def textFMIndexLocateMismatchS(pats, text, k, ctx=None):
+    """bytestringFMIndexLocateMismatchS over the UTF-8 bytes (ASCII only)."""
+    if len(pats) == 0 or len(text) == 0:
+        return []
+    res = bytestringFMIndexLocateMismatchS([p.encode("utf-8") for p in pats], _ascii_bytes(text), k, ctx)
+    return [(p, h) for p, (_, h) in zip(pats, res)]
+
+
+def textFMIndexLocateMismatchP(pats, text, k, ctx=None):
+    return textFMIndexLocateMismatchS(pats, text, k, ctx)
