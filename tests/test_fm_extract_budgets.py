@@ -2,13 +2,7 @@
 no GPU), in the manner of tests/test_fm_sampled_budgets.py.  The extract walk is, like the locate walk, a chain of
 dependent random reads per lane (the last-column byte, then one 64-byte rank line): what hides their latency is the
 number of waves a SIMD holds, so the kernel must stay at 8 waves per SIMD (at most 64 VGPRs) and must not spill."""
-import os
-import re
-import subprocess
-import tempfile
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "text-compression_amd")
+import kernel_resources
 
 # mangled-name fragment -> (max VGPRs, max scratch bytes per lane, min waves per SIMD)
 BUDGETS = {
@@ -22,22 +16,11 @@ BUDGETS = {
 
 
 def test_extract_kernel_budgets():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    with tempfile.TemporaryDirectory() as d:
-        out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread",
-                              "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"),
-                              "-Rpass-analysis=kernel-resource-usage", "-o", os.path.join(d, "libtextcomp_budget.so"),
-                              os.path.join(PKG, "csrc", "textcomp.hip")], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
     seen = {}
-    for blk in out.stderr.split("Function Name: ")[1:]:
-        name = blk.split()[0]
-        v = int(re.search(r"VGPRs: (\d+)", blk).group(1))
-        s = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", blk).group(1))
-        o = int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", blk).group(1))
+    for name, vso in kernel_resources.resources().items():
         for frag in BUDGETS:
             if frag in name:
-                seen[frag] = (v, s, o)
+                seen[frag] = vso
     for frag, (mv, ms, mo) in BUDGETS.items():
         assert frag in seen, "kernel not found: " + frag
         v, s, o = seen[frag]

@@ -269,7 +269,7 @@ def test_errors(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ 7
-# the export's layout (csrc/textcomp.hip, FmWire): a 1600-byte header padded to 256, then every part padded to 256
+# the export's layout (csrc/tc_fm_host.hpp, FmWire): a 1600-byte header padded to 256, then every part padded to 256
 _HDR = 1792
 _OFF_N, _OFF_PRIMARY, _OFF_LINES, _OFF_BYTES, _OFF_SIGMA, _OFF_WITH_LOCATE, _OFF_PAIRS, _OFF_RATE = 8, 24, 32, 40, 48, 52, 56, 60
 

@@ -379,6 +379,118 @@ def test_errors_and_edges(ctx):
         empty.close()
 
 
+# ------------------------------------------------------------------------------------------------ 9b: the shared locate pipeline
+# The exact search and the search with mismatches are one pipeline on the device (count pass, scan of the counts in tiles of
+# 2048 patterns, fill pass, walk): both are held to the same protocol here, through the host and the _dev entry, on a text of
+# 449 symbols (one row past a 448-bit line of the rank vectors) with and without pair vectors, full and sampled, for a batch
+# of one pattern and one of 2049 (one pattern past a tile of the scan).
+EDGE_TEXTS = {"acgt": b"ACGT", "six": b"\x00ab\x7f\x80\xff"}
+EDGE_TC_OK = 0
+
+
+@pytest.fixture(scope="module")
+def edge_indexes(ctx):
+    """{(alphabet, sa_rate): (text, index)}"""
+    made = {}
+    for i, (name, alphabet) in enumerate(sorted(EDGE_TEXTS.items())):
+        tb = _text(0x9B00 + i, 449, alphabet)
+        for rate in (1, 4):
+            made[name, rate] = (tb, ctx.fm_build(tb, sa_rate=rate))
+    yield made
+    for _, fm in made.values():
+        fm.close()
+
+
+def _raw_locate_any(ctx, fm, pats, k, cap, dev, null_hits=False, fill=0xAB):
+    """one locate call -- k None: the exact search; dev: the _dev entry -- with every output prefilled
+    -> (rc, nhits, hit_offs, hits, hit_mm) as numpy arrays"""
+    import torch
+    from textcomp import FMIndexHandle
+    npat = len(pats)
+    flat, offs = FMIndexHandle._pack(pats)
+    hoffs = np.full(npat + 1, fill * 0x0101010101010101, np.uint64)
+    hits = np.full(cap + 8, fill * 0x0101010101010101, np.uint64)
+    mm = np.full(cap + 8, fill, np.uint8)
+    host = [flat, offs, hoffs, hits, mm]
+    if dev:
+        bufs = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).cuda() for a in host]
+        torch.cuda.synchronize()
+        ptr = [C.c_void_p(t.data_ptr()) for t in bufs]
+    else:
+        ptr = [a.ctypes.data_as(C.c_void_p) for a in host]
+    if null_hits:
+        ptr[3] = ptr[4] = None
+    nh = C.c_uint64(cap)
+    lib, sfx = ctx.lib, "_dev" if dev else ""
+    if k is None:
+        rc = getattr(lib, "tc_fm_locate" + sfx)(ctx.handle, fm._h, ptr[0], ptr[1], npat, ptr[2], ptr[3], C.byref(nh))
+    else:
+        rc = getattr(lib, "tc_fm_locate_mm" + sfx)(ctx.handle, fm._h, ptr[0], ptr[1], npat, k, ptr[2], ptr[3], ptr[4], C.byref(nh))
+    if dev:
+        hoffs, hits, mm = (t.cpu().numpy().view(a.dtype) for t, a in zip(bufs[2:], host[2:]))
+    return rc, int(nh.value), hoffs, hits, mm
+
+
+def _edge_patterns(seed, tb, alphabet, npat, hit):
+    """hit: substrings of the text, 3 .. 8 symbols (every one occurs).  Otherwise: random strings of 16 symbols, and the
+    reference confirms that none has an occurrence within distance 1"""
+    rng = np.random.default_rng(seed)
+    a = np.frombuffer(bytes(alphabet), np.uint8)
+    pats = []
+    while len(pats) < npat:
+        if hit:
+            m = int(rng.integers(3, 9)); o = int(rng.integers(0, len(tb) - m + 1))
+            pats.append(tb[o:o + m])
+        else:
+            p = a[rng.integers(0, len(a), 16)].tobytes()
+            if R.count(tb, p, 1) == 0:
+                pats.append(p)
+    return pats
+
+
+@pytest.mark.parametrize("npat", [1, 2049])
+@pytest.mark.parametrize("rate", [1, 4])
+@pytest.mark.parametrize("name", sorted(EDGE_TEXTS))
+def test_zero_hit_batches(ctx, edge_indexes, name, rate, npat):
+    """no pattern occurs (within distance 1): TC_OK, a total of 0, all npat + 1 offsets 0, the hit buffers untouched -- with
+    room for hits, and with no room and null hit buffers"""
+    tb, fm = edge_indexes[name, rate]
+    pats = _edge_patterns(0x9B10 + npat, tb, EDGE_TEXTS[name], npat, hit=False)
+    assert all(R.count(tb, p, 1) == 0 for p in pats)
+    for k in (None, 1):
+        for dev in (False, True):
+            for cap, null_hits in ((8, False), (0, True)):
+                rc, nhits, hoffs, hits, mm = _raw_locate_any(ctx, fm, pats, k, cap, dev, null_hits)
+                what = (name, rate, npat, k, dev, cap)
+                assert rc == EDGE_TC_OK and nhits == 0, what
+                assert len(hoffs) == npat + 1 and not hoffs.any(), what
+                assert (hits == 0xABABABABABABABAB).all() and (mm == 0xAB).all(), what
+
+
+@pytest.mark.parametrize("npat", [1, 2049])
+@pytest.mark.parametrize("rate", [1, 4])
+@pytest.mark.parametrize("name", sorted(EDGE_TEXTS))
+def test_total_slot_on_the_capacity_path(ctx, edge_indexes, name, rate, npat):
+    """one slot short: TC_ERR_CAPACITY, *nhits = the total (the reference's), the hit buffers untouched, and the _dev
+    entries leave the total in d_hit_offs[npat]"""
+    from textcomp import _lib
+    tb, fm = edge_indexes[name, rate]
+    pats = _edge_patterns(0x9B20 + npat, tb, EDGE_TEXTS[name], npat, hit=True)
+    for k in (None, 1):
+        need = sum(R.count(tb, p, k or 0) for p in pats)
+        assert need >= npat
+        for dev in (False, True):
+            rc, nhits, hoffs, hits, mm = _raw_locate_any(ctx, fm, pats, k, need - 1, dev)
+            what = (name, rate, npat, k, dev)
+            assert rc == _lib.TC_ERR_CAPACITY and nhits == need, what
+            assert (hits == 0xABABABABABABABAB).all() and (mm == 0xAB).all(), what
+            if dev:
+                assert int(hoffs[npat]) == need, what
+            rc, nhits, hoffs, hits, mm = _raw_locate_any(ctx, fm, pats, k, need, dev)
+            assert rc == EDGE_TC_OK and nhits == need and int(hoffs[npat]) == need and hoffs[0] == 0, what
+            assert (hits[need:] == 0xABABABABABABABAB).all() and (hits[:need] >= 1).all() and (hits[:need] <= len(tb)).all(), what
+
+
 def test_python_mirrors(ctx):
     from textcomp import fmindex
     tb = b"ACGTACGTTACGA"

@@ -243,6 +243,7 @@ def test_locate_dev_on_a_full_index_and_capacity_protocol(ctx):
                                           C.c_void_p(hoffs.data_ptr()), C.c_void_p(hits.data_ptr()), C.byref(nh))
             assert rc == _lib.TC_ERR_CAPACITY and nh.value == total
             assert bool((hits == 0x5A5A5A5A5A5A5A5A).all()), "d_hits was written to although the capacity did not suffice"
+            assert int(hoffs[-1]) == total and int(hoffs[0]) == 0     # the offsets and the total are there all the same
         # the exact capacity works, and the slots behind it stay untouched
         hoffs = torch.zeros(len(pats) + 1, dtype=torch.int64, device="cuda")
         hits = torch.full((total + 8,), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
@@ -283,7 +284,7 @@ def test_footprint_follows_from_the_layout(ctx):
 
 
 # ------------------------------------------------------------------------------------------------ 7
-# the export's layout (csrc/textcomp.hip, FmWire): a 1600-byte header padded to 256, then every part padded to 256
+# the export's layout (csrc/tc_fm_host.hpp, FmWire): a 1600-byte header padded to 256, then every part padded to 256
 _HDR = 1792
 _OFF_N, _OFF_LINES, _OFF_BYTES, _OFF_SIGMA, _OFF_PAIRS, _OFF_RATE = 8, 32, 40, 48, 56, 60
 
@@ -468,22 +469,80 @@ def _child_shared_sampled():
 
 
 # ------------------------------------------------------------------------------------------------ 9
-def test_bad_rates_are_refused(ctx):
+def _build_calls(ctx, tb, d_t):
+    """the six builds as (name, call(n, sa_rate, text_rate, out) -> rc, takes sa_rate, takes text_rate); tb: numpy uint8, d_t:
+    the same text on the device"""
+    lib, H = ctx.lib, ctx.handle
+    hp = tb.ctypes.data_as(C.c_void_p) if len(tb) else None
+    dp = C.c_void_p(d_t.data_ptr()) if len(tb) else None
+    return [("build", lambda n, sa, tx, out: lib.tc_fm_build(H, hp, n, out), False, False),
+            ("build_dev", lambda n, sa, tx, out: lib.tc_fm_build_dev(H, dp, n, out), False, False),
+            ("build_sampled", lambda n, sa, tx, out: lib.tc_fm_build_sampled(H, hp, n, sa, out), True, False),
+            ("build_sampled_dev", lambda n, sa, tx, out: lib.tc_fm_build_sampled_dev(H, dp, n, sa, out), True, False),
+            ("build_self", lambda n, sa, tx, out: lib.tc_fm_build_self(H, hp, n, sa, tx, out), True, True),
+            ("build_self_dev", lambda n, sa, tx, out: lib.tc_fm_build_self_dev(H, dp, n, sa, tx, out), True, True)]
+
+
+@pytest.mark.parametrize("bad", [0, 3, 8192, 6, 4097, 1 << 31])
+def test_bad_rates_are_refused(ctx, bad):
+    """a bad sa_rate or text_rate (8192 = TC_FM_MAX_SA_RATE * 2), a text above TC_MAX_N and a null `out`: TC_ERR_ARG from
+    every build that takes the argument, and *out is null afterwards where it was given"""
     import torch
     from textcomp import _lib
+    assert 8192 == _lib.TC_FM_MAX_SA_RATE * 2
     tb = np.frombuffer(b"abracadabra", np.uint8).copy()
     d_t = torch.from_numpy(tb).cuda()
     torch.cuda.synchronize()
-    for k in (0, 3, 8192, 6, 4097, 1 << 31):
-        for fn, ptr in ((ctx.lib.tc_fm_build_sampled, tb.ctypes.data_as(C.c_void_p)),
-                        (ctx.lib.tc_fm_build_sampled_dev, C.c_void_p(d_t.data_ptr()))):
+    for name, call, takes_sa, takes_text in _build_calls(ctx, tb, d_t):
+        tries = [(len(tb), bad, 16)] * takes_sa + [(len(tb), 4, bad)] * takes_text + [(0x7ffffff0 + 1, 4, 16)]
+        for n, sa, tx in tries:
             h = C.c_void_p(0xDEAD)
-            assert fn(ctx.handle, ptr, len(tb), k, C.byref(h)) == _lib.TC_ERR_ARG
-            assert not h.value, "*out must be null after a refused build"
+            assert call(n, sa, tx, C.byref(h)) == _lib.TC_ERR_ARG, (name, n, sa, tx)
+            assert not h.value, "*out must be null after a refused build: " + name
+        assert call(len(tb), 4, 16, None) == _lib.TC_ERR_ARG, name
     fm = ctx.fm_build(bytes(tb), sa_rate=4096)          # the largest rate; the context is usable
     assert fm.sa_rate == 4096 and [h.tolist() for h in fm.locate([b"abra"])] == [O.FMIndex(bytes(tb)).locate(b"abra")]
     fm.close()
     assert ctx.encode(bytes(tb))["n"] == len(tb)
+
+
+@pytest.mark.parametrize("n", [0, 1, 448])
+def test_the_six_builds_agree(ctx, n):
+    """the host and the _dev form of tc_fm_build, tc_fm_build_sampled (4) and tc_fm_build_self (4, 16) make the same index:
+    equal tc_fm_info, rates and export bytes (into zeroed buffers: the padding between the parts is not written)"""
+    import torch
+    from textcomp import FMIndexHandle
+    tb = np.frombuffer(bytes(b"ACGT"[int(v)] for v in np.random.default_rng(0x5A9 + n).integers(0, 4, n)), np.uint8).copy()
+    d_t = torch.from_numpy(np.concatenate([tb, np.zeros(16, np.uint8)])).cuda()[:n]
+    torch.cuda.synchronize()
+
+    def describe(fm):
+        info = fm.info()
+        d = [info["N"], info["sigma"], info["primary"], info["c_sym"].tolist(), info["c_val"].tolist(), fm.sa_rate, fm.text_rate]
+        for w in (0, 1):
+            nb = int(ctx.lib.tc_fm_export_bound(fm._h, w))
+            buf = torch.zeros(nb, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            used = C.c_uint64(nb)
+            ctx._check(ctx.lib.tc_fm_export_dev(ctx.handle, fm._h, w, C.c_void_p(buf.data_ptr()), C.byref(used)))
+            assert used.value == nb
+            d.append(buf.cpu().numpy().tobytes())
+        return d
+
+    calls = _build_calls(ctx, tb, d_t)
+    want_rates = [(1, 0), (4, 0), (4, 16)] if n else [(0, 0)] * 3
+    for (name_h, host, _, _), (name_d, dev, _, _), rates in zip(calls[0::2], calls[1::2], want_rates):
+        made = []
+        for call in (host, dev):
+            h = C.c_void_p()
+            ctx._check(call(n, 4, 16, C.byref(h)))
+            assert h.value
+            made.append(FMIndexHandle(ctx, None, _handle=h, _n=n))
+        a, b = (describe(fm) for fm in made)
+        assert a == b, (name_h, name_d, n)
+        assert (a[5], a[6]) == rates and a[0] == (n + 1 if n else 0), (name_h, n)
+        for fm in made:
+            fm.close()
 
 
 if __name__ == "__main__":

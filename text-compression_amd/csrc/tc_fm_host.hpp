@@ -773,3 +773,505 @@ static void fm_mm_device(tc_ctx *ctx, const tc_fm *fm, const u8 *d_pats, const u
 #undef FM_MM_LAUNCH
     TC_LAUNCH_CHECK(ctx);
 }
+
+// ======================================================================================================================
+// The bodies of the tc_fm_* entry points (textcomp.hip forwards to them inside TC_API_BEGIN / TC_API_END).  A pair of
+// entry points that differs only in where its buffers live is one function with a `dev` flag; the exact search and the
+// search with mismatches are one function with an `exact` flag (k is ignored when it is set).
+
+static_assert(TC_FM_MAX_MISMATCH == FM_MM_MAXK, "fm_mm_kernel keeps TC_FM_MAX_MISMATCH frames per lane");
+
+static inline bool fm_rate_ok(u32 r) { return r >= 1 && r <= TC_FM_MAX_SA_RATE && (r & (r - 1)) == 0; }
+
+// the index of an empty text (FMIndex.hs:366: every query returns the empty result), and what an import starts from
+static tc_fm *fm_new_empty(tc_ctx *ctx) {
+    tc_fm *fm = new tc_fm();
+    fm->device = ctx->device;
+    return fm;
+}
+
+// the six tc_fm_build*: text_host or text_dev is the text (the other is null); rates = how many of (sa_rate, text_rate) are
+// the caller's and therefore validated -- 0: tc_fm_build, 1: tc_fm_build_sampled, 2: tc_fm_build_self
+static void fm_build_entry(tc_ctx *ctx, const u8 *text_host, const u8 *text_dev, u64 n, u32 sa_rate, u32 text_rate, int rates,
+                           tc_fm **out) {
+    static const char *const kBadArg[3] = {"bad argument", "bad argument (sa_rate: a power of two, 1 .. %d)",
+                                           "bad argument (sa_rate, text_rate: powers of two, 1 .. %d)"};
+    if (out) *out = nullptr;
+    if (!out || n > TC_MAX_N || (rates >= 1 && !fm_rate_ok(sa_rate)) || (rates >= 2 && !fm_rate_ok(text_rate)))
+        TC_FAIL(ctx, TC_ERR_ARG, kBadArg[rates], TC_FM_MAX_SA_RATE);
+    if (n == 0) {
+        *out = fm_new_empty(ctx);
+        return;
+    }
+    if (!text_host && !text_dev) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    *out = fm_build_device(ctx, text_host, n, text_dev, sa_rate, text_rate);
+}
+
+static u64 fm_device_bytes(const tc_fm *fm, int part) {
+    if (!fm || fm->n == 0 || part < 0 || part > 2) return 0;
+    const u64 ext = fm->text_rate ? fm->nisa * sizeof(u32) : 0;
+    if (part == 2) return ext;
+    u64 loc = 0;
+    if (fm->sa_rate == 1) loc = (fm->N + 16) + fm->N * sizeof(u32);
+    else if (fm->sa_rate > 1) loc = (fm->N + 16) + fm->lines * 64 + fm->nsamples * sizeof(u32);
+    if (part == 1) return loc;
+    u64 b = loc + ext + 768 * sizeof(u32) + (u64)fm->sigma_bytes * fm->lines * 64;
+    if (fm->d_bits2) b += (u64)fm->sigma_bytes * fm->sigma_bytes * fm->lines * 64 + FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32);
+    return b;
+}
+
+static int fm_info(const tc_fm *fm, u64 *N, u32 *sigma, i16 *c_sym, u64 *c_val, u64 *primary) {
+    if (!fm) return TC_ERR_ARG;
+    if (N) *N = fm->N;
+    if (primary) *primary = fm->primary;
+    u32 sg = 0;
+    if (fm->n) {  // seqToCc rows: (0, Nothing) first, then every present byte
+        u64 acc = 1;
+        if (c_sym) c_sym[0] = -1;
+        if (c_val) c_val[0] = 0;
+        sg = 1;
+        for (u32 c = 0; c < fm->sigma_bytes; c++, sg++) {
+            if (c_sym) c_sym[sg] = fm->sym_of_code[c];
+            if (c_val) c_val[sg] = acc;
+            acc += fm->counts[fm->sym_of_code[c]];
+        }
+    }
+    if (sigma) *sigma = sg;
+    return TC_OK;
+}
+
+// ---- the index as one device byte string (replication over the GPUs of a node) ----------------
+struct FmWire {
+    char magic[8];   // "TCFMI02\0"
+    u64 n, N, primary, lines, bytes;
+    u32 sigma_bytes, with_locate;   // with_locate: bit 0 = the locate part follows; bits 8.. = text_rate of the text samples
+                                    // that follow the locate part (0: none -- an index without them writes 0 or 1 as ever)
+    u32 with_pairs, sa_rate;    // 1: the pair vectors (sigma_bytes^2 of them) follow the per-byte vectors.  sa_rate (the word was
+                                // reserved = 0 before sampled indexes): 0 or 1 = the locate part is L + the full suffix array;
+                                // k > 1 = L + marks + samples (a full index writes 0: its export is what it always was)
+    u32 counts[256];
+    i16 sym_of_code[256];
+};
+static const char kFmMagic[8] = {'T', 'C', 'F', 'M', 'I', '0', '2', 0};
+static inline u64 fm_wire_align(u64 v) { return (v + 255) & ~(u64)255; }
+
+// What follows the header, in order: every part is `bytes` long and takes `padded` bytes of the string.  This list is the
+// layout: the size, the export's copies, the import's size check and the import's copies all walk it.
+enum FmPartKind { FM_PART_BITS, FM_PART_BITS2, FM_PART_L, FM_PART_MARKS, FM_PART_SAMPLES, FM_PART_SA, FM_PART_ISA };
+enum { FM_LOCATE_NONE = 0, FM_LOCATE_FULL = 1, FM_LOCATE_SAMPLED = 2 };
+struct FmWireLayout {
+    struct Part {
+        FmPartKind kind;
+        u64 bytes, padded;
+    } part[6];
+    int nparts = 0;
+    u64 total = fm_wire_align(sizeof(FmWire));
+    void add(FmPartKind kind, u64 bytes, u64 reserved) {
+        part[nparts++] = {kind, bytes, fm_wire_align(reserved)};
+        total += fm_wire_align(reserved);
+    }
+};
+static FmWireLayout fm_wire_layout(u64 n, u64 N, u64 lines, u32 sigma_bytes, bool with_pairs, int locate, u64 nsamples, u64 nisa) {
+    FmWireLayout Y;
+    if (n == 0) return Y;
+    const u64 bb = (u64)sigma_bytes * lines * 64;
+    Y.add(FM_PART_BITS, bb, bb);
+    if (with_pairs) Y.add(FM_PART_BITS2, bb * sigma_bytes, bb * sigma_bytes);
+    if (locate) Y.add(FM_PART_L, N, N + 16);
+    if (locate == FM_LOCATE_SAMPLED) {
+        Y.add(FM_PART_MARKS, lines * 64, lines * 64);
+        Y.add(FM_PART_SAMPLES, nsamples * sizeof(u32), nsamples * sizeof(u32));
+    } else if (locate) {
+        Y.add(FM_PART_SA, N * sizeof(u32), N * sizeof(u32));
+    }
+    if (nisa) Y.add(FM_PART_ISA, nisa * sizeof(u32), nisa * sizeof(u32));
+    return Y;
+}
+// what an export of fm holds (the text samples travel only behind a locate part)
+static FmWireLayout fm_wire_layout(const tc_fm *fm, int with_locate) {
+    return fm_wire_layout(fm->n, fm->N, fm->lines, fm->sigma_bytes, fm->d_bits2 != nullptr,
+                          !with_locate ? FM_LOCATE_NONE : fm->sa_rate > 1 ? FM_LOCATE_SAMPLED : FM_LOCATE_FULL, fm->nsamples,
+                          with_locate && fm->text_rate ? fm->nisa : 0);
+}
+// the index's device pointer of a part
+static void **fm_part_slot(tc_fm *fm, FmPartKind kind) {
+    switch (kind) {
+    case FM_PART_BITS: return (void **)&fm->d_bits;
+    case FM_PART_BITS2: return (void **)&fm->d_bits2;
+    case FM_PART_L: return (void **)&fm->d_L;
+    case FM_PART_MARKS: return (void **)&fm->d_marks;
+    case FM_PART_SAMPLES: return (void **)&fm->d_samples;
+    case FM_PART_SA: return (void **)&fm->d_sa;
+    default: return (void **)&fm->d_isa;
+    }
+}
+
+static u64 fm_export_bound(const tc_fm *fm, int with_locate) { return fm ? fm_wire_layout(fm, with_locate).total : 0; }
+
+static void fm_export_device(tc_ctx *ctx, const tc_fm *fm, int with_locate, u8 *d_out, u64 *bytes) {
+    if (!fm || !bytes) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const FmWireLayout Y = fm_wire_layout(fm, with_locate);
+    const u64 need = Y.total, cap = *bytes;
+    *bytes = need;
+    if (cap < need) TC_FAIL(ctx, TC_ERR_CAPACITY, "index export needs %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)cap);
+    if (!d_out || ((uintptr_t)d_out & 15)) TC_FAIL(ctx, TC_ERR_ARG, "export buffer must be 16-byte aligned");
+    FmWire h = {};
+    memcpy(h.magic, kFmMagic, 8);
+    h.n = fm->n; h.N = fm->N; h.primary = fm->primary; h.lines = fm->lines; h.bytes = need;
+    h.sigma_bytes = fm->sigma_bytes; h.with_locate = (fm->n && with_locate) ? (1u | fm->text_rate << 8) : 0u;
+    h.with_pairs = fm->d_bits2 ? 1u : 0u;
+    h.sa_rate = (h.with_locate && fm->sa_rate > 1) ? fm->sa_rate : 0u;
+    memcpy(h.counts, fm->counts, sizeof h.counts);
+    memcpy(h.sym_of_code, fm->sym_of_code, sizeof h.sym_of_code);
+    hipStream_t s = ctx->stream;
+    TC_HIP(ctx, hipMemcpyAsync(d_out, &h, sizeof h, hipMemcpyHostToDevice, s));
+    u64 o = fm_wire_align(sizeof(FmWire));
+    for (int i = 0; i < Y.nparts; o += Y.part[i++].padded)
+        TC_HIP(ctx, hipMemcpyAsync(d_out + o, *fm_part_slot(const_cast<tc_fm *>(fm), Y.part[i].kind), Y.part[i].bytes,
+                                   hipMemcpyDeviceToDevice, s));
+    TC_HIP(ctx, hipStreamSynchronize(s));   // h is a stack object
+}
+
+// an import check only the device can make: `launch(grid, d_res)` reduces `items` items into the zeroed 8 bytes at d_res,
+// which are returned
+template <class Launch>
+static u64 fm_import_probe(tc_ctx *ctx, u64 items, Launch &&launch) {
+    hipStream_t s = ctx->stream;
+    u64 *d_res = ctx->d_scalars + 10;
+    TC_HIP(ctx, hipMemsetAsync(d_res, 0, sizeof(u64), s));
+    u32 grid = tc_cdiv(items, 256 * 16);
+    if (grid > 4096) grid = 4096;
+    launch(grid, d_res);
+    TC_LAUNCH_CHECK(ctx);
+    TC_HIP(ctx, hipMemcpyAsync(&ctx->h_scalars[10], d_res, sizeof(u64), hipMemcpyDeviceToHost, s));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    return ctx->h_scalars[10];
+}
+
+static void fm_import_device(tc_ctx *ctx, const u8 *d_in, u64 bytes, tc_fm **out) {
+    if (!out || !d_in || bytes < sizeof(FmWire)) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    *out = nullptr;
+    FmWire h;
+    hipStream_t s = ctx->stream;
+    TC_HIP(ctx, hipMemcpyAsync(&h, d_in, sizeof h, hipMemcpyDeviceToHost, s));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    if (memcmp(h.magic, "TCFMI0", 6) == 0 && memcmp(h.magic, kFmMagic, 8) != 0)   // (an export of another build: the layout changed)
+        TC_FAIL(ctx, TC_ERR_MALFORMED, "unsupported FM export version %.7s (this build reads %s: an export travels between ranks of one build, it is not an archive format)", h.magic, kFmMagic);
+    if (memcmp(h.magic, kFmMagic, 8) != 0 || h.bytes > bytes || h.N != (h.n ? h.n + 1 : 0) || h.n > TC_MAX_N ||
+        h.sigma_bytes > 256 || (h.n && h.lines != h.N / FM_LINE_BITS + 1))
+        TC_FAIL(ctx, TC_ERR_MALFORMED, "not an exported FM-index");
+    {   // the scalars fm_count / fm_locate index with: primary row, symbol counts, code table
+        u64 total = 0;
+        u32 present = 0;
+        bool codes_ok = true;
+        for (int b = 0; b < 256; b++) {
+            total += h.counts[b];
+            if (h.counts[b]) {
+                codes_ok = codes_ok && present < h.sigma_bytes && h.sym_of_code[present] == (i16)b;
+                present++;
+            }
+        }
+        if (h.n && (h.primary == 0 || h.primary >= h.N || total != h.n || present != h.sigma_bytes || !codes_ok))
+            TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: header is inconsistent");
+    }
+    if (h.with_pairs > 1 || (h.with_pairs && (h.sigma_bytes > FM_PAIR_SIGMA || h.n < 2)))
+        TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: header is inconsistent");
+    // the sampling rate rides in the word that was reserved: 0 or 1 = full suffix array; otherwise a power of two within range,
+    // and only where there is a locate part
+    // the text samples' rate rides above bit 7 of the with_locate word: 0 = none; otherwise a power of two within range, and
+    // only behind a locate part
+    const bool wire_locate = (h.with_locate & 0xffu) != 0;
+    const u32 wire_text_rate = h.with_locate >> 8;
+    const bool wire_sampled = h.sa_rate > 1;
+    if (wire_sampled && (!fm_rate_ok(h.sa_rate) || !wire_locate || !h.n))
+        TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: bad suffix-array sampling rate %u", h.sa_rate);
+    if (wire_text_rate && (!fm_rate_ok(wire_text_rate) || (h.with_locate & 0xffu) != 1 || !h.n))
+        TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: bad text sampling rate %u", wire_text_rate);
+    tc_fm *fm = fm_new_empty(ctx);
+    fm->n = h.n; fm->N = h.N; fm->primary = h.primary; fm->lines = h.lines; fm->sigma_bytes = h.sigma_bytes;
+    memcpy(fm->counts, h.counts, sizeof h.counts);
+    memcpy(fm->sym_of_code, h.sym_of_code, sizeof h.sym_of_code);
+    try {
+        if (fm->n) {
+            if (wire_sampled) fm->nsamples = fm->n / h.sa_rate + 1;
+            if (wire_text_rate) fm->nisa = fm->n / wire_text_rate + 1;
+            const FmWireLayout Y = fm_wire_layout(fm->n, fm->N, fm->lines, fm->sigma_bytes, h.with_pairs != 0,
+                                                  wire_sampled ? FM_LOCATE_SAMPLED : wire_locate ? FM_LOCATE_FULL : FM_LOCATE_NONE,
+                                                  fm->nsamples, fm->nisa);
+            if (Y.total != h.bytes) TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: size mismatch");
+            u32 tab[768];
+            (void)fm_make_tab(fm->counts, tab, nullptr);
+            TC_HIP(ctx, hipMalloc((void **)&fm->d_tab, 768 * sizeof(u32)));
+            TC_HIP(ctx, hipMemcpyAsync(fm->d_tab, tab, sizeof tab, hipMemcpyHostToDevice, s));
+            TC_HIP(ctx, hipStreamSynchronize(s));   // tab is a stack buffer
+            u64 o = fm_wire_align(sizeof(FmWire));
+            for (int i = 0; i < Y.nparts; o += Y.part[i++].padded) {
+                void **slot = fm_part_slot(fm, Y.part[i].kind);
+                const bool is_L = Y.part[i].kind == FM_PART_L;   // (L is allocated with the 16 zero bytes of slack it is exported with)
+                TC_HIP(ctx, hipMalloc(slot, Y.part[i].bytes + (is_L ? 16 : 0)));
+                if (is_L) TC_HIP(ctx, hipMemsetAsync(fm->d_L + fm->N, 0, 16, s));
+                TC_HIP(ctx, hipMemcpyAsync(*slot, d_in + o, Y.part[i].bytes, hipMemcpyDeviceToDevice, s));
+            }
+            if (h.with_pairs) {
+                TC_HIP(ctx, hipMalloc((void **)&fm->d_tab2, FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32)));
+                TC_HIP(ctx, hipMemsetAsync(fm->d_tab2, 0, FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32), s));
+                fm_c2_kernel<<<1, 64, 0, s>>>(fm->d_bits, fm->lines, fm->d_tab, fm->sigma_bytes, fm->d_tab2);
+                TC_LAUNCH_CHECK(ctx);
+            }
+            if (wire_sampled) {
+                // what only the device can check: the marks hold exactly one bit per sample (the walk bounds everything else)
+                const u64 ones = fm_import_probe(ctx, fm->lines * 8, [&](u32 grid, u64 *d_res) {
+                    fm_popcount_kernel<<<grid, 256, 0, s>>>(fm->d_marks, fm->lines, reinterpret_cast<unsigned long long *>(d_res));
+                });
+                if (ones != fm->nsamples)
+                    TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: %llu rows are marked as sampled, %llu samples follow",
+                            (unsigned long long)ones, (unsigned long long)fm->nsamples);
+                fm->sa_rate = h.sa_rate;
+            } else if (wire_locate) {
+                fm->sa_rate = 1;
+            }
+            if (wire_text_rate) {
+                // what only the device can check: every sample is a row, and position 0 is the primary row's (the walk bounds
+                // everything else)
+                const u64 res = fm_import_probe(ctx, fm->nisa, [&](u32 grid, u64 *d_res) {
+                    fm_isa_max_kernel<<<grid, 256, 0, s>>>(fm->d_isa, fm->nisa, reinterpret_cast<u32 *>(d_res));
+                });
+                const u64 isa_max = res & 0xffffffffu, isa0 = res >> 32;
+                if (isa_max >= fm->N || isa0 != fm->primary)
+                    TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: text samples out of range (largest row %llu of %llu, position 0 at row %llu, primary row %llu)",
+                            (unsigned long long)isa_max, (unsigned long long)fm->N, (unsigned long long)isa0, (unsigned long long)fm->primary);
+                fm->text_rate = wire_text_rate;
+            }
+            TC_HIP(ctx, hipStreamSynchronize(s));
+        }
+    } catch (...) {
+        fm_release(fm);
+        throw;
+    }
+    *out = fm;
+}
+
+// ---- queries ---------------------------------------------------------------------------------------------------------
+// the answer "nothing" of an edge case (an empty index, an empty batch), written where the results live
+static void fm_zero_result(tc_ctx *ctx, void *p, size_t bytes, bool dev) {
+    if (!dev) {
+        memset(p, 0, bytes);
+        return;
+    }
+    tc_memset_async(ctx, p, 0, bytes);
+    tc_sync_check(ctx);
+}
+
+// the host forms' pattern batch in the workspace: carve inside the call's plan, upload behind it
+struct FmPatterns {
+    u8 *d_pats = nullptr;
+    u64 *d_offs = nullptr;
+    void carve(Arena &A, const u64 *offs, u64 npat) {
+        d_pats = A.get<u8>(offs[npat] + 16);
+        d_offs = A.get<u64>(npat + 1);
+    }
+    void upload(tc_ctx *ctx, const u8 *pats, const u64 *offs, u64 npat) {
+        tc_h2d(ctx, d_pats, pats, offs[npat]);
+        tc_h2d(ctx, d_offs, offs, (npat + 1) * sizeof(u64));
+    }
+};
+
+// the count pass of both searches: d_cnt[p] = hits of pattern p (exactly, or within distance k); d_ranges (the exact search
+// only; may be null) as fm_count_kernel writes them
+static void fm_count_pass(tc_ctx *ctx, const tc_fm *fm, const u8 *d_pats, const u64 *d_offs, u64 npat, bool exact, u32 k,
+                          i64 *d_cnt, u64 *d_ranges) {
+    if (exact) fm_count_device(ctx, fm, d_pats, d_offs, npat, d_cnt, d_ranges);
+    else fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, d_cnt, nullptr, nullptr, nullptr);
+}
+
+// tc_fm_count, tc_fm_count_dev, tc_fm_count_mm, tc_fm_count_mm_dev
+static void fm_count_entry(tc_ctx *ctx, const tc_fm *fm, const u8 *pats, const u64 *offs, u64 npat, bool exact, u32 k, i64 *out,
+                           bool dev) {
+    if (!fm) TC_FAIL(ctx, TC_ERR_ARG, "null index");
+    if (!exact && k > TC_FM_MAX_MISMATCH) TC_FAIL(ctx, TC_ERR_ARG, "k = %u mismatches (at most %d)", k, TC_FM_MAX_MISMATCH);
+    if (npat == 0) return;
+    if (!pats || !offs || !out) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (fm->n == 0) return fm_zero_result(ctx, out, npat * sizeof(i64), dev);
+    if (dev) {
+        fm_count_pass(ctx, fm, pats, offs, npat, exact, k, out, nullptr);
+    } else {
+        FmPatterns P;
+        i64 *d_out = nullptr;
+        tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+            P.carve(A, offs, npat);
+            d_out = A.get<i64>(npat);
+        });
+        P.upload(ctx, pats, offs, npat);
+        fm_count_pass(ctx, fm, P.d_pats, P.d_offs, npat, exact, k, d_out, nullptr);
+        tc_d2h(ctx, out, d_out, npat * sizeof(i64));
+    }
+    tc_sync_check(ctx);
+}
+
+// scratch of one locate batch besides patterns and results (the ranges: the exact search only)
+struct FmLocateScratch {
+    i64 *d_cnt = nullptr;
+    u64 *d_ranges = nullptr, *d_len = nullptr, *d_tsum = nullptr;
+    void carve(Arena &A, u64 npat, bool exact) {
+        d_cnt = A.get<i64>(npat);
+        if (exact) d_ranges = A.get<u64>(2 * npat);
+        d_len = A.get<u64>(npat + 1);
+        d_tsum = A.get<u64>(tc_cdiv(npat, SCAN_TILE) + 2);
+    }
+};
+
+// everything on the device: the count pass, the scan of the counts (d_hoffs[0 .. npat], the last entry the total, which is
+// returned), then -- when the total is neither 0 nor above cap -- the fill pass: the exact search copies its ranges' rows out of
+// the suffix array (a full index) or writes the rows themselves (a sampled one); the search with mismatches repeats its
+// enumeration, writing positions or rows likewise and the distances to d_mm (may be null).  On a sampled index the walk then
+// turns rows into positions.  When the total exceeds cap nothing is written to d_hits or d_mm.  The caller synchronises
+// (tc_sync_check: the walk's bounds raise the device error word).
+static u64 fm_locate_device(tc_ctx *ctx, const tc_fm *fm, const FmLocateScratch &W, const u8 *d_pats, const u64 *d_offs, u64 npat,
+                            bool exact, u32 k, u64 *d_hoffs, u64 *d_hits, u8 *d_mm, u64 cap) {
+    hipStream_t s = ctx->stream;
+    const u32 grid = tc_cdiv(npat, 256);
+    fm_count_pass(ctx, fm, d_pats, d_offs, npat, exact, k, W.d_cnt, W.d_ranges);
+    fm_cnt_to_u64_kernel<<<grid, 256, 0, s>>>(W.d_cnt, npat, W.d_len);
+    TC_LAUNCH_CHECK(ctx);
+    const u64 *d_total = tc_scan64(ctx, W.d_len, npat, W.d_tsum, d_hoffs);
+    TC_HIP(ctx, hipMemcpyAsync(d_hoffs + npat, d_total, sizeof(u64), hipMemcpyDeviceToDevice, s));
+    tc_d2h(ctx, &ctx->h_scalars[9], d_total, sizeof(u64));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    const u64 need = ctx->h_scalars[9];
+    if (need > cap || need == 0) return need;
+    if (!exact) {
+        fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, nullptr, d_hoffs, d_hits, d_mm);
+    } else {
+        if (fm->sa_rate > 1) fm_locate_rows_kernel<<<grid, 256, 0, s>>>(W.d_ranges, d_hoffs, npat, cap, d_hits);
+        else fm_locate_fill_kernel<<<grid, 256, 0, s>>>(W.d_ranges, d_hoffs, fm->d_sa, npat, cap, d_hits);
+        TC_LAUNCH_CHECK(ctx);
+    }
+    if (fm->sa_rate > 1) {
+        fm_locate_walk_kernel<<<tc_cdiv(need, 256), 256, 0, s>>>(fm->d_bits, fm->d_marks, fm->lines, fm->d_tab, fm->sigma_bytes,
+                                                                fm->d_L, fm->d_samples, fm->nsamples, fm->N, fm->primary,
+                                                                fm->sa_rate, need, d_hits, ctx->d_err);
+        TC_LAUNCH_CHECK(ctx);
+    }
+    return need;
+}
+
+// tc_fm_locate, tc_fm_locate_dev, tc_fm_locate_mm, tc_fm_locate_mm_dev (hit_mm: the search with mismatches only; may be null)
+static void fm_locate_entry(tc_ctx *ctx, const tc_fm *fm, const u8 *pats, const u64 *offs, u64 npat, bool exact, u32 k,
+                            u64 *hit_offs, u64 *hits, u8 *hit_mm, u64 *nhits, bool dev) {
+    if (!fm || !nhits) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const u64 cap = *nhits;
+    *nhits = 0;
+    if (!exact && k > TC_FM_MAX_MISMATCH) TC_FAIL(ctx, TC_ERR_ARG, "k = %u mismatches (at most %d)", k, TC_FM_MAX_MISMATCH);
+    if (npat == 0) return;
+    if (!pats || !offs || !hit_offs || (!hits && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (fm->n == 0) return fm_zero_result(ctx, hit_offs, (npat + 1) * sizeof(u64), dev);
+    if (!fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
+    FmLocateScratch W;
+    FmPatterns P;
+    u64 *d_hoffs = hit_offs, *d_hits = hits;
+    u8 *d_mm = hit_mm;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+        if (!dev) P.carve(A, offs, npat);
+        W.carve(A, npat, exact);
+        if (!dev) {
+            d_hoffs = A.get<u64>(npat + 1);
+            d_hits = A.get<u64>(cap + 1);
+            d_mm = hit_mm ? A.get<u8>(cap + 16) : nullptr;
+        }
+    });
+    if (!dev) P.upload(ctx, pats, offs, npat);
+    const u64 need = fm_locate_device(ctx, fm, W, dev ? pats : P.d_pats, dev ? offs : P.d_offs, npat, exact, k, d_hoffs, d_hits,
+                                      d_mm, cap);
+    *nhits = need;
+    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu hit slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
+    if (!dev) {
+        tc_d2h(ctx, hit_offs, d_hoffs, (npat + 1) * sizeof(u64));
+        if (need) tc_d2h(ctx, hits, d_hits, need * sizeof(u64));
+        if (need && hit_mm) tc_d2h(ctx, hit_mm, d_mm, need);
+    }
+    tc_sync_check(ctx);
+}
+
+// scratch of one extract batch besides queries and results
+struct FmExtractScratch {
+    u64 *d_len = nullptr, *d_segs = nullptr, *d_soffs = nullptr, *d_tsum_b = nullptr, *d_tsum_s = nullptr;
+    u32 *d_bad = nullptr;
+    void carve(Arena &A, u64 nq) {
+        const u64 tiles = tc_cdiv(nq, SCAN_TILE);
+        d_len = A.get<u64>(nq);
+        d_segs = A.get<u64>(nq);
+        d_soffs = A.get<u64>(nq + 1);
+        d_tsum_b = A.get<u64>(tiles + 2);
+        d_tsum_s = A.get<u64>(tiles + 2);
+        d_bad = A.get<u32>(2);
+    }
+};
+
+// everything on the device: the plan (validation, byte and segment counts, their scans: d_out_offs[0 .. nq], the last entry
+// the total), then -- after the host has seen the flag and the totals -- the walks.  Returns the byte total; a bad query is
+// TC_ERR_ARG, and then, as with a total above cap, nothing is written to d_out.  The caller synchronises (tc_sync_check:
+// the walk's bounds raise the device error word).
+static u64 fm_extract_device(tc_ctx *ctx, const tc_fm *fm, const FmExtractScratch &W, const u64 *d_starts, const u64 *d_lens,
+                             u64 nq, u64 *d_out_offs, u8 *d_out, u64 cap) {
+    hipStream_t s = ctx->stream;
+    const u32 lg = fm_log2(fm->text_rate);
+    TC_HIP(ctx, hipMemsetAsync(W.d_bad, 0, 2 * sizeof(u32), s));
+    fm_extract_plan_kernel<<<tc_cdiv(nq, 256), 256, 0, s>>>(d_starts, d_lens, nq, fm->n, lg, W.d_len, W.d_segs, W.d_bad);
+    TC_LAUNCH_CHECK(ctx);
+    const u64 *d_bytes = tc_scan64(ctx, W.d_len, nq, W.d_tsum_b, d_out_offs);
+    const u64 *d_nsegs = tc_scan64(ctx, W.d_segs, nq, W.d_tsum_s, W.d_soffs);
+    TC_HIP(ctx, hipMemcpyAsync(d_out_offs + nq, d_bytes, sizeof(u64), hipMemcpyDeviceToDevice, s));
+    tc_d2h(ctx, &ctx->h_scalars[9], d_bytes, sizeof(u64));
+    tc_d2h(ctx, &ctx->h_scalars[8], d_nsegs, sizeof(u64));
+    tc_d2h(ctx, &ctx->h_scalars[10], W.d_bad, sizeof(u32));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    const u64 need = ctx->h_scalars[9], nsegs = ctx->h_scalars[8];
+    if ((u32)ctx->h_scalars[10])
+        TC_FAIL(ctx, TC_ERR_ARG, "extract: a query lies outside the text (start is 1-based: 1 <= start, start - 1 + len <= %llu)",
+                (unsigned long long)fm->n);
+    if (need > cap || nsegs == 0) return need;
+    fm_extract_walk_kernel<<<tc_cdiv(nsegs, 256), 256, 0, s>>>(fm->d_bits, fm->lines, fm->d_tab, fm->sigma_bytes, fm->d_L,
+                                                             fm->d_isa, fm->nisa, fm->N, fm->primary, lg, d_starts, d_lens,
+                                                             W.d_soffs, d_out_offs, nq, nsegs, d_out, ctx->d_err);
+    TC_LAUNCH_CHECK(ctx);
+    return need;
+}
+
+// tc_fm_extract, tc_fm_extract_dev
+static void fm_extract_entry(tc_ctx *ctx, const tc_fm *fm, const u64 *starts, const u64 *lens, u64 nq, u64 *out_offs, u8 *out,
+                             u64 *nbytes, bool dev) {
+    if (!fm || !nbytes) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const u64 cap = *nbytes;
+    *nbytes = 0;
+    if (nq == 0) {
+        if (out_offs) fm_zero_result(ctx, out_offs, sizeof(u64), dev);
+        return;
+    }
+    if (!fm->text_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index holds no text samples (build it with tc_fm_build_self; an import without the locate part has none)");
+    if (!starts || !lens || !out_offs || (!out && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    u64 *u_starts = nullptr, *u_lens = nullptr;   // the host form's copies of the queries
+    u64 *d_offs = out_offs;
+    u8 *d_out = out;
+    FmExtractScratch W;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+        if (!dev) {
+            u_starts = A.get<u64>(nq);
+            u_lens = A.get<u64>(nq);
+            d_offs = A.get<u64>(nq + 1);
+        }
+        W.carve(A, nq);
+        if (!dev) d_out = A.get<u8>(cap + 16);
+    });
+    if (!dev) {
+        tc_h2d(ctx, u_starts, starts, nq * sizeof(u64));
+        tc_h2d(ctx, u_lens, lens, nq * sizeof(u64));
+    }
+    const u64 need = fm_extract_device(ctx, fm, W, dev ? starts : u_starts, dev ? lens : u_lens, nq, d_offs, d_out, cap);
+    *nbytes = need;
+    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)cap);
+    if (!dev) {
+        tc_d2h(ctx, out_offs, d_offs, (nq + 1) * sizeof(u64));
+        if (need) tc_d2h(ctx, out, d_out, need);
+    }
+    tc_sync_check(ctx);
+}

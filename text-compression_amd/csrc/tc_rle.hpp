@@ -396,6 +396,18 @@ __global__ __launch_bounds__(SCAN_NT) void scan64_down_kernel(const u64 *__restr
         run += v[k];
     }
 }
+// the three of them on the context's stream: out[0 .. n) = the exclusive scan of in[0 .. n); tsum holds
+// cdiv(n, SCAN_TILE) + 2 words.  Returns where the total is left (tsum[tiles], on the device).
+static const u64 *tc_scan64(tc_ctx *ctx, const u64 *in, u64 n, u64 *tsum, u64 *out) {
+    const u32 tiles = tc_cdiv(n, SCAN_TILE);
+    scan64_reduce_kernel<<<tiles, SCAN_NT, 0, ctx->stream>>>(in, n, tsum);
+    TC_LAUNCH_CHECK(ctx);
+    scan64_spine_kernel<<<1, 1024, 0, ctx->stream>>>(tsum, tiles);
+    TC_LAUNCH_CHECK(ctx);
+    scan64_down_kernel<<<tiles, SCAN_NT, 0, ctx->stream>>>(in, n, tsum, out);
+    TC_LAUNCH_CHECK(ctx);
+    return tsum + tiles;
+}
 
 // one lane per run fills its slice; runs >= 32 are filled by the whole wave; runs >= RLE_HUGE are
 // queued and filled by the whole grid afterwards (a block of "AAAA..." is a handful of runs)

@@ -1443,778 +1443,136 @@ int tc_decode_stream(tc_ctx *ctx, const uint8_t *stream, uint64_t bytes, uint8_t
     TC_API_END(ctx)
 }
 
-// =============================================================== Data.FMIndex
+// =============================================================== Data.FMIndex (the bodies: tc_fm_host.hpp)
 int tc_fm_build(tc_ctx *ctx, const uint8_t *text, uint64_t n, tc_fm **out) {
     TC_API_BEGIN(ctx)
-    if (!out || n > TC_MAX_N) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    *out = nullptr;
-    if (n == 0) {  // FMIndex.hs:366: empty input => every query returns the empty result
-        tc_fm *fm = new tc_fm();
-        fm->device = ctx->device;
-        *out = fm;
-        return TC_OK;
-    }
-    if (!text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    *out = fm_build_device(ctx, text, n);
+    fm_build_entry(ctx, text, nullptr, n, 1, 0, 0, out);
     TC_API_END(ctx)
 }
 
 int tc_fm_build_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, tc_fm **out) {
     TC_API_BEGIN(ctx)
-    if (!out || n > TC_MAX_N) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    *out = nullptr;
-    if (n == 0) {
-        tc_fm *fm = new tc_fm();
-        fm->device = ctx->device;
-        *out = fm;
-        return TC_OK;
-    }
-    if (!d_text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    *out = fm_build_device(ctx, nullptr, n, d_text);
+    fm_build_entry(ctx, nullptr, d_text, n, 1, 0, 0, out);
     TC_API_END(ctx)
 }
 
-static inline bool fm_rate_ok(u32 r) { return r >= 1 && r <= TC_FM_MAX_SA_RATE && (r & (r - 1)) == 0; }
-
 int tc_fm_build_sampled(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sa_rate, tc_fm **out) {
     TC_API_BEGIN(ctx)
-    if (out) *out = nullptr;
-    if (!out || n > TC_MAX_N || !fm_rate_ok(sa_rate)) TC_FAIL(ctx, TC_ERR_ARG, "bad argument (sa_rate: a power of two, 1 .. %d)", TC_FM_MAX_SA_RATE);
-    if (n == 0) {
-        tc_fm *fm = new tc_fm();
-        fm->device = ctx->device;
-        *out = fm;
-        return TC_OK;
-    }
-    if (!text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    *out = fm_build_device(ctx, text, n, nullptr, sa_rate);
+    fm_build_entry(ctx, text, nullptr, n, sa_rate, 0, 1, out);
     TC_API_END(ctx)
 }
 
 int tc_fm_build_sampled_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t sa_rate, tc_fm **out) {
     TC_API_BEGIN(ctx)
-    if (out) *out = nullptr;
-    if (!out || n > TC_MAX_N || !fm_rate_ok(sa_rate)) TC_FAIL(ctx, TC_ERR_ARG, "bad argument (sa_rate: a power of two, 1 .. %d)", TC_FM_MAX_SA_RATE);
-    if (n == 0) {
-        tc_fm *fm = new tc_fm();
-        fm->device = ctx->device;
-        *out = fm;
-        return TC_OK;
-    }
-    if (!d_text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    *out = fm_build_device(ctx, nullptr, n, d_text, sa_rate);
+    fm_build_entry(ctx, nullptr, d_text, n, sa_rate, 0, 1, out);
     TC_API_END(ctx)
 }
 
 int tc_fm_build_self(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, tc_fm **out) {
     TC_API_BEGIN(ctx)
-    if (out) *out = nullptr;
-    if (!out || n > TC_MAX_N || !fm_rate_ok(sa_rate) || !fm_rate_ok(text_rate))
-        TC_FAIL(ctx, TC_ERR_ARG, "bad argument (sa_rate, text_rate: powers of two, 1 .. %d)", TC_FM_MAX_SA_RATE);
-    if (n == 0) {
-        tc_fm *fm = new tc_fm();
-        fm->device = ctx->device;
-        *out = fm;
-        return TC_OK;
-    }
-    if (!text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    *out = fm_build_device(ctx, text, n, nullptr, sa_rate, text_rate);
+    fm_build_entry(ctx, text, nullptr, n, sa_rate, text_rate, 2, out);
     TC_API_END(ctx)
 }
 
 int tc_fm_build_self_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, tc_fm **out) {
     TC_API_BEGIN(ctx)
-    if (out) *out = nullptr;
-    if (!out || n > TC_MAX_N || !fm_rate_ok(sa_rate) || !fm_rate_ok(text_rate))
-        TC_FAIL(ctx, TC_ERR_ARG, "bad argument (sa_rate, text_rate: powers of two, 1 .. %d)", TC_FM_MAX_SA_RATE);
-    if (n == 0) {
-        tc_fm *fm = new tc_fm();
-        fm->device = ctx->device;
-        *out = fm;
-        return TC_OK;
-    }
-    if (!d_text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    *out = fm_build_device(ctx, nullptr, n, d_text, sa_rate, text_rate);
+    fm_build_entry(ctx, nullptr, d_text, n, sa_rate, text_rate, 2, out);
     TC_API_END(ctx)
 }
 
 uint32_t tc_fm_sa_rate(const tc_fm *fm) { return fm ? fm->sa_rate : 0; }
 uint32_t tc_fm_text_rate(const tc_fm *fm) { return fm ? fm->text_rate : 0; }
-
-uint64_t tc_fm_device_bytes(const tc_fm *fm, int part) {
-    if (!fm || fm->n == 0 || part < 0 || part > 2) return 0;
-    const u64 ext = fm->text_rate ? fm->nisa * sizeof(u32) : 0;
-    if (part == 2) return ext;
-    u64 loc = 0;
-    if (fm->sa_rate == 1) loc = (fm->N + 16) + fm->N * sizeof(u32);
-    else if (fm->sa_rate > 1) loc = (fm->N + 16) + fm->lines * 64 + fm->nsamples * sizeof(u32);
-    if (part == 1) return loc;
-    u64 b = loc + ext + 768 * sizeof(u32) + (u64)fm->sigma_bytes * fm->lines * 64;
-    if (fm->d_bits2) b += (u64)fm->sigma_bytes * fm->sigma_bytes * fm->lines * 64 + FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32);
-    return b;
-}
-
+uint64_t tc_fm_device_bytes(const tc_fm *fm, int part) { return fm_device_bytes(fm, part); }
 void tc_fm_free(tc_fm *fm) { fm_release(fm); }
 
-// ---- the index as one device byte string (replication over the GPUs of a node) ----------------
-struct FmWire {
-    char magic[8];   // "TCFMI02\0"
-    u64 n, N, primary, lines, bytes;
-    u32 sigma_bytes, with_locate;   // with_locate: bit 0 = the locate part follows; bits 8.. = text_rate of the text samples
-                                    // that follow the locate part (0: none -- an index without them writes 0 or 1 as ever)
-    u32 with_pairs, sa_rate;    // 1: the pair vectors (sigma_bytes^2 of them) follow the per-byte vectors.  sa_rate (the word was
-                                // reserved = 0 before sampled indexes): 0 or 1 = the locate part is L + the full suffix array;
-                                // k > 1 = L + marks + samples (a full index writes 0: its export is what it always was)
-    u32 counts[256];
-    i16 sym_of_code[256];
-};
-static const char kFmMagic[8] = {'T', 'C', 'F', 'M', 'I', '0', '2', 0};
-static inline u64 fm_wire_align(u64 v) { return (v + 255) & ~(u64)255; }
-static u64 fm_wire_bytes(const tc_fm *fm, int with_locate) {
-    u64 b = fm_wire_align(sizeof(FmWire));
-    if (fm->n == 0) return b;
-    b += fm_wire_align((u64)fm->sigma_bytes * fm->lines * 64);
-    if (fm->d_bits2) b += fm_wire_align((u64)fm->sigma_bytes * fm->sigma_bytes * fm->lines * 64);
-    if (with_locate && fm->sa_rate > 1)
-        b += fm_wire_align(fm->N + 16) + fm_wire_align(fm->lines * 64) + fm_wire_align(fm->nsamples * sizeof(u32));
-    else if (with_locate) b += fm_wire_align(fm->N + 16) + fm_wire_align(fm->N * sizeof(u32));
-    if (with_locate && fm->text_rate) b += fm_wire_align(fm->nisa * sizeof(u32));
-    return b;
-}
-
-uint64_t tc_fm_export_bound(const tc_fm *fm, int with_locate) { return fm ? fm_wire_bytes(fm, with_locate) : 0; }
+uint64_t tc_fm_export_bound(const tc_fm *fm, int with_locate) { return fm_export_bound(fm, with_locate); }
 
 int tc_fm_export_dev(tc_ctx *ctx, const tc_fm *fm, int with_locate, uint8_t *d_out, uint64_t *bytes) {
     TC_API_BEGIN(ctx)
-    if (!fm || !bytes) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    const u64 need = fm_wire_bytes(fm, with_locate), cap = *bytes;
-    *bytes = need;
-    if (cap < need) TC_FAIL(ctx, TC_ERR_CAPACITY, "index export needs %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    if (!d_out || ((uintptr_t)d_out & 15)) TC_FAIL(ctx, TC_ERR_ARG, "export buffer must be 16-byte aligned");
-    FmWire h = {};
-    memcpy(h.magic, kFmMagic, 8);
-    h.n = fm->n; h.N = fm->N; h.primary = fm->primary; h.lines = fm->lines; h.bytes = need;
-    h.sigma_bytes = fm->sigma_bytes; h.with_locate = (fm->n && with_locate) ? (1u | fm->text_rate << 8) : 0u;
-    h.with_pairs = fm->d_bits2 ? 1u : 0u;
-    h.sa_rate = (h.with_locate && fm->sa_rate > 1) ? fm->sa_rate : 0u;
-    memcpy(h.counts, fm->counts, sizeof h.counts);
-    memcpy(h.sym_of_code, fm->sym_of_code, sizeof h.sym_of_code);
-    hipStream_t s = ctx->stream;
-    TC_HIP(ctx, hipMemcpyAsync(d_out, &h, sizeof h, hipMemcpyHostToDevice, s));
-    u64 o = fm_wire_align(sizeof(FmWire));
-    if (fm->n) {
-        const u64 bb = (u64)fm->sigma_bytes * fm->lines * 64;
-        TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_bits, bb, hipMemcpyDeviceToDevice, s));
-        o += fm_wire_align(bb);
-        if (fm->d_bits2) {
-            TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_bits2, bb * fm->sigma_bytes, hipMemcpyDeviceToDevice, s));
-            o += fm_wire_align(bb * fm->sigma_bytes);
-        }
-        if (with_locate) {
-            TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_L, fm->N, hipMemcpyDeviceToDevice, s));
-            o += fm_wire_align(fm->N + 16);
-            if (fm->sa_rate > 1) {
-                TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_marks, fm->lines * 64, hipMemcpyDeviceToDevice, s));
-                o += fm_wire_align(fm->lines * 64);
-                TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_samples, fm->nsamples * sizeof(u32), hipMemcpyDeviceToDevice, s));
-                o += fm_wire_align(fm->nsamples * sizeof(u32));
-            } else {
-                TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_sa, fm->N * sizeof(u32), hipMemcpyDeviceToDevice, s));
-                o += fm_wire_align(fm->N * sizeof(u32));
-            }
-            if (fm->text_rate)
-                TC_HIP(ctx, hipMemcpyAsync(d_out + o, fm->d_isa, fm->nisa * sizeof(u32), hipMemcpyDeviceToDevice, s));
-        }
-    }
-    TC_HIP(ctx, hipStreamSynchronize(s));   // h is a stack object
+    fm_export_device(ctx, fm, with_locate, d_out, bytes);
     TC_API_END(ctx)
 }
 
 int tc_fm_import_dev(tc_ctx *ctx, const uint8_t *d_in, uint64_t bytes, tc_fm **out) {
     TC_API_BEGIN(ctx)
-    if (!out || !d_in || bytes < sizeof(FmWire)) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    *out = nullptr;
-    FmWire h;
-    hipStream_t s = ctx->stream;
-    TC_HIP(ctx, hipMemcpyAsync(&h, d_in, sizeof h, hipMemcpyDeviceToHost, s));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    if (memcmp(h.magic, "TCFMI0", 6) == 0 && memcmp(h.magic, kFmMagic, 8) != 0)   // (an export of another build: the layout changed)
-        TC_FAIL(ctx, TC_ERR_MALFORMED, "unsupported FM export version %.7s (this build reads %s: an export travels between ranks of one build, it is not an archive format)", h.magic, kFmMagic);
-    if (memcmp(h.magic, kFmMagic, 8) != 0 || h.bytes > bytes || h.N != (h.n ? h.n + 1 : 0) || h.n > TC_MAX_N ||
-        h.sigma_bytes > 256 || (h.n && h.lines != h.N / FM_LINE_BITS + 1))
-        TC_FAIL(ctx, TC_ERR_MALFORMED, "not an exported FM-index");
-    {   // the scalars fm_count / fm_locate index with: primary row, symbol counts, code table
-        u64 total = 0;
-        u32 present = 0;
-        bool codes_ok = true;
-        for (int b = 0; b < 256; b++) {
-            total += h.counts[b];
-            if (h.counts[b]) {
-                codes_ok = codes_ok && present < h.sigma_bytes && h.sym_of_code[present] == (i16)b;
-                present++;
-            }
-        }
-        if (h.n && (h.primary == 0 || h.primary >= h.N || total != h.n || present != h.sigma_bytes || !codes_ok))
-            TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: header is inconsistent");
-    }
-    if (h.with_pairs > 1 || (h.with_pairs && (h.sigma_bytes > FM_PAIR_SIGMA || h.n < 2)))
-        TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: header is inconsistent");
-    // the sampling rate rides in the word that was reserved: 0 or 1 = full suffix array; otherwise a power of two within range,
-    // and only where there is a locate part
-    // the text samples' rate rides above bit 7 of the with_locate word: 0 = none; otherwise a power of two within range, and
-    // only behind a locate part
-    const bool wire_locate = (h.with_locate & 0xffu) != 0;
-    const u32 wire_text_rate = h.with_locate >> 8;
-    const bool wire_sampled = h.sa_rate > 1;
-    if (wire_sampled && (!fm_rate_ok(h.sa_rate) || !wire_locate || !h.n))
-        TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: bad suffix-array sampling rate %u", h.sa_rate);
-    if (wire_text_rate && (!fm_rate_ok(wire_text_rate) || (h.with_locate & 0xffu) != 1 || !h.n))
-        TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: bad text sampling rate %u", wire_text_rate);
-    tc_fm *fm = new tc_fm();
-    fm->device = ctx->device;
-    fm->n = h.n; fm->N = h.N; fm->primary = h.primary; fm->lines = h.lines; fm->sigma_bytes = h.sigma_bytes;
-    memcpy(fm->counts, h.counts, sizeof h.counts);
-    memcpy(fm->sym_of_code, h.sym_of_code, sizeof h.sym_of_code);
-    try {
-        if (fm->n) {
-            const u64 bb = (u64)fm->sigma_bytes * fm->lines * 64;
-            u64 need = fm_wire_align(sizeof(FmWire)) + fm_wire_align(bb);
-            if (h.with_pairs) need += fm_wire_align(bb * fm->sigma_bytes);
-            if (wire_sampled) {
-                fm->nsamples = fm->n / h.sa_rate + 1;
-                need += fm_wire_align(fm->N + 16) + fm_wire_align(fm->lines * 64) + fm_wire_align(fm->nsamples * sizeof(u32));
-            } else if (wire_locate) {
-                need += fm_wire_align(fm->N + 16) + fm_wire_align(fm->N * sizeof(u32));
-            }
-            if (wire_text_rate) {
-                fm->nisa = fm->n / wire_text_rate + 1;
-                need += fm_wire_align(fm->nisa * sizeof(u32));
-            }
-            if (need != h.bytes) TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: size mismatch");
-            u32 tab[768];
-            (void)fm_make_tab(fm->counts, tab, nullptr);
-            TC_HIP(ctx, hipMalloc((void **)&fm->d_tab, 768 * sizeof(u32)));
-            TC_HIP(ctx, hipMalloc((void **)&fm->d_bits, bb));
-            TC_HIP(ctx, hipMemcpyAsync(fm->d_tab, tab, sizeof tab, hipMemcpyHostToDevice, s));
-            TC_HIP(ctx, hipStreamSynchronize(s));   // tab is a stack buffer
-            u64 o = fm_wire_align(sizeof(FmWire));
-            TC_HIP(ctx, hipMemcpyAsync(fm->d_bits, d_in + o, bb, hipMemcpyDeviceToDevice, s));
-            o += fm_wire_align(bb);
-            if (h.with_pairs) {
-                TC_HIP(ctx, hipMalloc((void **)&fm->d_tab2, FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32)));
-                TC_HIP(ctx, hipMalloc((void **)&fm->d_bits2, bb * fm->sigma_bytes));
-                TC_HIP(ctx, hipMemsetAsync(fm->d_tab2, 0, FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32), s));
-                TC_HIP(ctx, hipMemcpyAsync(fm->d_bits2, d_in + o, bb * fm->sigma_bytes, hipMemcpyDeviceToDevice, s));
-                o += fm_wire_align(bb * fm->sigma_bytes);
-                fm_c2_kernel<<<1, 64, 0, s>>>(fm->d_bits, fm->lines, fm->d_tab, fm->sigma_bytes, fm->d_tab2);
-                TC_LAUNCH_CHECK(ctx);
-            }
-            if (wire_sampled) {
-                TC_HIP(ctx, hipMalloc((void **)&fm->d_L, fm->N + 16));
-                TC_HIP(ctx, hipMalloc((void **)&fm->d_marks, fm->lines * 64));
-                TC_HIP(ctx, hipMalloc((void **)&fm->d_samples, fm->nsamples * sizeof(u32)));
-                TC_HIP(ctx, hipMemsetAsync(fm->d_L + fm->N, 0, 16, s));
-                TC_HIP(ctx, hipMemcpyAsync(fm->d_L, d_in + o, fm->N, hipMemcpyDeviceToDevice, s));
-                o += fm_wire_align(fm->N + 16);
-                TC_HIP(ctx, hipMemcpyAsync(fm->d_marks, d_in + o, fm->lines * 64, hipMemcpyDeviceToDevice, s));
-                o += fm_wire_align(fm->lines * 64);
-                TC_HIP(ctx, hipMemcpyAsync(fm->d_samples, d_in + o, fm->nsamples * sizeof(u32), hipMemcpyDeviceToDevice, s));
-                // what only the device can check: the marks hold exactly one bit per sample (the walk bounds everything else)
-                unsigned long long *d_ones = reinterpret_cast<unsigned long long *>(ctx->d_scalars + 10);
-                TC_HIP(ctx, hipMemsetAsync(d_ones, 0, sizeof(u64), s));
-                u32 grid = tc_cdiv(fm->lines * 8, 256 * 16);
-                if (grid > 4096) grid = 4096;
-                fm_popcount_kernel<<<grid, 256, 0, s>>>(fm->d_marks, fm->lines, d_ones);
-                TC_LAUNCH_CHECK(ctx);
-                TC_HIP(ctx, hipMemcpyAsync(&ctx->h_scalars[10], d_ones, sizeof(u64), hipMemcpyDeviceToHost, s));
-                TC_HIP(ctx, hipStreamSynchronize(s));
-                if (ctx->h_scalars[10] != fm->nsamples)
-                    TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: %llu rows are marked as sampled, %llu samples follow",
-                            (unsigned long long)ctx->h_scalars[10], (unsigned long long)fm->nsamples);
-                o += fm_wire_align(fm->nsamples * sizeof(u32));
-                fm->sa_rate = h.sa_rate;
-            } else if (wire_locate) {
-                TC_HIP(ctx, hipMalloc((void **)&fm->d_L, fm->N + 16));
-                TC_HIP(ctx, hipMalloc((void **)&fm->d_sa, fm->N * sizeof(u32)));
-                TC_HIP(ctx, hipMemcpyAsync(fm->d_L, d_in + o, fm->N, hipMemcpyDeviceToDevice, s));
-                o += fm_wire_align(fm->N + 16);
-                TC_HIP(ctx, hipMemcpyAsync(fm->d_sa, d_in + o, fm->N * sizeof(u32), hipMemcpyDeviceToDevice, s));
-                o += fm_wire_align(fm->N * sizeof(u32));
-                fm->sa_rate = 1;
-            }
-            if (wire_text_rate) {
-                TC_HIP(ctx, hipMalloc((void **)&fm->d_isa, fm->nisa * sizeof(u32)));
-                TC_HIP(ctx, hipMemcpyAsync(fm->d_isa, d_in + o, fm->nisa * sizeof(u32), hipMemcpyDeviceToDevice, s));
-                // what only the device can check: every sample is a row, and position 0 is the primary row's (the walk bounds
-                // everything else)
-                u32 *d_res = reinterpret_cast<u32 *>(ctx->d_scalars + 10);
-                TC_HIP(ctx, hipMemsetAsync(d_res, 0, sizeof(u64), s));
-                u32 grid = tc_cdiv(fm->nisa, 256 * 16);
-                if (grid > 4096) grid = 4096;
-                fm_isa_max_kernel<<<grid, 256, 0, s>>>(fm->d_isa, fm->nisa, d_res);
-                TC_LAUNCH_CHECK(ctx);
-                TC_HIP(ctx, hipMemcpyAsync(&ctx->h_scalars[10], d_res, sizeof(u64), hipMemcpyDeviceToHost, s));
-                TC_HIP(ctx, hipStreamSynchronize(s));
-                const u64 isa_max = ctx->h_scalars[10] & 0xffffffffu, isa0 = ctx->h_scalars[10] >> 32;
-                if (isa_max >= fm->N || isa0 != fm->primary)
-                    TC_FAIL(ctx, TC_ERR_MALFORMED, "exported FM-index: text samples out of range (largest row %llu of %llu, position 0 at row %llu, primary row %llu)",
-                            (unsigned long long)isa_max, (unsigned long long)fm->N, (unsigned long long)isa0, (unsigned long long)fm->primary);
-                fm->text_rate = wire_text_rate;
-            }
-            TC_HIP(ctx, hipStreamSynchronize(s));
-        }
-    } catch (...) {
-        fm_release(fm);
-        throw;
-    }
-    *out = fm;
+    fm_import_device(ctx, d_in, bytes, out);
     TC_API_END(ctx)
 }
 
 int tc_fm_count_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs,
                     uint64_t npat, int64_t *d_out) {
     TC_API_BEGIN(ctx)
-    if (!fm) TC_FAIL(ctx, TC_ERR_ARG, "null index");
-    if (npat == 0) return TC_OK;
-    if (!d_pats || !d_offs || !d_out) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    if (fm->n == 0) {
-        tc_memset_async(ctx, d_out, 0, npat * sizeof(i64));
-    } else {
-        fm_count_device(ctx, fm, d_pats, d_offs, npat, d_out, nullptr);
-    }
-    tc_sync_check(ctx);
+    fm_count_entry(ctx, fm, d_pats, d_offs, npat, true, 0, d_out, true);
     TC_API_END(ctx)
 }
 
 int tc_fm_count(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs,
                 uint64_t npat, int64_t *out) {
     TC_API_BEGIN(ctx)
-    if (!fm) TC_FAIL(ctx, TC_ERR_ARG, "null index");
-    if (npat == 0) return TC_OK;
-    if (!pats || !offs || !out) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    if (fm->n == 0) {
-        memset(out, 0, npat * sizeof(i64));
-        return TC_OK;
-    }
-    const u64 total = offs[npat];
-    u8 *d_pats = nullptr;
-    u64 *d_offs = nullptr;
-    i64 *d_out = nullptr;
-    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
-        d_pats = A.get<u8>(total + 16);
-        d_offs = A.get<u64>(npat + 1);
-        d_out = A.get<i64>(npat);
-    });
-    tc_h2d(ctx, d_pats, pats, total);
-    tc_h2d(ctx, d_offs, offs, (npat + 1) * sizeof(u64));
-    fm_count_device(ctx, fm, d_pats, d_offs, npat, d_out, nullptr);
-    tc_d2h(ctx, out, d_out, npat * sizeof(i64));
-    tc_sync_check(ctx);
+    fm_count_entry(ctx, fm, pats, offs, npat, true, 0, out, false);
     TC_API_END(ctx)
-}
-
-// scratch of one locate batch besides patterns and results
-struct FmLocateScratch {
-    i64 *d_cnt = nullptr;
-    u64 *d_ranges = nullptr, *d_len = nullptr, *d_tsum = nullptr;
-    u64 tiles = 0;
-    void carve(Arena &A, u64 npat) {
-        tiles = tc_cdiv(npat, SCAN_TILE);
-        d_cnt = A.get<i64>(npat);
-        d_ranges = A.get<u64>(2 * npat);
-        d_len = A.get<u64>(npat + 1);
-        d_tsum = A.get<u64>(tiles + 2);
-    }
-};
-
-// everything on the device: ranges, hit offsets (d_hoffs[0 .. npat); the total is returned), then the hits -- from the suffix
-// array (a full index: the table lookup) or as rows walked to positions (a sampled one).  Returns the total; when it exceeds
-// cap nothing is written to d_hits.  The caller synchronises (tc_sync_check: the walk's bounds raise the device error word).
-static u64 fm_locate_device(tc_ctx *ctx, const tc_fm *fm, const FmLocateScratch &W, const u8 *d_pats, const u64 *d_offs,
-                            u64 npat, u64 *d_hoffs, u64 *d_hits, u64 cap) {
-    hipStream_t s = ctx->stream;
-    const u64 tiles = W.tiles;
-    fm_count_device(ctx, fm, d_pats, d_offs, npat, W.d_cnt, W.d_ranges);
-    fm_cnt_to_u64_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(W.d_cnt, npat, W.d_len);
-    TC_LAUNCH_CHECK(ctx);
-    scan64_reduce_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(W.d_len, npat, W.d_tsum);
-    TC_LAUNCH_CHECK(ctx);
-    scan64_spine_kernel<<<1, 1024, 0, s>>>(W.d_tsum, tiles);
-    TC_LAUNCH_CHECK(ctx);
-    scan64_down_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(W.d_len, npat, W.d_tsum, d_hoffs);
-    TC_LAUNCH_CHECK(ctx);
-    tc_d2h(ctx, &ctx->h_scalars[9], W.d_tsum + tiles, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 need = ctx->h_scalars[9];
-    if (need > cap) return need;
-    if (fm->sa_rate > 1) {
-        fm_locate_rows_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(W.d_ranges, d_hoffs, npat, cap, d_hits);
-        TC_LAUNCH_CHECK(ctx);
-        if (need) {
-            fm_locate_walk_kernel<<<tc_cdiv(need, 256), 256, 0, s>>>(fm->d_bits, fm->d_marks, fm->lines, fm->d_tab,
-                                                                    fm->sigma_bytes, fm->d_L, fm->d_samples, fm->nsamples,
-                                                                    fm->N, fm->primary, fm->sa_rate, need, d_hits,
-                                                                    ctx->d_err);
-            TC_LAUNCH_CHECK(ctx);
-        }
-    } else {
-        fm_locate_fill_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(W.d_ranges, d_hoffs, fm->d_sa, npat, cap, d_hits);
-        TC_LAUNCH_CHECK(ctx);
-    }
-    return need;
 }
 
 int tc_fm_locate(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs,
                  uint64_t npat, uint64_t *hit_offs, uint64_t *hits, uint64_t *nhits) {
     TC_API_BEGIN(ctx)
-    if (!fm || !nhits) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    const u64 cap = *nhits;
-    *nhits = 0;
-    if (npat == 0) return TC_OK;
-    if (!pats || !offs || !hit_offs || (!hits && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    if (fm->n == 0) {
-        memset(hit_offs, 0, (npat + 1) * sizeof(u64));
-        return TC_OK;
-    }
-    if (!fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
-    const u64 total = offs[npat];
-    u8 *d_pats = nullptr;
-    u64 *d_offs = nullptr, *d_hoffs = nullptr, *d_hits = nullptr;
-    FmLocateScratch W;
-    auto carve = [&](Arena &A, bool) {
-        d_pats = A.get<u8>(total + 16);
-        d_offs = A.get<u64>(npat + 1);
-        W.carve(A, npat);
-        d_hoffs = A.get<u64>(npat + 1);
-        d_hits = A.get<u64>(cap + 1);
-    };
-    tc_ws_plan(ctx, 0, carve);
-    tc_h2d(ctx, d_pats, pats, total);
-    tc_h2d(ctx, d_offs, offs, (npat + 1) * sizeof(u64));
-    const u64 need = fm_locate_device(ctx, fm, W, d_pats, d_offs, npat, d_hoffs, d_hits, cap);
-    *nhits = need;
-    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu hit slots, have %llu",
-                            (unsigned long long)need, (unsigned long long)cap);
-    tc_d2h(ctx, hit_offs, d_hoffs, npat * sizeof(u64));
-    if (need) tc_d2h(ctx, hits, d_hits, need * sizeof(u64));
-    tc_sync_check(ctx);
-    hit_offs[npat] = need;
+    fm_locate_entry(ctx, fm, pats, offs, npat, true, 0, hit_offs, hits, nullptr, nhits, false);
     TC_API_END(ctx)
 }
 
 int tc_fm_locate_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs,
                      uint64_t npat, uint64_t *d_hit_offs, uint64_t *d_hits, uint64_t *nhits) {
     TC_API_BEGIN(ctx)
-    if (!fm || !nhits) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    const u64 cap = *nhits;
-    *nhits = 0;
-    if (npat == 0) return TC_OK;
-    if (!d_pats || !d_offs || !d_hit_offs || (!d_hits && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    if (fm->n == 0) {
-        tc_memset_async(ctx, d_hit_offs, 0, (npat + 1) * sizeof(u64));
-        tc_sync_check(ctx);
-        return TC_OK;
-    }
-    if (!fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
-    FmLocateScratch W;
-    tc_ws_plan(ctx, 0, [&](Arena &A, bool) { W.carve(A, npat); });
-    const u64 need = fm_locate_device(ctx, fm, W, d_pats, d_offs, npat, d_hit_offs, d_hits, cap);
-    *nhits = need;
-    TC_HIP(ctx, hipMemcpyAsync(d_hit_offs + npat, W.d_tsum + W.tiles, sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
-    if (need > cap) {
-        TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu hit slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    }
-    tc_sync_check(ctx);
+    fm_locate_entry(ctx, fm, d_pats, d_offs, npat, true, 0, d_hit_offs, d_hits, nullptr, nhits, true);
     TC_API_END(ctx)
 }
 
-// ---- search with mismatches (tc_fm_count_mm / tc_fm_locate_mm; the kernel: tc_fm_mm.hpp) ---------------------------------
-static_assert(TC_FM_MAX_MISMATCH == FM_MM_MAXK, "fm_mm_kernel keeps TC_FM_MAX_MISMATCH frames per lane");
-
+// ---- search with mismatches (the kernel: tc_fm_mm.hpp) ---------------------------------
 int tc_fm_count_mm_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint32_t k,
                        int64_t *d_out) {
     TC_API_BEGIN(ctx)
-    if (!fm) TC_FAIL(ctx, TC_ERR_ARG, "null index");
-    if (k > TC_FM_MAX_MISMATCH) TC_FAIL(ctx, TC_ERR_ARG, "k = %u mismatches (at most %d)", k, TC_FM_MAX_MISMATCH);
-    if (npat == 0) return TC_OK;
-    if (!d_pats || !d_offs || !d_out) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    if (fm->n == 0) {
-        tc_memset_async(ctx, d_out, 0, npat * sizeof(i64));
-    } else {
-        fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, d_out, nullptr, nullptr, nullptr);
-    }
-    tc_sync_check(ctx);
+    fm_count_entry(ctx, fm, d_pats, d_offs, npat, false, k, d_out, true);
     TC_API_END(ctx)
 }
 
 int tc_fm_count_mm(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat, uint32_t k,
                    int64_t *out) {
     TC_API_BEGIN(ctx)
-    if (!fm) TC_FAIL(ctx, TC_ERR_ARG, "null index");
-    if (k > TC_FM_MAX_MISMATCH) TC_FAIL(ctx, TC_ERR_ARG, "k = %u mismatches (at most %d)", k, TC_FM_MAX_MISMATCH);
-    if (npat == 0) return TC_OK;
-    if (!pats || !offs || !out) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    if (fm->n == 0) {
-        memset(out, 0, npat * sizeof(i64));
-        return TC_OK;
-    }
-    const u64 total = offs[npat];
-    u8 *d_pats = nullptr;
-    u64 *d_offs = nullptr;
-    i64 *d_out = nullptr;
-    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
-        d_pats = A.get<u8>(total + 16);
-        d_offs = A.get<u64>(npat + 1);
-        d_out = A.get<i64>(npat);
-    });
-    tc_h2d(ctx, d_pats, pats, total);
-    tc_h2d(ctx, d_offs, offs, (npat + 1) * sizeof(u64));
-    fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, d_out, nullptr, nullptr, nullptr);
-    tc_d2h(ctx, out, d_out, npat * sizeof(i64));
-    tc_sync_check(ctx);
+    fm_count_entry(ctx, fm, pats, offs, npat, false, k, out, false);
     TC_API_END(ctx)
-}
-
-// scratch of one locate-with-mismatches batch besides patterns and results
-struct FmMmScratch {
-    i64 *d_cnt = nullptr;
-    u64 *d_len = nullptr, *d_tsum = nullptr;
-    u64 tiles = 0;
-    void carve(Arena &A, u64 npat) {
-        tiles = tc_cdiv(npat, SCAN_TILE);
-        d_cnt = A.get<i64>(npat);
-        d_len = A.get<u64>(npat + 1);
-        d_tsum = A.get<u64>(tiles + 2);
-    }
-};
-
-// fm_locate_device for the search with mismatches: the count pass, the scan of the counts (d_hoffs[0 .. npat]; the total is
-// returned), then -- when the total fits -- the fill pass, which repeats the enumeration and writes positions (a full index)
-// or rows that the walk then turns into positions (a sampled one), and the distances to d_mm (may be null).  When the total
-// exceeds cap nothing is written to d_hits or d_mm.  The caller synchronises (tc_sync_check).
-static u64 fm_locate_mm_device(tc_ctx *ctx, const tc_fm *fm, const FmMmScratch &W, const u8 *d_pats, const u64 *d_offs,
-                               u64 npat, u32 k, u64 *d_hoffs, u64 *d_hits, u8 *d_mm, u64 cap) {
-    hipStream_t s = ctx->stream;
-    const u64 tiles = W.tiles;
-    fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, W.d_cnt, nullptr, nullptr, nullptr);
-    fm_cnt_to_u64_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(W.d_cnt, npat, W.d_len);
-    TC_LAUNCH_CHECK(ctx);
-    scan64_reduce_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(W.d_len, npat, W.d_tsum);
-    TC_LAUNCH_CHECK(ctx);
-    scan64_spine_kernel<<<1, 1024, 0, s>>>(W.d_tsum, tiles);
-    TC_LAUNCH_CHECK(ctx);
-    scan64_down_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(W.d_len, npat, W.d_tsum, d_hoffs);
-    TC_LAUNCH_CHECK(ctx);
-    TC_HIP(ctx, hipMemcpyAsync(d_hoffs + npat, W.d_tsum + tiles, sizeof(u64), hipMemcpyDeviceToDevice, s));
-    tc_d2h(ctx, &ctx->h_scalars[9], W.d_tsum + tiles, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 need = ctx->h_scalars[9];
-    if (need > cap || need == 0) return need;
-    fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, nullptr, d_hoffs, d_hits, d_mm);
-    if (fm->sa_rate > 1) {
-        fm_locate_walk_kernel<<<tc_cdiv(need, 256), 256, 0, s>>>(fm->d_bits, fm->d_marks, fm->lines, fm->d_tab, fm->sigma_bytes,
-                                                                fm->d_L, fm->d_samples, fm->nsamples, fm->N, fm->primary,
-                                                                fm->sa_rate, need, d_hits, ctx->d_err);
-        TC_LAUNCH_CHECK(ctx);
-    }
-    return need;
 }
 
 int tc_fm_locate_mm(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat, uint32_t k,
                     uint64_t *hit_offs, uint64_t *hits, uint8_t *hit_mm, uint64_t *nhits) {
     TC_API_BEGIN(ctx)
-    if (!fm || !nhits) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    const u64 cap = *nhits;
-    *nhits = 0;
-    if (k > TC_FM_MAX_MISMATCH) TC_FAIL(ctx, TC_ERR_ARG, "k = %u mismatches (at most %d)", k, TC_FM_MAX_MISMATCH);
-    if (npat == 0) return TC_OK;
-    if (!pats || !offs || !hit_offs || (!hits && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    if (fm->n == 0) {
-        memset(hit_offs, 0, (npat + 1) * sizeof(u64));
-        return TC_OK;
-    }
-    if (!fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
-    const u64 total = offs[npat];
-    u8 *d_pats = nullptr, *d_mm = nullptr;
-    u64 *d_offs = nullptr, *d_hoffs = nullptr, *d_hits = nullptr;
-    FmMmScratch W;
-    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
-        d_pats = A.get<u8>(total + 16);
-        d_offs = A.get<u64>(npat + 1);
-        W.carve(A, npat);
-        d_hoffs = A.get<u64>(npat + 1);
-        d_hits = A.get<u64>(cap + 1);
-        d_mm = hit_mm ? A.get<u8>(cap + 16) : nullptr;
-    });
-    tc_h2d(ctx, d_pats, pats, total);
-    tc_h2d(ctx, d_offs, offs, (npat + 1) * sizeof(u64));
-    const u64 need = fm_locate_mm_device(ctx, fm, W, d_pats, d_offs, npat, k, d_hoffs, d_hits, d_mm, cap);
-    *nhits = need;
-    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu hit slots, have %llu",
-                            (unsigned long long)need, (unsigned long long)cap);
-    tc_d2h(ctx, hit_offs, d_hoffs, (npat + 1) * sizeof(u64));
-    if (need) tc_d2h(ctx, hits, d_hits, need * sizeof(u64));
-    if (need && hit_mm) tc_d2h(ctx, hit_mm, d_mm, need);
-    tc_sync_check(ctx);
+    fm_locate_entry(ctx, fm, pats, offs, npat, false, k, hit_offs, hits, hit_mm, nhits, false);
     TC_API_END(ctx)
 }
 
 int tc_fm_locate_mm_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint32_t k,
                         uint64_t *d_hit_offs, uint64_t *d_hits, uint8_t *d_hit_mm, uint64_t *nhits) {
     TC_API_BEGIN(ctx)
-    if (!fm || !nhits) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    const u64 cap = *nhits;
-    *nhits = 0;
-    if (k > TC_FM_MAX_MISMATCH) TC_FAIL(ctx, TC_ERR_ARG, "k = %u mismatches (at most %d)", k, TC_FM_MAX_MISMATCH);
-    if (npat == 0) return TC_OK;
-    if (!d_pats || !d_offs || !d_hit_offs || (!d_hits && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    if (fm->n == 0) {
-        tc_memset_async(ctx, d_hit_offs, 0, (npat + 1) * sizeof(u64));
-        tc_sync_check(ctx);
-        return TC_OK;
-    }
-    if (!fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
-    FmMmScratch W;
-    tc_ws_plan(ctx, 0, [&](Arena &A, bool) { W.carve(A, npat); });
-    const u64 need = fm_locate_mm_device(ctx, fm, W, d_pats, d_offs, npat, k, d_hit_offs, d_hits, d_hit_mm, cap);
-    *nhits = need;
-    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu hit slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    tc_sync_check(ctx);
+    fm_locate_entry(ctx, fm, d_pats, d_offs, npat, false, k, d_hit_offs, d_hits, d_hit_mm, nhits, true);
     TC_API_END(ctx)
-}
-
-// scratch of one extract batch besides queries and results
-struct FmExtractScratch {
-    u64 *d_len = nullptr, *d_segs = nullptr, *d_soffs = nullptr, *d_tsum_b = nullptr, *d_tsum_s = nullptr;
-    u32 *d_bad = nullptr;
-    u64 tiles = 0;
-    void carve(Arena &A, u64 nq) {
-        tiles = tc_cdiv(nq, SCAN_TILE);
-        d_len = A.get<u64>(nq);
-        d_segs = A.get<u64>(nq);
-        d_soffs = A.get<u64>(nq + 1);
-        d_tsum_b = A.get<u64>(tiles + 2);
-        d_tsum_s = A.get<u64>(tiles + 2);
-        d_bad = A.get<u32>(2);
-    }
-};
-
-// everything on the device: the plan (validation, byte and segment counts, their scans: d_out_offs[0 .. nq], the last entry
-// the total), then -- after the host has seen the flag and the totals -- the walks.  Returns the byte total; a bad query is
-// TC_ERR_ARG, and then, as with a total above cap, nothing is written to d_out.  The caller synchronises (tc_sync_check:
-// the walk's bounds raise the device error word).
-static u64 fm_extract_device(tc_ctx *ctx, const tc_fm *fm, const FmExtractScratch &W, const u64 *d_starts, const u64 *d_lens,
-                             u64 nq, u64 *d_out_offs, u8 *d_out, u64 cap) {
-    hipStream_t s = ctx->stream;
-    const u64 tiles = W.tiles;
-    const u32 lg = fm_log2(fm->text_rate);
-    TC_HIP(ctx, hipMemsetAsync(W.d_bad, 0, 2 * sizeof(u32), s));
-    fm_extract_plan_kernel<<<tc_cdiv(nq, 256), 256, 0, s>>>(d_starts, d_lens, nq, fm->n, lg, W.d_len, W.d_segs, W.d_bad);
-    TC_LAUNCH_CHECK(ctx);
-    const u64 *in[2] = {W.d_len, W.d_segs};
-    u64 *tsum[2] = {W.d_tsum_b, W.d_tsum_s}, *outp[2] = {d_out_offs, W.d_soffs};
-    for (int i = 0; i < 2; i++) {
-        scan64_reduce_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(in[i], nq, tsum[i]);
-        TC_LAUNCH_CHECK(ctx);
-        scan64_spine_kernel<<<1, 1024, 0, s>>>(tsum[i], tiles);
-        TC_LAUNCH_CHECK(ctx);
-        scan64_down_kernel<<<(u32)tiles, SCAN_NT, 0, s>>>(in[i], nq, tsum[i], outp[i]);
-        TC_LAUNCH_CHECK(ctx);
-    }
-    TC_HIP(ctx, hipMemcpyAsync(d_out_offs + nq, W.d_tsum_b + tiles, sizeof(u64), hipMemcpyDeviceToDevice, s));
-    tc_d2h(ctx, &ctx->h_scalars[9], W.d_tsum_b + tiles, sizeof(u64));
-    tc_d2h(ctx, &ctx->h_scalars[8], W.d_tsum_s + tiles, sizeof(u64));
-    tc_d2h(ctx, &ctx->h_scalars[10], W.d_bad, sizeof(u32));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 need = ctx->h_scalars[9], nsegs = ctx->h_scalars[8];
-    if ((u32)ctx->h_scalars[10])
-        TC_FAIL(ctx, TC_ERR_ARG, "extract: a query lies outside the text (start is 1-based: 1 <= start, start - 1 + len <= %llu)",
-                (unsigned long long)fm->n);
-    if (need > cap || nsegs == 0) return need;
-    fm_extract_walk_kernel<<<tc_cdiv(nsegs, 256), 256, 0, s>>>(fm->d_bits, fm->lines, fm->d_tab, fm->sigma_bytes, fm->d_L,
-                                                             fm->d_isa, fm->nisa, fm->N, fm->primary, lg, d_starts, d_lens,
-                                                             W.d_soffs, d_out_offs, nq, nsegs, d_out, ctx->d_err);
-    TC_LAUNCH_CHECK(ctx);
-    return need;
 }
 
 int tc_fm_extract_dev(tc_ctx *ctx, const tc_fm *fm, const uint64_t *d_starts, const uint64_t *d_lens, uint64_t nq,
                       uint64_t *d_out_offs, uint8_t *d_out, uint64_t *nbytes) {
     TC_API_BEGIN(ctx)
-    if (!fm || !nbytes) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    const u64 cap = *nbytes;
-    *nbytes = 0;
-    if (nq == 0) {
-        if (d_out_offs) {
-            tc_memset_async(ctx, d_out_offs, 0, sizeof(u64));
-            tc_sync_check(ctx);
-        }
-        return TC_OK;
-    }
-    if (!fm->text_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index holds no text samples (build it with tc_fm_build_self; an import without the locate part has none)");
-    if (!d_starts || !d_lens || !d_out_offs || (!d_out && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    FmExtractScratch W;
-    tc_ws_plan(ctx, 0, [&](Arena &A, bool) { W.carve(A, nq); });
-    const u64 need = fm_extract_device(ctx, fm, W, d_starts, d_lens, nq, d_out_offs, d_out, cap);
-    *nbytes = need;
-    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    tc_sync_check(ctx);
+    fm_extract_entry(ctx, fm, d_starts, d_lens, nq, d_out_offs, d_out, nbytes, true);
     TC_API_END(ctx)
 }
 
 int tc_fm_extract(tc_ctx *ctx, const tc_fm *fm, const uint64_t *starts, const uint64_t *lens, uint64_t nq,
                   uint64_t *out_offs, uint8_t *out, uint64_t *nbytes) {
     TC_API_BEGIN(ctx)
-    if (!fm || !nbytes) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    const u64 cap = *nbytes;
-    *nbytes = 0;
-    if (nq == 0) {
-        if (out_offs) out_offs[0] = 0;
-        return TC_OK;
-    }
-    if (!fm->text_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index holds no text samples (build it with tc_fm_build_self; an import without the locate part has none)");
-    if (!starts || !lens || !out_offs || (!out && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    u64 *d_starts = nullptr, *d_lens = nullptr, *d_offs = nullptr;
-    u8 *d_out = nullptr;
-    FmExtractScratch W;
-    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
-        d_starts = A.get<u64>(nq);
-        d_lens = A.get<u64>(nq);
-        d_offs = A.get<u64>(nq + 1);
-        W.carve(A, nq);
-        d_out = A.get<u8>(cap + 16);
-    });
-    tc_h2d(ctx, d_starts, starts, nq * sizeof(u64));
-    tc_h2d(ctx, d_lens, lens, nq * sizeof(u64));
-    const u64 need = fm_extract_device(ctx, fm, W, d_starts, d_lens, nq, d_offs, d_out, cap);
-    *nbytes = need;
-    if (need > cap) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    tc_d2h(ctx, out_offs, d_offs, (nq + 1) * sizeof(u64));
-    if (need) tc_d2h(ctx, out, d_out, need);
-    tc_sync_check(ctx);
+    fm_extract_entry(ctx, fm, starts, lens, nq, out_offs, out, nbytes, false);
     TC_API_END(ctx)
 }
 
 int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, uint64_t *c_val,
                uint64_t *primary) {
-    if (!fm) return TC_ERR_ARG;
-    if (N) *N = fm->N;
-    if (primary) *primary = fm->primary;
-    u32 sg = 0;
-    if (fm->n) {  // seqToCc rows: (0, Nothing) first, then every present byte
-        u64 acc = 1;
-        if (c_sym) c_sym[0] = -1;
-        if (c_val) c_val[0] = 0;
-        sg = 1;
-        for (u32 c = 0; c < fm->sigma_bytes; c++, sg++) {
-            if (c_sym) c_sym[sg] = fm->sym_of_code[c];
-            if (c_val) c_val[sg] = acc;
-            acc += fm->counts[fm->sym_of_code[c]];
-        }
-    }
-    if (sigma) *sigma = sg;
-    return TC_OK;
+    return fm_info(fm, N, sigma, c_sym, c_val, primary);
 }
 
 
