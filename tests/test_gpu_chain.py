@@ -1,4 +1,4 @@
-"""The host's chain-round policy (csrc/tc_chain.hpp, tc_encode_host.hpp) at a size where its own trigger fires (2^22 members
+"""The host's chain-round policy (csrc/tc_chain.hpp, tc_sa_plan.hpp: ChainPolicy) at a size where its own trigger fires (2^22 members
 >= 2^20): a periodic text is done in three rounds with ONE chain round; a Fibonacci word -- repetitive, not periodic: the
 chains are short -- makes the chain rounds back off (at most three attempts); a text with a long run of one symbol inside
 random text takes a chain round on SPARSE ranks.  Each result is compared with the same encode without chain rounds

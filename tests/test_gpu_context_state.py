@@ -7,7 +7,7 @@ the last encode alone: the path tests read msd_path, msd_keyonly, seg_rounds, ch
 evidence of which path ran, so no field may survive from an earlier call.
 
 The ticket redo: round 0's radix passes draw XCD-grouped tile tickets; if a look-back spin runs out there, the
-suffix sort is redone with the single counter and the context keeps that mode (csrc/tc_encode_host.hpp,
+suffix sort is redone with the single counter and the context keeps that mode (csrc/tc_sa_host.hpp,
 ticket_check).  TC_DBG_TICKET_TRIP=1 makes the first attempt's check find the flag set, so the redo runs on the
 spent attempt's buffers and counters."""
 import ctypes as C

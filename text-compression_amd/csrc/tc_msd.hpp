@@ -30,7 +30,7 @@
 //                                                                 12 B read, 5 B written
 // A text with a level-3 bucket above MSDF_CAP, or with more than 2^18 suffixes tied beyond the key
 // (repeats, runs), takes the LSD way instead; the host does not even try when the byte entropy or the
-// collision sample say the text is not iid-like (tc_encode_host.hpp).
+// collision sample say the text is not iid-like (tc_sa_plan.hpp: sa_round0_plan).
 #pragma once
 #include "tc_sa.hpp"
 

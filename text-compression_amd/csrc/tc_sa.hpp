@@ -298,7 +298,7 @@ struct GroupArgs {
     u8 *L;
     u32 *out_slot, *out_idx, *out_grp, *out_tpos;  // next active set
     int isa_only;
-    int norank;         // REFINE, the key round (tc_encode_host.hpp): no rank array / table exists yet -- nothing to store, no table rows
+    int norank;         // REFINE, the key round (tc_sa_host.hpp): no rank array / table exists yet -- nothing to store, no table rows
     u64 *status_max, *status_sum;  // look-back granules, [tiles] each
     u32 *ticket;
     u64 *scalars;  // [1] active count
