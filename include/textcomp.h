@@ -447,6 +447,46 @@ int tc_fm_locate_mm(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uin
                     uint64_t *hit_offs, uint64_t *hits, uint8_t *hit_mm, uint64_t *nhits);
 int tc_fm_locate_mm_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint32_t k,
                         uint64_t *d_hit_offs, uint64_t *d_hits, uint8_t *d_hit_mm, uint64_t *nhits);
+/* Factorize: the greedy longest-match parse of patterns against the indexed text, and its inverse (an addition to the
+ * reference's surface, as the sampled locate, extract and the search with mismatches are).  Where tc_fm_count answers 0 for
+ * a pattern that occurs only in pieces, this call names the pieces: it is the seed step of seed-and-extend, and relative
+ * Lempel-Ziv compression of the patterns against the text.  Patterns as in tc_fm_count: pattern j = pats[offs[j] ..
+ * offs[j+1]), result order = pattern order.
+ * THE PARSE runs right to left, the direction backward search extends a match, and is greedy.  For a pattern p of length m
+ * start with j = m and repeat while j > 0: let l be the largest value such that p[j-l .. j) occurs in the text (inside it,
+ * never over its end).  l >= 1: the MATCH factor (pos, len = l), pos the 1-based text position, as tc_fm_locate answers
+ * them, of the occurrence in the first suffix-array row of the phrase's interval -- the occurrence whose text suffix is
+ * lexicographically smallest, the end of the text sorting first; j -= l.  l = 0 (the byte p[j-1] does not occur in the
+ * text): the LITERAL factor (pos = that byte's value, len = 0); j -= 1.  len = 0 is never a match, so it marks literals.
+ * The factors of one pattern are stored in pattern order, left to right: concatenated they give the pattern back.  The
+ * empty pattern has 0 factors.  The answer is fully determined: the same through the host and _dev entries and on a full
+ * and a sampled index of one text.
+ * fac_offs[npat + 1] (out) delimits each pattern's factors inside fac_pos[] / fac_len[]; *nfac: in = capacity of both, out =
+ * total factors.  A capacity that is too small: TC_ERR_CAPACITY, *nfac = the needed total, nothing written to fac_pos or
+ * fac_len.  fac_pos = fac_len = NULL with capacity 0 is the sizes-only form: TC_OK, fac_offs and the total written -- the
+ * factor count of every pattern, a similarity measure on its own.
+ * UNFACTORIZE expands factor lists back to bytes from an index that holds text samples (tc_fm_text_rate > 0): a match is the
+ * text range [pos, pos + len), a literal its byte; unfactorize(factorize(p)) = p for every byte string p, and the text
+ * itself need not be kept.  out_offs[npat + 1], out and *nbytes as in tc_fm_extract (TC_ERR_CAPACITY: the needed total,
+ * nothing written to out).  A bad list -- fac_offs[0] != 0, fac_offs decreasing, a match with pos = 0 or pos - 1 + len > n,
+ * a literal with pos > 255 -- is TC_ERR_ARG with nothing written to out.
+ * ERRORS AND EDGES.  A null index or null buffers: TC_ERR_ARG.  npat = 0: TC_OK.  The empty index: every byte is a literal.
+ * Factorize on an index imported without its locate part: TC_ERR_ARG.  Unfactorize without text samples: TC_ERR_ARG.
+ * The _dev forms take everything in HBM (nfac / nbytes are host words); the host forms are those calls between a copy in and
+ * a copy out.  Scratch comes from the calling ctx: any number of ctxs may use one tc_fm at once.
+ * Cost: one lane per pattern, one dependent random 64-byte line per pattern symbol (per two symbols with pair vectors) plus
+ * about one per factor; the parse runs twice (sizes, then factors), and on a sampled index one locate walk per match factor
+ * follows.  Unfactorize is one flat extract over all factors.  On an IMPORTED index the parse reads caller data: it is
+ * bounded on any bytes (intervals that leave [1, N] count as empty, every turn consumes a byte or closes a phrase), and the
+ * walks answer TC_ERR_MALFORMED as in tc_fm_locate_dev and tc_fm_extract_dev. */
+int tc_fm_factorize(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat,
+                    uint64_t *fac_offs, uint64_t *fac_pos, uint32_t *fac_len, uint64_t *nfac);
+int tc_fm_factorize_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat,
+                        uint64_t *d_fac_offs, uint64_t *d_fac_pos, uint32_t *d_fac_len, uint64_t *nfac);
+int tc_fm_unfactorize(tc_ctx *ctx, const tc_fm *fm, const uint64_t *fac_offs, const uint64_t *fac_pos, const uint32_t *fac_len,
+                      uint64_t npat, uint64_t *out_offs, uint8_t *out, uint64_t *nbytes);
+int tc_fm_unfactorize_dev(tc_ctx *ctx, const tc_fm *fm, const uint64_t *d_fac_offs, const uint64_t *d_fac_pos,
+                          const uint32_t *d_fac_len, uint64_t npat, uint64_t *d_out_offs, uint8_t *d_out, uint64_t *nbytes);
 /* seqToCc / seqFromFMIndex views for the Haskell shim: present symbols (sorted,
  * Nothing first) with C[c]; and L / primary. */
 int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, uint64_t *c_val,

@@ -1,4 +1,4 @@
-// tc_fm_host.hpp -- FM-index: build, batched count, locate, extract.
+// tc_fm_host.hpp -- FM-index: build, batched count, locate, extract, factorize.
 //
 // Replaces (reference FMIndex/Internal.hs) seqToCc :275-316 (C[c], there derived
 // from an O(n^2) rotation matrix, BWT/Internal.hs:209-241; here a byte histogram),
@@ -414,16 +414,20 @@ __global__ __launch_bounds__(256) void fm_locate_rows_kernel(const u64 *__restri
 // be a multiple of the rate plus the steps and lie in the text; a lane that runs into any of these raises FM_ERR_WALK (the
 // call answers TC_ERR_MALFORMED) and writes 0.  So no content can make the kernel spin or read outside L [N + 16], the
 // vectors [lines = N / 448 + 1 lines each] and samples [nsamples].
-__global__ __launch_bounds__(256) void fm_locate_walk_kernel(const u64 *__restrict__ bits, const u64 *__restrict__ marks,
-                                                             u64 lines, const u32 *__restrict__ tab, u32 sigma,
-                                                             const u8 *__restrict__ L, const u32 *__restrict__ samples,
-                                                             u64 nsamples, u64 N, u64 primary, u32 rate, u64 total,
-                                                             u64 *__restrict__ hits, u32 *__restrict__ err) {
+// (the body of two kernels: skip = null for locate; for factorize skip[h] = 0 marks an entry that is no row -- a literal
+// factor -- and is left as it is)
+__device__ __forceinline__ void fm_locate_walk_body(const u64 *__restrict__ bits, const u64 *__restrict__ marks,
+                                                    u64 lines, const u32 *__restrict__ tab, u32 sigma,
+                                                    const u8 *__restrict__ L, const u32 *__restrict__ samples,
+                                                    u64 nsamples, u64 N, u64 primary, u32 rate, u64 total,
+                                                    u64 *__restrict__ hits, u32 *__restrict__ err,
+                                                    const u32 *__restrict__ skip) {
     __shared__ u32 s_tab[512];
     for (int i = threadIdx.x; i < 512; i += 256) s_tab[i] = tab[i];
     __syncthreads();
     const u64 h = (u64)blockIdx.x * 256 + threadIdx.x;
     if (h >= total) return;
+    if (skip && skip[h] == 0) return;
     u64 row = hits[h];
     bool bad = row >= N;
     if (bad) row = 0;
@@ -460,6 +464,22 @@ __global__ __launch_bounds__(256) void fm_locate_walk_kernel(const u64 *__restri
     }
     if (bad) atomicOr(err, FM_ERR_WALK);
     hits[h] = bad ? 0 : pos + 1;
+}
+__global__ __launch_bounds__(256) void fm_locate_walk_kernel(const u64 *__restrict__ bits, const u64 *__restrict__ marks,
+                                                             u64 lines, const u32 *__restrict__ tab, u32 sigma,
+                                                             const u8 *__restrict__ L, const u32 *__restrict__ samples,
+                                                             u64 nsamples, u64 N, u64 primary, u32 rate, u64 total,
+                                                             u64 *__restrict__ hits, u32 *__restrict__ err) {
+    fm_locate_walk_body(bits, marks, lines, tab, sigma, L, samples, nsamples, N, primary, rate, total, hits, err, nullptr);
+}
+// the walk over a factor list (tc_fm_factor.hpp): fpos[f] of a match factor (flen[f] > 0) is a row; literals are skipped
+__global__ __launch_bounds__(256) void fm_factor_walk_kernel(const u64 *__restrict__ bits, const u64 *__restrict__ marks,
+                                                             u64 lines, const u32 *__restrict__ tab, u32 sigma,
+                                                             const u8 *__restrict__ L, const u32 *__restrict__ samples,
+                                                             u64 nsamples, u64 N, u64 primary, u32 rate, u64 total,
+                                                             u64 *__restrict__ fpos, const u32 *__restrict__ flen,
+                                                             u32 *__restrict__ err) {
+    fm_locate_walk_body(bits, marks, lines, tab, sigma, L, samples, nsamples, N, primary, rate, total, fpos, err, flen);
 }
 
 // ---- extract: text ranges read back from the index -----------------------------------------------------------------
@@ -598,6 +618,7 @@ __global__ __launch_bounds__(256) void fm_extract_walk_kernel(const u64 *__restr
 }
 
 #include "tc_fm_mm.hpp"   // fm_mm_kernel: count / locate within Hamming distance k
+#include "tc_fm_factor.hpp"   // fm_factor_kernel: the longest-match parse; the small kernels of its inverse
 
 #endif  // __HIPCC__
 
@@ -1120,6 +1141,19 @@ struct FmLocateScratch {
     }
 };
 
+// between the two passes of locate and of factorize: the counts of the first pass (W.d_cnt) scanned into d_offs[0 .. npat], the
+// last entry the total, which is read back and returned
+static u64 fm_offsets_of_counts(tc_ctx *ctx, const FmLocateScratch &W, u64 npat, u64 *d_offs) {
+    hipStream_t s = ctx->stream;
+    fm_cnt_to_u64_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(W.d_cnt, npat, W.d_len);
+    TC_LAUNCH_CHECK(ctx);
+    const u64 *d_total = tc_scan64(ctx, W.d_len, npat, W.d_tsum, d_offs);
+    TC_HIP(ctx, hipMemcpyAsync(d_offs + npat, d_total, sizeof(u64), hipMemcpyDeviceToDevice, s));
+    tc_d2h(ctx, &ctx->h_scalars[9], d_total, sizeof(u64));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    return ctx->h_scalars[9];
+}
+
 // everything on the device: the count pass, the scan of the counts (d_hoffs[0 .. npat], the last entry the total, which is
 // returned), then -- when the total is neither 0 nor above cap -- the fill pass: the exact search copies its ranges' rows out of
 // the suffix array (a full index) or writes the rows themselves (a sampled one); the search with mismatches repeats its
@@ -1131,13 +1165,7 @@ static u64 fm_locate_device(tc_ctx *ctx, const tc_fm *fm, const FmLocateScratch 
     hipStream_t s = ctx->stream;
     const u32 grid = tc_cdiv(npat, 256);
     fm_count_pass(ctx, fm, d_pats, d_offs, npat, exact, k, W.d_cnt, W.d_ranges);
-    fm_cnt_to_u64_kernel<<<grid, 256, 0, s>>>(W.d_cnt, npat, W.d_len);
-    TC_LAUNCH_CHECK(ctx);
-    const u64 *d_total = tc_scan64(ctx, W.d_len, npat, W.d_tsum, d_hoffs);
-    TC_HIP(ctx, hipMemcpyAsync(d_hoffs + npat, d_total, sizeof(u64), hipMemcpyDeviceToDevice, s));
-    tc_d2h(ctx, &ctx->h_scalars[9], d_total, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 need = ctx->h_scalars[9];
+    const u64 need = fm_offsets_of_counts(ctx, W, npat, d_hoffs);
     if (need > cap || need == 0) return need;
     if (!exact) {
         fm_mm_device(ctx, fm, d_pats, d_offs, npat, k, nullptr, d_hoffs, d_hits, d_mm);
@@ -1273,5 +1301,199 @@ static void fm_extract_entry(tc_ctx *ctx, const tc_fm *fm, const u64 *starts, co
         tc_d2h(ctx, out_offs, d_offs, (nq + 1) * sizeof(u64));
         if (need) tc_d2h(ctx, out, d_out, need);
     }
+    tc_sync_check(ctx);
+}
+
+// ---- factorize / unfactorize (the kernels: tc_fm_factor.hpp) ---------------------------------------------------------------
+// fm_factor_kernel over a batch.  d_foffs = null: the sizes pass (d_cnt[p] = factors of pattern p).  Otherwise the fill pass:
+// the same parse writes pattern p's factors to [d_foffs[p], d_foffs[p + 1]) of d_fpos / d_flen -- positions on a full index,
+// rows on a sampled one.  (An empty index has no tables: every byte is a literal.)
+static void fm_factor_pass(tc_ctx *ctx, const tc_fm *fm, const u8 *d_pats, const u64 *d_offs, u64 npat, i64 *d_cnt,
+                           const u64 *d_foffs, u64 *d_fpos, u32 *d_flen) {
+    const u32 grid = tc_cdiv(npat, 256);
+    hipStream_t s = ctx->stream;
+#define FM_FACTOR_LAUNCH(P, F)                                                                                                \
+    fm_factor_kernel<P, F><<<grid, 256, 0, s>>>(fm->d_bits, fm->d_bits2, fm->lines, fm->d_tab, fm->d_tab2, fm->sigma_bytes,    \
+                                                (u32)fm->N, d_pats, d_offs, npat, d_cnt, d_foffs, fm->d_sa, d_fpos, d_flen)
+    if (d_foffs) {
+        if (fm->d_bits2) FM_FACTOR_LAUNCH(true, true); else FM_FACTOR_LAUNCH(false, true);
+    } else {
+        if (fm->d_bits2) FM_FACTOR_LAUNCH(true, false); else FM_FACTOR_LAUNCH(false, false);
+    }
+#undef FM_FACTOR_LAUNCH
+    TC_LAUNCH_CHECK(ctx);
+}
+
+// everything on the device: the sizes pass, the scan of the counts (d_foffs[0 .. npat], the last entry the total, which is
+// returned), then -- when the total is neither 0 nor above cap -- the fill pass and, on a sampled index, the walk that turns
+// the match factors' rows into positions.  When the total exceeds cap nothing is written to d_fpos or d_flen.  The caller
+// synchronises (tc_sync_check: the walk's bounds raise the device error word).
+static u64 fm_factor_device(tc_ctx *ctx, const tc_fm *fm, const FmLocateScratch &W, const u8 *d_pats, const u64 *d_offs, u64 npat,
+                            u64 *d_foffs, u64 *d_fpos, u32 *d_flen, u64 cap) {
+    fm_factor_pass(ctx, fm, d_pats, d_offs, npat, W.d_cnt, nullptr, nullptr, nullptr);
+    const u64 need = fm_offsets_of_counts(ctx, W, npat, d_foffs);
+    if (need > cap || need == 0) return need;
+    fm_factor_pass(ctx, fm, d_pats, d_offs, npat, nullptr, d_foffs, d_fpos, d_flen);
+    if (fm->sa_rate > 1) {
+        fm_factor_walk_kernel<<<tc_cdiv(need, 256), 256, 0, ctx->stream>>>(fm->d_bits, fm->d_marks, fm->lines, fm->d_tab,
+                                                                          fm->sigma_bytes, fm->d_L, fm->d_samples, fm->nsamples,
+                                                                          fm->N, fm->primary, fm->sa_rate, need, d_fpos, d_flen,
+                                                                          ctx->d_err);
+        TC_LAUNCH_CHECK(ctx);
+    }
+    return need;
+}
+
+// tc_fm_factorize, tc_fm_factorize_dev.  fac_pos = fac_len = null with capacity 0 is the sizes-only form: fac_offs and the
+// total, TC_OK.
+static void fm_factor_entry(tc_ctx *ctx, const tc_fm *fm, const u8 *pats, const u64 *offs, u64 npat, u64 *fac_offs, u64 *fac_pos,
+                            u32 *fac_len, u64 *nfac, bool dev) {
+    if (!fm || !nfac) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const u64 cap = *nfac;
+    *nfac = 0;
+    if (npat == 0) return;
+    const bool sizes_only = !fac_pos && !fac_len && cap == 0;
+    if (!pats || !offs || !fac_offs || (!sizes_only && (!fac_pos || !fac_len))) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (fm->n && !fm->sa_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index was imported without its locate part");
+    FmLocateScratch W;
+    FmPatterns P;
+    u64 *d_foffs = fac_offs, *d_fpos = fac_pos;
+    u32 *d_flen = fac_len;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+        if (!dev) P.carve(A, offs, npat);
+        W.carve(A, npat, false);
+        if (!dev) {
+            d_foffs = A.get<u64>(npat + 1);
+            d_fpos = A.get<u64>(cap + 1);
+            d_flen = A.get<u32>(cap + 1);
+        }
+    });
+    if (!dev) P.upload(ctx, pats, offs, npat);
+    const u64 need = fm_factor_device(ctx, fm, W, dev ? pats : P.d_pats, dev ? offs : P.d_offs, npat, d_foffs, d_fpos, d_flen,
+                                      sizes_only ? 0 : cap);
+    *nfac = need;
+    if (!dev) tc_d2h(ctx, fac_offs, d_foffs, (npat + 1) * sizeof(u64));
+    if (need > cap && !sizes_only) {
+        tc_sync_check(ctx);
+        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu factor slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
+    }
+    if (!dev && need && !sizes_only) {
+        tc_d2h(ctx, fac_pos, d_fpos, need * sizeof(u64));
+        tc_d2h(ctx, fac_len, d_flen, need * sizeof(u32));
+    }
+    tc_sync_check(ctx);
+}
+
+// scratch of one unfactorize batch besides factors and results: that of a flat extract over nf factors, the factors' byte
+// offsets [nf + 1] (what the extract calls out_offs), and the factor lengths as the walk reads them (FmExtractScratch::d_len)
+struct FmUnfactorScratch {
+    FmExtractScratch X;
+    u64 *d_boffs = nullptr;
+    void carve(Arena &A, u64 nf) {
+        X.carve(A, nf ? nf : 1);
+        d_boffs = A.get<u64>(nf + 1);
+    }
+};
+
+// everything on the device, nf = the factor total (fac_offs[npat], read by the entry): the offsets' check and the plan
+// (validation, byte and segment counts, their scans), the gather of d_out_offs[0 .. npat], then -- after the host has seen
+// the flag and the totals -- fm_extract_walk_kernel, unchanged, over the match factors (a factor is a query (pos, len); the
+// walk never selects a factor without segments) and the literals' bytes.  Returns the byte total; a bad list is TC_ERR_ARG,
+// and then, as with a total above cap, nothing is written to d_out.  The caller synchronises.
+static u64 fm_unfactor_device(tc_ctx *ctx, const tc_fm *fm, const FmUnfactorScratch &W, const u64 *d_foffs, const u64 *d_fpos,
+                              const u32 *d_flen, u64 npat, u64 nf, u64 *d_out_offs, u8 *d_out, u64 cap) {
+    hipStream_t s = ctx->stream;
+    const u32 lg = fm_log2(fm->text_rate);
+    const FmExtractScratch &X = W.X;
+    TC_HIP(ctx, hipMemsetAsync(X.d_bad, 0, 2 * sizeof(u32), s));
+    TC_HIP(ctx, hipMemsetAsync(W.d_boffs, 0, sizeof(u64), s));
+    fm_unfactor_offs_kernel<<<tc_cdiv(npat, 256), 256, 0, s>>>(d_foffs, npat, X.d_bad);
+    TC_LAUNCH_CHECK(ctx);
+    u64 need = 0, nsegs = 0;
+    if (nf) {
+        fm_unfactor_plan_kernel<<<tc_cdiv(nf, 256), 256, 0, s>>>(d_fpos, d_flen, nf, fm->n, lg, X.d_len, X.d_segs, X.d_bad);
+        TC_LAUNCH_CHECK(ctx);
+        const u64 *d_bytes = tc_scan64(ctx, X.d_len, nf, X.d_tsum_b, W.d_boffs);
+        const u64 *d_nsegs = tc_scan64(ctx, X.d_segs, nf, X.d_tsum_s, X.d_soffs);
+        TC_HIP(ctx, hipMemcpyAsync(W.d_boffs + nf, d_bytes, sizeof(u64), hipMemcpyDeviceToDevice, s));
+        tc_d2h(ctx, &ctx->h_scalars[9], d_bytes, sizeof(u64));
+        tc_d2h(ctx, &ctx->h_scalars[8], d_nsegs, sizeof(u64));
+    }
+    tc_d2h(ctx, &ctx->h_scalars[10], X.d_bad, sizeof(u32));
+    TC_HIP(ctx, hipStreamSynchronize(s));
+    if (nf) need = ctx->h_scalars[9], nsegs = ctx->h_scalars[8];
+    if ((u32)ctx->h_scalars[10])
+        TC_FAIL(ctx, TC_ERR_ARG, "unfactorize: a bad factor list (fac_offs starts at 0 and never decreases; a match has 1 <= pos, pos - 1 + len <= %llu; a literal has len 0 and pos <= 255)",
+                (unsigned long long)fm->n);
+    fm_unfactor_gather_kernel<<<tc_cdiv(npat + 1, 256), 256, 0, s>>>(d_foffs, npat, W.d_boffs, d_out_offs);
+    TC_LAUNCH_CHECK(ctx);
+    if (need > cap || need == 0) return need;
+    if (nsegs) {
+        fm_extract_walk_kernel<<<tc_cdiv(nsegs, 256), 256, 0, s>>>(fm->d_bits, fm->lines, fm->d_tab, fm->sigma_bytes, fm->d_L,
+                                                                 fm->d_isa, fm->nisa, fm->N, fm->primary, lg, d_fpos, X.d_len,
+                                                                 X.d_soffs, W.d_boffs, nf, nsegs, d_out, ctx->d_err);
+        TC_LAUNCH_CHECK(ctx);
+    }
+    fm_unfactor_literal_kernel<<<tc_cdiv(nf, 256), 256, 0, s>>>(d_fpos, d_flen, nf, W.d_boffs, d_out);
+    TC_LAUNCH_CHECK(ctx);
+    return need;
+}
+
+// tc_fm_unfactorize, tc_fm_unfactorize_dev
+static void fm_unfactor_entry(tc_ctx *ctx, const tc_fm *fm, const u64 *fac_offs, const u64 *fac_pos, const u32 *fac_len, u64 npat,
+                              u64 *out_offs, u8 *out, u64 *nbytes, bool dev) {
+    if (!fm || !nbytes) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const u64 cap = *nbytes;
+    *nbytes = 0;
+    if (npat == 0) {
+        if (out_offs) fm_zero_result(ctx, out_offs, sizeof(u64), dev);
+        return;
+    }
+    if (!fm->text_rate) TC_FAIL(ctx, TC_ERR_ARG, "this index holds no text samples (build it with tc_fm_build_self; an import without the locate part has none)");
+    if (!fac_offs || !out_offs || (!out && cap)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    u64 ends[2];    // fac_offs[0] and fac_offs[npat]: the list starts at 0, and its last offset is the factor total
+    if (dev) {
+        tc_d2h(ctx, &ctx->h_scalars[8], fac_offs, sizeof(u64));
+        tc_d2h(ctx, &ctx->h_scalars[9], fac_offs + npat, sizeof(u64));
+        TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ends[0] = ctx->h_scalars[8];
+        ends[1] = ctx->h_scalars[9];
+    } else {
+        ends[0] = fac_offs[0];
+        ends[1] = fac_offs[npat];
+    }
+    const u64 nf = ends[1];
+    // (a total no pair of factor arrays can hold is refused here: the sizes below are computed from it)
+    if (ends[0] != 0 || nf > ((u64)1 << 40)) TC_FAIL(ctx, TC_ERR_ARG, "unfactorize: a bad factor list (fac_offs[0] = %llu, fac_offs[npat] = %llu)", (unsigned long long)ends[0], (unsigned long long)nf);
+    if (nf && (!fac_pos || !fac_len)) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    u64 *u_foffs = nullptr, *u_fpos = nullptr;   // the host form's copies of the factor list
+    u32 *u_flen = nullptr;
+    u64 *d_offs = out_offs;
+    u8 *d_out = out;
+    FmUnfactorScratch W;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+        if (!dev) {
+            u_foffs = A.get<u64>(npat + 1);
+            u_fpos = A.get<u64>(nf + 1);
+            u_flen = A.get<u32>(nf + 1);
+            d_offs = A.get<u64>(npat + 1);
+        }
+        W.carve(A, nf);
+        if (!dev) d_out = A.get<u8>(cap + 16);
+    });
+    if (!dev) {
+        tc_h2d(ctx, u_foffs, fac_offs, (npat + 1) * sizeof(u64));
+        if (nf) tc_h2d(ctx, u_fpos, fac_pos, nf * sizeof(u64));
+        if (nf) tc_h2d(ctx, u_flen, fac_len, nf * sizeof(u32));
+    }
+    const u64 need = fm_unfactor_device(ctx, fm, W, dev ? fac_offs : u_foffs, dev ? fac_pos : u_fpos, dev ? fac_len : u_flen, npat,
+                                        nf, d_offs, d_out, cap);
+    *nbytes = need;
+    if (!dev) tc_d2h(ctx, out_offs, d_offs, (npat + 1) * sizeof(u64));
+    if (need > cap) {
+        tc_sync_check(ctx);
+        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)cap);
+    }
+    if (!dev && need) tc_d2h(ctx, out, d_out, need);
     tc_sync_check(ctx);
 }

@@ -1570,6 +1570,35 @@ int tc_fm_extract(tc_ctx *ctx, const tc_fm *fm, const uint64_t *starts, const ui
     TC_API_END(ctx)
 }
 
+// ---- factorize / unfactorize (the kernels: tc_fm_factor.hpp) ---------------------------
+int tc_fm_factorize(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat, uint64_t *fac_offs,
+                    uint64_t *fac_pos, uint32_t *fac_len, uint64_t *nfac) {
+    TC_API_BEGIN(ctx)
+    fm_factor_entry(ctx, fm, pats, offs, npat, fac_offs, fac_pos, fac_len, nfac, false);
+    TC_API_END(ctx)
+}
+
+int tc_fm_factorize_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat,
+                        uint64_t *d_fac_offs, uint64_t *d_fac_pos, uint32_t *d_fac_len, uint64_t *nfac) {
+    TC_API_BEGIN(ctx)
+    fm_factor_entry(ctx, fm, d_pats, d_offs, npat, d_fac_offs, d_fac_pos, d_fac_len, nfac, true);
+    TC_API_END(ctx)
+}
+
+int tc_fm_unfactorize(tc_ctx *ctx, const tc_fm *fm, const uint64_t *fac_offs, const uint64_t *fac_pos, const uint32_t *fac_len,
+                      uint64_t npat, uint64_t *out_offs, uint8_t *out, uint64_t *nbytes) {
+    TC_API_BEGIN(ctx)
+    fm_unfactor_entry(ctx, fm, fac_offs, fac_pos, fac_len, npat, out_offs, out, nbytes, false);
+    TC_API_END(ctx)
+}
+
+int tc_fm_unfactorize_dev(tc_ctx *ctx, const tc_fm *fm, const uint64_t *d_fac_offs, const uint64_t *d_fac_pos,
+                          const uint32_t *d_fac_len, uint64_t npat, uint64_t *d_out_offs, uint8_t *d_out, uint64_t *nbytes) {
+    TC_API_BEGIN(ctx)
+    fm_unfactor_entry(ctx, fm, d_fac_offs, d_fac_pos, d_fac_len, npat, d_out_offs, d_out, nbytes, true);
+    TC_API_END(ctx)
+}
+
 int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, uint64_t *c_val,
                uint64_t *primary) {
     return fm_info(fm, N, sigma, c_sym, c_val, primary);

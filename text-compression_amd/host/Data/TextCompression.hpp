@@ -279,6 +279,57 @@ inline LocateMismatchResult bytestringFMIndexLocateMismatchP(const std::vector<s
     return bytestringFMIndexLocateMismatchS(pats, input, k);
 }
 
+// Not in the reference: factorize -- the greedy right-to-left longest-match parse of each pattern against the text
+// (textcomp.h).  Per pattern its factors in pattern order, in the ABI's convention: a match is (1-based text position of the
+// occurrence in the first suffix-array row, length >= 1), a literal -- a byte the text does not hold -- is (byte value, 0).
+// An empty pattern list gives an empty result; against an empty text every byte is a literal.
+struct Factors {
+    std::vector<uint64_t> offs, pos;    // offs [npat + 1]: pattern i's factors are [offs[i], offs[i + 1])
+    std::vector<uint32_t> len;
+};
+namespace detail {
+inline Factors factorize(const tc_fm *fm, const std::vector<std::string> &pats) {
+    Factors f;
+    f.offs.assign(pats.size() + 1, 0);
+    if (pats.empty()) return f;
+    std::vector<uint64_t> offs;
+    const std::string flat = packPatterns(pats, offs);
+    uint64_t nf = 0;        // the sizes-only form first: the total
+    Context::check(tc_fm_factorize(Context::get(), fm, (const uint8_t *)flat.data(), offs.data(), pats.size(), f.offs.data(),
+                                   nullptr, nullptr, &nf));
+    f.pos.resize(nf);
+    f.len.resize(nf);
+    if (nf)
+        Context::check(tc_fm_factorize(Context::get(), fm, (const uint8_t *)flat.data(), offs.data(), pats.size(), f.offs.data(),
+                                       f.pos.data(), f.len.data(), &nf));
+    return f;
+}
+}  // namespace detail
+using FactorizeResult = std::vector<std::pair<std::string, std::vector<std::pair<uint64_t, uint32_t>>>>;
+inline FactorizeResult bytestringFMIndexFactorizeS(const std::vector<std::string> &pats, const std::string &input) {
+    FactorizeResult out;
+    if (pats.empty()) return out;
+    tc_fm *fm = nullptr;
+    Context::check(tc_fm_build(Context::get(), (const uint8_t *)input.data(), input.size(), &fm));
+    Factors f;
+    try {
+        f = detail::factorize(fm, pats);
+    } catch (...) {
+        tc_fm_free(fm);
+        throw;
+    }
+    tc_fm_free(fm);
+    for (size_t i = 0; i < pats.size(); i++) {
+        std::vector<std::pair<uint64_t, uint32_t>> v;
+        for (uint64_t t = f.offs[i]; t < f.offs[i + 1]; t++) v.emplace_back(f.pos[t], f.len[t]);
+        out.emplace_back(pats[i], std::move(v));
+    }
+    return out;
+}
+inline FactorizeResult bytestringFMIndexFactorizeP(const std::vector<std::string> &pats, const std::string &input) {
+    return bytestringFMIndexFactorizeS(pats, input);
+}
+
 // Not in the reference: an index that is kept between queries, optionally with a sampled suffix array (sa_rate > 1: every
 // sa_rate-th entry is kept and locate walks the LF mapping to the next one; textcomp.h), queried with everything in HBM.
 class Index {
@@ -333,6 +384,43 @@ class Index {
                         uint64_t cap) const {
         uint64_t nb = cap;
         int rc = tc_fm_extract_dev(Context::get(), fm_, d_starts, d_lens, nq, d_out_offs, d_out, &nb);
+        if (rc != TC_ERR_CAPACITY) Context::check(rc);
+        return nb;
+    }
+    // the factors of every pattern (bytestringFMIndexFactorizeS on the kept index), and their inverse on an index with text
+    // samples: unfactorize(factorize(pats)) == pats, and the text itself need not be kept
+    Factors factorize(const std::vector<std::string> &pats) const { return detail::factorize(fm_, pats); }
+    std::vector<std::string> unfactorize(const Factors &f) const {
+        const size_t npat = f.offs.empty() ? 0 : f.offs.size() - 1;
+        std::vector<std::string> res(npat);
+        if (!npat) return res;
+        std::vector<uint64_t> offs(npat + 1);
+        std::string flat(1, '\0');
+        uint64_t nb = 0;
+        int rc = tc_fm_unfactorize(Context::get(), fm_, f.offs.data(), f.pos.data(), f.len.data(), npat, offs.data(),
+                                   (uint8_t *)&flat[0], &nb);
+        if (rc == TC_ERR_CAPACITY) {            // *nbytes = the bytes needed: once more with room for them
+            flat.assign(nb, '\0');
+            rc = tc_fm_unfactorize(Context::get(), fm_, f.offs.data(), f.pos.data(), f.len.data(), npat, offs.data(),
+                                   (uint8_t *)&flat[0], &nb);
+        }
+        Context::check(rc);
+        for (size_t i = 0; i < npat; i++) res[i] = flat.substr(offs[i], offs[i + 1] - offs[i]);
+        return res;
+    }
+    // everything in HBM (d_fac_offs [npat + 1], d_fac_pos / d_fac_len [cap]; d_out_offs [npat + 1], d_out [cap]).  Each returns
+    // the total; when it exceeds cap nothing was written to the payload arrays and the caller repeats the call with it.
+    uint64_t factorizeDev(const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint64_t *d_fac_offs, uint64_t *d_fac_pos,
+                          uint32_t *d_fac_len, uint64_t cap) const {
+        uint64_t nf = cap;
+        int rc = tc_fm_factorize_dev(Context::get(), fm_, d_pats, d_offs, npat, d_fac_offs, d_fac_pos, d_fac_len, &nf);
+        if (rc != TC_ERR_CAPACITY) Context::check(rc);
+        return nf;
+    }
+    uint64_t unfactorizeDev(const uint64_t *d_fac_offs, const uint64_t *d_fac_pos, const uint32_t *d_fac_len, uint64_t npat,
+                            uint64_t *d_out_offs, uint8_t *d_out, uint64_t cap) const {
+        uint64_t nb = cap;
+        int rc = tc_fm_unfactorize_dev(Context::get(), fm_, d_fac_offs, d_fac_pos, d_fac_len, npat, d_out_offs, d_out, &nb);
         if (rc != TC_ERR_CAPACITY) Context::check(rc);
         return nb;
     }

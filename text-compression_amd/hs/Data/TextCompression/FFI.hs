@@ -76,6 +76,17 @@ foreign import ccall safe "tc_fm_locate_mm"
   c_tc_fm_locate_mm :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Word32 -> Ptr Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
 foreign import ccall safe "tc_fm_locate_mm_dev"
   c_tc_fm_locate_mm_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Word32 -> Ptr Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
+-- factorize: the greedy right-to-left longest-match parse of patterns against the text -- factor offsets, (position,
+-- length) per factor, a literal is (byte, 0) -- and its inverse on an index with text samples (no counterpart in the
+-- reference).  fac_pos = fac_len = nullPtr with capacity 0 asks for the sizes alone
+foreign import ccall safe "tc_fm_factorize"
+  c_tc_fm_factorize :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Ptr Word64 -> Ptr Word64 -> Ptr Word32 -> Ptr Word64 -> IO Int32
+foreign import ccall safe "tc_fm_factorize_dev"
+  c_tc_fm_factorize_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Ptr Word64 -> Ptr Word64 -> Ptr Word32 -> Ptr Word64 -> IO Int32
+foreign import ccall safe "tc_fm_unfactorize"
+  c_tc_fm_unfactorize :: Ptr TcCtx -> Ptr TcFm -> Ptr Word64 -> Ptr Word64 -> Ptr Word32 -> Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
+foreign import ccall safe "tc_fm_unfactorize_dev"
+  c_tc_fm_unfactorize_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word64 -> Ptr Word64 -> Ptr Word32 -> Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
 -- stored / shipped form (no counterpart in the reference): one record, or any length cut into records
 foreign import ccall unsafe "tc_container_bound"
   c_tc_container_bound :: Word64 -> Word32 -> Word64

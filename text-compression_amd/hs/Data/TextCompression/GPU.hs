@@ -17,6 +17,7 @@ module Data.TextCompression.GPU
   , bytestringFMIndexLocateS, bytestringFMIndexLocateP
   , bytestringFMIndexCountMismatchS, bytestringFMIndexCountMismatchP
   , bytestringFMIndexLocateMismatchS, bytestringFMIndexLocateMismatchP
+  , bytestringFMIndexFactorizeS, bytestringFMIndexFactorizeP
   ) where
 
 import Control.Concurrent.MVar (MVar, newMVar, modifyMVar_, withMVar)
@@ -329,3 +330,38 @@ bytestringFMIndexLocateMismatchS k pats input
 
 bytestringFMIndexLocateMismatchP :: Int -> [BS.ByteString] -> BS.ByteString -> IO (Seq (BS.ByteString, Seq (Int, Int)))
 bytestringFMIndexLocateMismatchP k pats input = pure (bytestringFMIndexLocateMismatchS k pats input)
+
+-- | Not in the reference: the greedy right-to-left longest-match parse of each pattern against the text, its factors in
+-- pattern order as (position, length): a match is the 1-based text position of the occurrence in the first suffix-array
+-- row and a length >= 1, a literal -- a byte the text does not hold -- is (byte value, 0).  Against an empty text every
+-- byte is a literal.  Two device calls: tc_fm_factorize in its sizes-only form, then with room for the factors.
+bytestringFMIndexFactorizeS :: [BS.ByteString] -> BS.ByteString -> Seq (BS.ByteString, Seq (Int, Int))
+bytestringFMIndexFactorizeS pats input
+  | null pats = DS.Empty
+  | otherwise = unsafePerformIO $ withCtx $ \ctx ->
+      BSU.unsafeUseAsCStringLen input $ \(p, n) -> alloca $ \ph -> do
+        c_tc_fm_build ctx (castPtr p) (fromIntegral n) ph >>= check ctx
+        fm <- peek ph
+        let np   = length pats
+            flat = BS.concat pats `BS.snoc` 0
+            offs = scanl (+) 0 (map (fromIntegral . BS.length) pats)
+        (os, fs) <- BSU.unsafeUseAsCString flat $ \fp -> withArray offs $ \op ->
+          allocaArray (np + 1) $ \fo -> with 0 $ \nf -> do
+            rc0 <- c_tc_fm_factorize ctx fm (castPtr fp) op (fromIntegral np) fo nullPtr nullPtr nf
+            when (rc0 /= 0) (c_tc_fm_free fm)
+            check ctx rc0
+            total <- fromIntegral <$> peek nf
+            allocaArray (max 1 total) $ \fpos -> allocaArray (max 1 total) $ \flen -> do
+              rc <- if total == 0 then pure 0
+                    else c_tc_fm_factorize ctx fm (castPtr fp) op (fromIntegral np) fo fpos flen nf
+              c_tc_fm_free fm
+              check ctx rc
+              os <- map fromIntegral <$> peekArray (np + 1) fo
+              as <- map fromIntegral <$> peekArray total fpos
+              ls <- map fromIntegral <$> peekArray total flen
+              pure (os, zip as ls)
+        let slices = [ take (e - a) (drop a fs) | (a, e) <- zip os (tail os) ]
+        pure . DS.fromList $ [ (q, DS.fromList f) | (q, f) <- zip pats slices ]
+
+bytestringFMIndexFactorizeP :: [BS.ByteString] -> BS.ByteString -> IO (Seq (BS.ByteString, Seq (Int, Int)))
+bytestringFMIndexFactorizeP pats input = pure (bytestringFMIndexFactorizeS pats input)

@@ -611,6 +611,118 @@ class FMIndexHandle:
         return [(hits[int(hoffs[i]):int(hoffs[i + 1])].copy(), mm[int(hoffs[i]):int(hoffs[i + 1])].copy())
                 for i in range(len(pats))]
 
+    def factorize(self, pats):
+        """the greedy right-to-left longest-match parse of each pattern against the text -> (fac_offs uint64 [npat + 1],
+        fac_pos uint64 [total], fac_len uint32 [total]): pattern i's factors are [fac_offs[i], fac_offs[i + 1]), in
+        pattern order; a match is (1-based position, length >= 1), a literal (byte value, 0): tc_fm_factorize"""
+        ctx = self._ctx
+        npat = len(pats)
+        foffs = np.zeros(npat + 1, np.uint64)
+        if npat == 0:
+            return foffs, np.empty(0, np.uint64), np.empty(0, np.uint32)
+        flat, offs = self._pack(pats)
+        cap = 1 << 16
+        while True:
+            fpos = np.empty(cap, np.uint64)
+            flen = np.empty(cap, np.uint32)
+            nf = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_factorize(ctx.handle, self._h, _ptr(flat), _ptr(offs), npat, _ptr(foffs), _ptr(fpos), _ptr(flen),
+                                         C.byref(nf))
+            if rc == _lib.TC_ERR_CAPACITY and int(nf.value) > cap:
+                cap = int(nf.value)
+                continue
+            ctx._check(rc)
+            break
+        return foffs, fpos[:int(nf.value)].copy(), flen[:int(nf.value)].copy()
+
+    def factor_counts(self, pats):
+        """-> uint64[npat]: the number of factors of each pattern (the sizes-only form of tc_fm_factorize)"""
+        ctx = self._ctx
+        npat = len(pats)
+        if npat == 0:
+            return np.empty(0, np.uint64)
+        flat, offs = self._pack(pats)
+        foffs = np.zeros(npat + 1, np.uint64)
+        nf = C.c_uint64(0)
+        ctx._check(ctx.lib.tc_fm_factorize(ctx.handle, self._h, _ptr(flat), _ptr(offs), npat, _ptr(foffs), None, None, C.byref(nf)))
+        return np.diff(foffs)
+
+    def unfactorize(self, fac_offs, fac_pos, fac_len):
+        """the inverse of factorize on an index with text samples (text_rate > 0) -> list of bytes, one per pattern:
+        tc_fm_unfactorize"""
+        fo = np.ascontiguousarray(fac_offs, dtype=np.uint64)
+        fp = np.ascontiguousarray(fac_pos, dtype=np.uint64)
+        fl = np.ascontiguousarray(fac_len, dtype=np.uint32)
+        if fo.ndim != 1 or len(fo) == 0 or fp.shape != fl.shape or fp.ndim != 1:
+            raise ValueError("fac_offs [npat + 1], and fac_pos and fac_len of one length")
+        npat = len(fo) - 1
+        if npat == 0:
+            return []
+        if int(fo[-1]) > len(fp):
+            raise ValueError("fac_offs names %d factors, %d given" % (int(fo[-1]), len(fp)))
+        ctx = self._ctx
+        offs = np.empty(npat + 1, np.uint64)
+        cap = 1 << 16
+        while True:
+            out = np.empty(max(cap, 1), np.uint8)
+            nb = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_unfactorize(ctx.handle, self._h, _ptr(fo), _ptr(fp) if len(fp) else None,
+                                           _ptr(fl) if len(fl) else None, npat, _ptr(offs), _ptr(out), C.byref(nb))
+            if rc == _lib.TC_ERR_CAPACITY and int(nb.value) > cap:
+                cap = int(nb.value)
+                continue
+            ctx._check(rc)
+            break
+        blob = out[:int(nb.value)].tobytes()
+        return [blob[int(offs[i]):int(offs[i + 1])] for i in range(npat)]
+
+    def factorize_dev(self, d_pats, d_offs, npat, cap=None):
+        """patterns resident on the device (as count_dev) -> (fac_offs int64 tensor [npat + 1], fac_pos int64 tensor
+        [total], fac_len int32 tensor [total]), all on the device: tc_fm_factorize_dev"""
+        import torch
+        ctx = self._ctx
+        dev = d_pats.device
+        foffs = torch.zeros(npat + 1, dtype=torch.int64, device=dev)
+        if npat == 0:
+            return foffs, torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev)
+        cap = max(int(cap) if cap is not None else 4 * npat, 1)
+        for _ in range(2):
+            fpos = torch.empty(cap, dtype=torch.int64, device=dev)
+            flen = torch.empty(cap, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            nf = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_factorize_dev(ctx.handle, self._h, C.c_void_p(d_pats.data_ptr()), C.c_void_p(d_offs.data_ptr()),
+                                             npat, C.c_void_p(foffs.data_ptr()), C.c_void_p(fpos.data_ptr()),
+                                             C.c_void_p(flen.data_ptr()), C.byref(nf))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nf.value), 1)
+        ctx._check(rc)
+        return foffs, fpos[:int(nf.value)], flen[:int(nf.value)]
+
+    def unfactorize_dev(self, d_fac_offs, d_fac_pos, d_fac_len, npat, cap=None):
+        """a factor list resident on the device (what factorize_dev returns) -> (offs int64 tensor [npat + 1], bytes uint8
+        tensor [total]), both on the device: tc_fm_unfactorize_dev"""
+        import torch
+        ctx = self._ctx
+        dev = d_fac_offs.device
+        offs = torch.zeros(npat + 1, dtype=torch.int64, device=dev)
+        if npat == 0:
+            return offs, torch.zeros(0, dtype=torch.uint8, device=dev)
+        cap = max(int(cap) if cap is not None else 128 * npat, 1)
+        for _ in range(2):
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            nb = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_unfactorize_dev(ctx.handle, self._h, C.c_void_p(d_fac_offs.data_ptr()),
+                                               C.c_void_p(d_fac_pos.data_ptr()), C.c_void_p(d_fac_len.data_ptr()), npat,
+                                               C.c_void_p(offs.data_ptr()), C.c_void_p(out.data_ptr()), C.byref(nb))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nb.value), 1)
+        ctx._check(rc)
+        return offs, out[:int(nb.value)]
+
     def info(self):
         ctx = self._ctx
         N, sig, prim = C.c_uint64(), C.c_uint32(), C.c_uint64()

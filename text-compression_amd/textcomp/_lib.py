@@ -117,6 +117,10 @@ SYMBOLS = [
     ("tc_fm_count_mm_dev", _INT, [_P, _P, _P, _P, _U64, _U32, _P]),
     ("tc_fm_locate_mm", _INT, [_P, _P, _P, _P, _U64, _U32, _P, _P, _P, _PU64]),
     ("tc_fm_locate_mm_dev", _INT, [_P, _P, _P, _P, _U64, _U32, _P, _P, _P, _PU64]),
+    ("tc_fm_factorize", _INT, [_P, _P, _P, _P, _U64, _P, _P, _P, _PU64]),
+    ("tc_fm_factorize_dev", _INT, [_P, _P, _P, _P, _U64, _P, _P, _P, _PU64]),
+    ("tc_fm_unfactorize", _INT, [_P, _P, _P, _P, _P, _U64, _P, _P, _PU64]),
+    ("tc_fm_unfactorize_dev", _INT, [_P, _P, _P, _P, _P, _U64, _P, _P, _PU64]),
     ("tc_fm_info", _INT, [_P, _PU64, _PU32, _P, _P, _PU64]),
     ("tc_comm_unique_id", _INT, [_P, _P]),
     ("tc_comm_create", _INT, [_P, _P, _INT, _INT, C.POINTER(_P)]),

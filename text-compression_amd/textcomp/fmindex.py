@@ -76,6 +76,27 @@ def bytestringFMIndexLocateMismatchP(pats, text, k, ctx=None):
     return bytestringFMIndexLocateMismatchS(pats, text, k, ctx)
 
 
+# ---- factorize (no counterpart in the reference; the value shape of the locate mirrors above) ----
+def bytestringFMIndexFactorizeS(pats, text, ctx=None):
+    """[(pattern, [(pos, len)])]: the greedy right-to-left longest-match parse of each pattern against the text, factors
+    in pattern order, in the ABI's convention: a match is (1-based text position of the occurrence in the first
+    suffix-array row, length >= 1), a literal -- a byte the text does not hold -- is (byte value, 0).  Empty pattern list
+    => empty result; against an empty text every byte is a literal."""
+    if len(pats) == 0:
+        return []
+    fm = (ctx or default_context()).fm_build(text)
+    try:
+        foffs, fpos, flen = fm.factorize(pats)
+    finally:
+        fm.close()
+    return [(p, [(int(fpos[f]), int(flen[f])) for f in range(int(foffs[i]), int(foffs[i + 1]))]) for i, p in enumerate(pats)]
+
+
+def bytestringFMIndexFactorizeP(pats, text, ctx=None):
+    """the same values in the same order: the batch is one launch either way"""
+    return bytestringFMIndexFactorizeS(pats, text, ctx)
+
+
 # ---- Text instantiations (FMIndex.hs:385-403,436-462,503-530,570-599) ----------------------------
 # The index is built over the UTF-8 bytes, each turned into a Text by decodeUtf8 . BS.singleton
 # (ASCII only, an exception otherwise); patterns are split into characters.  For ASCII input that is
@@ -188,3 +209,15 @@ def textFMIndexLocateMismatchS(pats, text, k, ctx=None):
 
 def textFMIndexLocateMismatchP(pats, text, k, ctx=None):
     return textFMIndexLocateMismatchS(pats, text, k, ctx)
+
+
+def textFMIndexFactorizeS(pats, text, ctx=None):
+    """bytestringFMIndexFactorizeS over the UTF-8 bytes (ASCII only, as the other text... variants)."""
+    if len(pats) == 0:
+        return []
+    res = bytestringFMIndexFactorizeS([p.encode("utf-8") for p in pats], _ascii_bytes(text), ctx)
+    return [(p, f) for p, (_, f) in zip(pats, res)]
+
+
+def textFMIndexFactorizeP(pats, text, ctx=None):
+    return textFMIndexFactorizeS(pats, text, ctx)
