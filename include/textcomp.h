@@ -150,6 +150,27 @@ int tc_bwt_encode_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint8_t *d
 /* createSuffixArray alone: sa[j] = 0-based start of the j-th smallest suffix of
  * text.'$' (reference: 1-based suffixstartpos), n+1 entries. */
 int tc_suffix_array(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *sa);
+/* The same with text and array resident in HBM: d_sa receives n+1 entries (n == 0: the one entry 0, as above).
+ * Not part of the reference's surface, like the three calls below. */
+int tc_suffix_array_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_sa);
+/* The LCP array that goes with that suffix array (together: the enhanced suffix array).  lcp has n+1 entries:
+ * lcp[0] = 0, and for j >= 1 lcp[j] = length of the longest common prefix of the suffixes starting at sa[j-1] and
+ * sa[j].  The end of the text matches nothing, so lcp[j] <= n - max(sa[j-1], sa[j]) and lcp[1] = 0.  n == 0 writes
+ * lcp[0] = 0 (and sa[0] = 0).
+ *   tc_lcp_array      sorts and computes in one call; sa (host, n+1 entries) may be NULL.
+ *   tc_lcp_array_dev  takes a suffix array that already lies in HBM (tc_suffix_array_dev's, or one the caller kept).
+ *                     d_text holds exactly n bytes: nothing before or behind them is read.  A d_sa that is not a
+ *                     permutation of 0..n (an entry above n, a value twice, a value missing): TC_ERR_MALFORMED, every
+ *                     read and write in bounds; a permutation that is not the suffix array of d_text: values without
+ *                     meaning, each still <= n - max(sa[j-1], sa[j]), no error.  n == 0: d_sa is not read.
+ * Null buffers or n > TC_MAX_N: TC_ERR_ARG.  Scratch (4 bytes per entry, plus at most another 4 n for comparisons
+ * longer than a few hundred bytes) comes from the calling ctx's workspace. */
+int tc_lcp_array_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uint32_t *d_sa, uint32_t *d_lcp);
+int tc_lcp_array(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *sa, uint32_t *lcp);
+/* One reduction over N entries of an LCP array in HBM: *max_lcp = the largest entry, *row = the smallest row that
+ * holds it (rows row-1 and row of the suffix array are the longest repeat), *sum = the sum of all entries (the text
+ * has n(n+1)/2 - sum distinct substrings).  N == 0: TC_ERR_ARG. */
+int tc_lcp_summary_dev(tc_ctx *ctx, const uint32_t *d_lcp, uint64_t N, uint32_t *max_lcp, uint64_t *row, uint64_t *sum);
 
 /* bytestringFromWord8BWT (BWT.hs:108-110) = fromBWT (:93-104) + sortTB
  * (BWT/Internal.hs:144-149) + magicInverseBWT (:163-200), for a well-formed BWT

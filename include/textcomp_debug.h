@@ -29,6 +29,10 @@ int tc_dbg_scatter_bench(tc_ctx *ctx, uint64_t n, uint32_t bins, uint32_t xrun, 
  * threads with `lds_bytes` of LDS each (147456: one per CU) spin for `spin_cycles`; out6[6 * grid] (host)
  * receives per workgroup: XCC id, HW_ID register, start (2 words, 100 MHz wall clock), duration, scratch. */
 int tc_dbg_dispatch_probe(tc_ctx *ctx, uint32_t grid, uint32_t lds_bytes, uint32_t spin_cycles, uint32_t *out6);
+/* The short cap of the LCP array's one-lane compare kernel (csrc/tc_lcp.hpp: comparisons that reach it go on, one
+ * workgroup each) for the later tc_lcp_array / tc_lcp_array_dev calls of this context: a multiple of 16 in 16 .. 65536,
+ * or 0 for the library's TC_LCP_SHORT_CAP.  The results do not depend on it; scripts/lcp_bench.py sweeps it. */
+int tc_dbg_lcp_set_short_cap(tc_ctx *ctx, uint32_t cap);
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
 #include "tc_encode_host.hpp"
 #include "tc_decode_host.hpp"
 #include "tc_fm_host.hpp"
+#include "tc_lcp_host.hpp"
 #include "tc_pack.hpp"
 #include "tc_huff.hpp"
 #include "tc_container_host.hpp"
@@ -761,6 +762,31 @@ int tc_suffix_array(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *sa) 
     if (!text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
     u64 primary;
     bwt_host(ctx, text, n, nullptr, sa, &primary);
+    TC_API_END(ctx)
+}
+
+// the enhanced suffix array (an addition to the reference's surface): tc_lcp_host.hpp
+int tc_suffix_array_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_sa) {
+    TC_API_BEGIN(ctx)
+    suffix_array_dev_entry(ctx, d_text, n, d_sa);
+    TC_API_END(ctx)
+}
+
+int tc_lcp_array_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uint32_t *d_sa, uint32_t *d_lcp) {
+    TC_API_BEGIN(ctx)
+    lcp_array_dev_entry(ctx, d_text, n, d_sa, d_lcp);
+    TC_API_END(ctx)
+}
+
+int tc_lcp_array(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *sa, uint32_t *lcp) {
+    TC_API_BEGIN(ctx)
+    lcp_array_host_entry(ctx, text, n, sa, lcp);
+    TC_API_END(ctx)
+}
+
+int tc_lcp_summary_dev(tc_ctx *ctx, const uint32_t *d_lcp, uint64_t N, uint32_t *max_lcp, uint64_t *row, uint64_t *sum) {
+    TC_API_BEGIN(ctx)
+    lcp_summary_entry(ctx, d_lcp, N, max_lcp, row, sum);
     TC_API_END(ctx)
 }
 
@@ -1820,6 +1846,16 @@ __global__ __launch_bounds__(1024) void dbg_dispatch_kernel(u32 *out, u32 spin) 
         out[blockIdx.x * 6 + 4] = (u32)(w1 - w0);
         out[blockIdx.x * 6 + 5] = acc;
     }
+}
+
+int tc_dbg_lcp_set_short_cap(tc_ctx *ctx, uint32_t cap) {
+    if (!ctx) return TC_ERR_ARG;
+    if (cap != 0 && (cap < 16 || cap > 65536 || cap % 16 != 0)) {
+        ctx->err = "the short cap is a multiple of 16 in 16 .. 65536, or 0";
+        return TC_ERR_ARG;
+    }
+    ctx->lcp_cap = cap;
+    return TC_OK;
 }
 
 int tc_dbg_dispatch_probe(tc_ctx *ctx, uint32_t grid, uint32_t lds_bytes, uint32_t spin_cycles, uint32_t *out6) {

@@ -89,6 +89,42 @@ inline std::string bytestringFromWord8BWT(const Word8Seq &bwt) {
     out.resize(n);
     return out;
 }
+
+// Not in the reference: the enhanced suffix array -- the suffix array (0-based starts, n + 1 rows, row 0 the empty
+// suffix) and its LCP array (lcp[0] = 0; lcp[j] = longest common prefix of the suffixes at sa[j - 1] and sa[j]; the end
+// of the text matches nothing) -- and what follows from it without a pattern.
+struct EnhancedSuffixArray {
+    std::vector<uint32_t> sa, lcp;
+};
+inline EnhancedSuffixArray bytestringToEnhancedSuffixArray(const std::string &bs) {
+    EnhancedSuffixArray e;
+    e.sa.resize(bs.size() + 1);
+    e.lcp.resize(bs.size() + 1);
+    Context::check(tc_lcp_array(Context::get(), (const uint8_t *)bs.data(), bs.size(), e.sa.data(), e.lcp.data()));
+    return e;
+}
+inline std::vector<uint32_t> bytestringToLCPArray(const std::string &bs) {
+    std::vector<uint32_t> lcp(bs.size() + 1);
+    Context::check(tc_lcp_array(Context::get(), (const uint8_t *)bs.data(), bs.size(), nullptr, lcp.data()));
+    return lcp;
+}
+// text, suffix array and LCP array resident in HBM (tc_suffix_array_dev, tc_lcp_array_dev: n + 1 entries each)
+inline void suffixArrayDev(const uint8_t *d_text, uint64_t n, uint32_t *d_sa) {
+    Context::check(tc_suffix_array_dev(Context::get(), d_text, n, d_sa));
+}
+inline void lcpArrayDev(const uint8_t *d_text, uint64_t n, const uint32_t *d_sa, uint32_t *d_lcp) {
+    Context::check(tc_lcp_array_dev(Context::get(), d_text, n, d_sa, d_lcp));
+}
+struct LCPSummary {
+    uint32_t maxLcp;   // the largest entry
+    uint64_t row;      // the smallest row holding it: rows row - 1 and row of the suffix array are the longest repeat
+    uint64_t sum;      // of all entries: the text has n (n + 1) / 2 - sum distinct substrings
+};
+inline LCPSummary lcpSummaryDev(const uint32_t *d_lcp, uint64_t N) {
+    LCPSummary s{};
+    Context::check(tc_lcp_summary_dev(Context::get(), d_lcp, N, &s.maxLcp, &s.row, &s.sum));
+    return s;
+}
 }  // namespace BWT
 
 namespace MTF {

@@ -24,6 +24,17 @@ foreign import ccall safe "tc_bwt_decode_sym"
   c_tc_bwt_decode_sym :: Ptr TcCtx -> Ptr Int16 -> Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
 foreign import ccall safe "tc_suffix_array"
   c_tc_suffix_array :: Ptr TcCtx -> Ptr Word8 -> Word64 -> Ptr Word32 -> IO Int32
+-- the enhanced suffix array (no counterpart in the reference): the suffix array with text and array in HBM, the LCP
+-- array that goes with it (n + 1 entries, lcp[0] = 0; the host form's sa may be nullPtr), and one reduction over an
+-- LCP array in HBM: largest entry, smallest row holding it, sum
+foreign import ccall safe "tc_suffix_array_dev"
+  c_tc_suffix_array_dev :: Ptr TcCtx -> Ptr Word8 -> Word64 -> Ptr Word32 -> IO Int32
+foreign import ccall safe "tc_lcp_array_dev"
+  c_tc_lcp_array_dev :: Ptr TcCtx -> Ptr Word8 -> Word64 -> Ptr Word32 -> Ptr Word32 -> IO Int32
+foreign import ccall safe "tc_lcp_array"
+  c_tc_lcp_array :: Ptr TcCtx -> Ptr Word8 -> Word64 -> Ptr Word32 -> Ptr Word32 -> IO Int32
+foreign import ccall safe "tc_lcp_summary_dev"
+  c_tc_lcp_summary_dev :: Ptr TcCtx -> Ptr Word32 -> Word64 -> Ptr Word32 -> Ptr Word64 -> Ptr Word64 -> IO Int32
 -- Data.MTF
 foreign import ccall safe "tc_mtf_encode_sym"
   c_tc_mtf_encode_sym :: Ptr TcCtx -> Ptr Int16 -> Word64 -> Ptr Word16 -> Ptr Int16 -> Ptr Word32 -> IO Int32

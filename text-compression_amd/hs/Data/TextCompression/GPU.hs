@@ -13,6 +13,8 @@ module Data.TextCompression.GPU
   , bytestringBWTToMTFB, bytestringBWTFromMTFB
   , bytestringBWTToRLEB, bytestringBWTFromRLEB
   , bytestringToBWTToFMIndexB
+  , bytestringToSuffixAndLCPArrays, bytestringToLCPArray
+  , suffixArrayDev, lcpArrayDev, lcpSummaryDev
   , bytestringFMIndexCountS, bytestringFMIndexCountP
   , bytestringFMIndexLocateS, bytestringFMIndexLocateP
   , bytestringFMIndexCountMismatchS, bytestringFMIndexCountMismatchP
@@ -165,6 +167,38 @@ bytestringBWTFromRLEB (RLE s)
           BWT . DS.fromList . map (fmap BS.singleton . ofSym) <$> peekArray m out
   where pairs (a : b : r) = (a, b) : pairs r
         pairs _ = []
+
+-- | No counterpart in the reference: the enhanced suffix array.  0-based starts, n + 1 rows, row 0 the empty suffix;
+-- lcp !! 0 = 0 and lcp !! j = the longest common prefix of the suffixes at sa !! (j - 1) and sa !! j (the end of the
+-- text matches nothing).  One device call: tc_lcp_array.
+bytestringToSuffixAndLCPArrays :: BS.ByteString -> ([Int], [Int])
+bytestringToSuffixAndLCPArrays bs = unsafePerformIO $ withCtx $ \ctx ->
+  BSU.unsafeUseAsCStringLen bs $ \(p, n) ->
+    allocaArray (n + 1) $ \ps -> allocaArray (n + 1) $ \pl -> do
+      c_tc_lcp_array ctx (castPtr p) (fromIntegral n) ps pl >>= check ctx
+      (,) <$> (map fromIntegral <$> peekArray (n + 1) ps) <*> (map fromIntegral <$> peekArray (n + 1) pl)
+
+-- | The LCP array alone (the suffix array stays on the device).
+bytestringToLCPArray :: BS.ByteString -> [Int]
+bytestringToLCPArray bs = unsafePerformIO $ withCtx $ \ctx ->
+  BSU.unsafeUseAsCStringLen bs $ \(p, n) ->
+    allocaArray (n + 1) $ \pl -> do
+      c_tc_lcp_array ctx (castPtr p) (fromIntegral n) nullPtr pl >>= check ctx
+      map fromIntegral <$> peekArray (n + 1) pl
+
+-- | Text, suffix array and LCP array resident in HBM (device pointers; n + 1 entries each): tc_suffix_array_dev,
+-- tc_lcp_array_dev, and tc_lcp_summary_dev = (largest entry, smallest row holding it, sum of all entries).
+suffixArrayDev :: Ptr Word8 -> Int -> Ptr Word32 -> IO ()
+suffixArrayDev dText n dSa = withCtx $ \ctx -> c_tc_suffix_array_dev ctx dText (fromIntegral n) dSa >>= check ctx
+
+lcpArrayDev :: Ptr Word8 -> Int -> Ptr Word32 -> Ptr Word32 -> IO ()
+lcpArrayDev dText n dSa dLcp = withCtx $ \ctx -> c_tc_lcp_array_dev ctx dText (fromIntegral n) dSa dLcp >>= check ctx
+
+lcpSummaryDev :: Ptr Word32 -> Int -> IO (Int, Int, Integer)
+lcpSummaryDev dLcp rows = withCtx $ \ctx ->
+  alloca $ \pm -> alloca $ \pr -> alloca $ \psum -> do
+    c_tc_lcp_summary_dev ctx dLcp (fromIntegral rows) pm pr psum >>= check ctx
+    (,,) <$> (fromIntegral <$> peek pm) <*> (fromIntegral <$> peek pr) <*> (fromIntegral <$> peek psum)
 
 -- | FMIndex.hs:108-111 (via bytestringBWTToFMIndexB :162-183): the FMIndex VALUE (Cc, OccCK, SA) -- sigma
 -- pairs, sigma x N triples and N suffix records, a shape for small inputs only (the reference builds it

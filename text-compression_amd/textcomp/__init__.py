@@ -139,6 +139,74 @@ class Context:
         self._check(self._lib.tc_suffix_array(self._h, _ptr(t) if len(t) else None, len(t), _ptr(sa)))
         return sa
 
+    # ------------------------------------- suffix array + LCP array (the enhanced suffix array)
+    def suffix_array_dev(self, d_text):
+        """text resident in HBM (a torch uint8 tensor on this context's device) -> its suffix array as an int32 tensor
+        of n + 1 entries on the device (the values are < 2^31): tc_suffix_array_dev"""
+        import torch
+        n = d_text.numel()
+        d_sa = torch.empty(n + 1, dtype=torch.int32, device=d_text.device)
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_suffix_array_dev(self._h, C.c_void_p(d_text.data_ptr()) if n else None, n,
+                                                  C.c_void_p(d_sa.data_ptr())))
+        return d_sa
+
+    def lcp_array_dev(self, d_text, d_sa):
+        """text and its suffix array resident in HBM -> the LCP array, an int32 tensor of n + 1 entries on the device:
+        tc_lcp_array_dev.  TcMalformed when d_sa is no permutation of 0 .. n."""
+        import torch
+        n = d_text.numel()
+        if d_sa.numel() != n + 1 or d_sa.element_size() != 4:
+            raise ValueError("d_sa must hold n + 1 32-bit entries")
+        d_lcp = torch.empty(n + 1, dtype=torch.int32, device=d_text.device)
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_lcp_array_dev(self._h, C.c_void_p(d_text.data_ptr()) if n else None, n,
+                                               C.c_void_p(d_sa.data_ptr()), C.c_void_p(d_lcp.data_ptr())))
+        return d_lcp
+
+    def lcp_summary_dev(self, d_lcp):
+        """an LCP array resident in HBM -> (largest entry, smallest row holding it, sum of all entries):
+        tc_lcp_summary_dev"""
+        import torch
+        mx, row, tot = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_lcp_summary_dev(self._h, C.c_void_p(d_lcp.data_ptr()), d_lcp.numel(), C.byref(mx),
+                                                 C.byref(row), C.byref(tot)))
+        return int(mx.value), int(row.value), int(tot.value)
+
+    def lcp_array(self, text):
+        """-> (sa, lcp), two uint32 arrays of n + 1 entries: lcp[0] = 0, lcp[j] = longest common prefix of the suffixes
+        at sa[j - 1] and sa[j] (tc_lcp_array)."""
+        t = _u8(text)
+        sa = np.empty(len(t) + 1, np.uint32)
+        lcp = np.empty(len(t) + 1, np.uint32)
+        self._check(self._lib.tc_lcp_array(self._h, _ptr(t) if len(t) else None, len(t), _ptr(sa), _ptr(lcp)))
+        return sa, lcp
+
+    def _esa_dev(self, text):
+        import torch
+        t = _u8(text)
+        d_text = torch.from_numpy(t.copy()).to("cuda:%d" % self.device)
+        d_sa = self.suffix_array_dev(d_text)
+        return d_sa, self.lcp_array_dev(d_text, d_sa)
+
+    def longest_repeat(self, text):
+        """-> (pos_a, pos_b, length), 0-based: text[pos_a : pos_a + length] == text[pos_b : pos_b + length] is a longest
+        substring that occurs twice (the two may overlap); of several the one first in suffix-array order: rows
+        row - 1 and row of the suffix array, row from tc_lcp_summary_dev.  No byte occurs twice: (0, 0, 0)."""
+        d_sa, d_lcp = self._esa_dev(text)
+        length, row, _ = self.lcp_summary_dev(d_lcp)
+        if length == 0:
+            return 0, 0, 0
+        pair = d_sa[row - 1:row + 1].cpu().tolist()
+        return int(pair[0]), int(pair[1]), length
+
+    def distinct_substrings(self, text):
+        """number of distinct non-empty substrings of text: n (n + 1) / 2 - sum(lcp)"""
+        n = len(_u8(text))
+        _, d_lcp = self._esa_dev(text)
+        return n * (n + 1) // 2 - self.lcp_summary_dev(d_lcp)[2]
+
     def bwt_decode(self, L, primary):
         L = _u8(L)
         N = len(L)

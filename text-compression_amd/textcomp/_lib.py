@@ -16,6 +16,8 @@ TC_MAX_ROUNDS = 40
 TC_CODING_PACKED, TC_CODING_HUFFMAN = 0, 1
 TC_FM_MAX_SA_RATE = 4096
 TC_FM_MAX_MISMATCH = 3
+TC_MAX_N = 0x7ffffff0
+TC_LCP_SHORT_CAP = 256   # csrc/tc_lcp.hpp: comparisons of the LCP array longer than this leave the one-lane kernel
 
 ERR_NAMES = {-1: "TC_ERR_ARG", -2: "TC_ERR_CAPACITY", -3: "TC_ERR_MALFORMED", -4: "TC_ERR_HIP",
              -5: "TC_ERR_OOM", -6: "TC_ERR_INTERNAL", -7: "TC_ERR_NCCL"}
@@ -69,6 +71,10 @@ SYMBOLS = [
     ("tc_bwt_encode", _INT, [_P, _P, _U64, _P, _PU64]),
     ("tc_bwt_encode_dev", _INT, [_P, _P, _U64, _P, _PU64]),
     ("tc_suffix_array", _INT, [_P, _P, _U64, _P]),
+    ("tc_suffix_array_dev", _INT, [_P, _P, _U64, _P]),
+    ("tc_lcp_array_dev", _INT, [_P, _P, _U64, _P, _P]),
+    ("tc_lcp_array", _INT, [_P, _P, _U64, _P, _P]),
+    ("tc_lcp_summary_dev", _INT, [_P, _P, _U64, _PU32, _PU64, _PU64]),
     ("tc_bwt_decode", _INT, [_P, _P, _U64, _U64, _P]),
     ("tc_bwt_decode_sym", _INT, [_P, _P, _U64, _P, _PU64]),
     ("tc_mtf_encode", _INT, [_P, _P, _U64, _I64, _P, _P, _PU32]),
