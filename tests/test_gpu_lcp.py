@@ -2,8 +2,9 @@
 against tests/lcp_ref.py, exactly.  Every text goes through both entry paths: the host form, and the two `_dev` calls
 on tensors.  The shapes are the smallest at which each kernel can go wrong: the wide-load tails at the end of the text,
 positions without a byte in front, values one below / on / above the short cap, a long item, a scan over several tiles
-with an odd remainder, many workgroups.  No test hands the device a malformed suffix array (host/check/lcp_kernels.cpp
-walks those under a host sanitizer)."""
+with an odd remainder, many workgroups.  The long-compare kernel's turn geometry, the short cap moved, and malformed
+suffix arrays through the library are test_gpu_lcp_long.py (host/check/lcp_kernels.cpp walks the same malformed arrays
+under a host sanitizer first)."""
 import ctypes as C
 
 import numpy as np

@@ -10,7 +10,13 @@
 //   - suffix arrays with an entry above n (in row 0, in the middle, in the last row), with a value twice (one missing),
 //     with row 0 repeated: the flag must be raised, and nothing out of bounds;
 //   - wrong permutations (reversed, rotated, random): no flag required, every value within n - max(sa[j-1], sa[j]),
-//     also with a long-item list of one slot, which such an array can overflow.
+//     also with a long-item list of one slot, which such an array can overflow;
+//   - planted pairs (a random block twice, one byte between) of 15 .. 14609 bytes, the second copy running to the end of
+//     the text or stopping at a differing byte, at caps 16, 32, 48 and 256: the one-lane turn is 32 bytes, so the end of
+//     the comparable bytes falls on every offset within a turn;
+//   - the texts and arrays of tests/test_gpu_lcp_long.py (its part e: n = 1000 and 4097, the same generator): rows set
+//     to n + 1 and 0xffffffff in row 0, the middle and the last row, a value twice, row 0's value repeated, the reversed
+//     and a shuffled permutation -- walked here before the device sees them.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -100,6 +106,93 @@ static void check_bounds(const std::vector<u32> &sa, const std::vector<u32> &lcp
     }
 }
 
+// the generator of tests/test_gpu_lcp_long.py (class Lcg), so that both walk the same texts and arrays
+struct Lcg {
+    u32 x;
+    u32 next() {
+        x = (u32)(((u64)x * 1103515245u + 12345u) & 0x7fffffffu);
+        return x >> 16;
+    }
+};
+
+// a random block of m bytes over 4 letters twice, '#' between; at_end: the text ends with the second copy, else '$' and
+// five more letters follow
+static std::vector<u8> planted_pair(std::mt19937_64 &rng, u32 m, bool at_end) {
+    std::vector<u8> b(m), t;
+    for (auto &c : b) c = (u8)"ACGT"[rng() % 4];
+    t.insert(t.end(), b.begin(), b.end());
+    t.push_back('#');
+    t.insert(t.end(), b.begin(), b.end());
+    if (!at_end) {
+        t.push_back('$');
+        for (int k = 0; k < 5; k++) t.push_back((u8)"ACGT"[rng() % 4]);
+    }
+    return t;
+}
+
+static u64 planted_pairs(std::mt19937_64 &rng) {
+    const u32 lengths[] = {15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 255, 256, 257, 272, 287, 288, 289, 1279, 2304, 6401, 14609};
+    const u32 caps[] = {16, 32, 48, 256};
+    u64 runs = 0;
+    for (u32 m : lengths)
+        for (int at_end = 0; at_end < 2; at_end++) {
+            const std::vector<u8> text = planted_pair(rng, m, at_end != 0);
+            std::vector<u32> sa, want, got;
+            reference(text, sa, want);
+            EXPECT(*std::max_element(want.begin(), want.end()) == m);
+            for (u32 cap : caps) {
+                EXPECT(run_lcp(text, sa, cap, list_cap_of(text.size(), cap), got) == 0);
+                EXPECT(got == want);
+                runs++;
+            }
+        }
+    return runs;
+}
+
+// part e of tests/test_gpu_lcp_long.py: the same text, the same arrays
+static u64 malformed_as_the_device_test(u32 n) {
+    Lcg g{n};
+    std::vector<u8> text(n);
+    for (auto &c : text) c = (u8)(65 + (g.next() & 1));
+    for (u32 k = 0; k < 300; k++) text[n / 2 + k] = text[k];
+    std::vector<u32> sa, want, got, bad;
+    reference(text, sa, want);
+    u64 arrays = 0;
+    for (u32 cap : {256u, 16u}) {
+        const u64 lc = list_cap_of(n, cap);
+        EXPECT(run_lcp(text, sa, cap, lc, got) == 0);
+        EXPECT(got == want);
+        for (u32 where : {0u, n / 2, n})
+            for (u32 value : {n + 1, 0xffffffffu}) {
+                bad = sa;
+                bad[where] = value;
+                EXPECT(run_lcp(text, bad, cap, lc, got) & LCP_ERR_SA);
+                check_bounds(bad, got, n);
+                arrays++;
+            }
+        bad = sa;
+        bad[n / 3] = sa[2 * n / 3];
+        EXPECT(run_lcp(text, bad, cap, lc, got) & LCP_ERR_SA);
+        check_bounds(bad, got, n);
+        bad = sa;
+        bad[n / 2 + 1] = sa[0];
+        EXPECT(run_lcp(text, bad, cap, lc, got) & LCP_ERR_SA);
+        check_bounds(bad, got, n);
+        // the two permutations must come back WITHOUT the flag: the device test expects a result from them
+        bad = sa;
+        std::reverse(bad.begin(), bad.end());
+        EXPECT(run_lcp(text, bad, cap, lc, got) == 0);
+        check_bounds(bad, got, n);
+        bad = sa;
+        Lcg h{n + 1};
+        for (u32 i = n; i > 0; i--) std::swap(bad[i], bad[h.next() % (i + 1)]);
+        EXPECT(run_lcp(text, bad, cap, lc, got) == 0);
+        check_bounds(bad, got, n);
+        arrays += 4;
+    }
+    return arrays;
+}
+
 int main() {
     std::mt19937_64 rng(0x1C9);
     const u32 alphabets[] = {1, 2, 4, 256};
@@ -178,7 +271,10 @@ int main() {
         }
     }
     EXPECT(long_runs > 20);
-    std::printf("lcp kernels: %llu texts x 3 caps exact (%llu runs with long items), malformed and wrong suffix arrays in bounds\n",
-                (unsigned long long)texts, (unsigned long long)long_runs);
+    const u64 pair_runs = planted_pairs(rng);
+    const u64 arrays = malformed_as_the_device_test(1000) + malformed_as_the_device_test(4097);
+    std::printf("lcp kernels: %llu texts x 3 caps exact (%llu runs with long items), %llu runs of planted pairs exact, malformed and "
+                "wrong suffix arrays in bounds (%llu of them the device test's)\n",
+                (unsigned long long)texts, (unsigned long long)long_runs, (unsigned long long)pair_runs, (unsigned long long)arrays);
     return 0;
 }
