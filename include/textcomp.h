@@ -108,10 +108,12 @@ typedef struct tc_stats {
  * no such container (it never feeds MTF output into RLE); this is
  * the documented glue: RLE runs over the MTF index stream as plain integers, with
  * the BWT primary index and the MTF final list (MTF/Internal.hs:125,140-141)
- * carried in the header. */
+ * carried in the header.
+ * Decode treats `primary` as a hint: the Nothing in the index stream decides (the
+ * reference's decode takes no primary).  A wrong one costs time, not correctness. */
 typedef struct tc_block {
     uint64_t n;                          /* out: input length */
-    uint64_t primary;                    /* out: BWT slot of Nothing */
+    uint64_t primary;                    /* out: BWT slot of Nothing (decode: a hint) */
     uint32_t sigma;                      /* out: MTF alphabet size */
     int16_t final_list[TC_MAX_SIGMA];    /* out: MTF list after the last move */
     uint64_t nruns;                      /* in: capacity of the run arrays; out: runs */
@@ -221,7 +223,17 @@ int tc_rle_decode_u16(tc_ctx *ctx, const uint32_t *counts, const uint16_t *run_v
 int tc_encode(tc_ctx *ctx, const uint8_t *text, uint64_t n, tc_block *out);
 /* d_text and out->run_count / out->run_value are device pointers. */
 int tc_encode_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, tc_block *out);
-/* Inverse chain: RLE -> MTF -> BWT decode; text receives blk->n bytes. */
+/* Inverse chain: RLE -> MTF -> BWT decode; text receives blk->n bytes.
+ * The block may come from anywhere: the answer is the reference's on the same runs and list
+ * (np.repeat, seqFromMTF over sort(unique(final_list)), magicInverseBWT) -- its text, or
+ * TC_ERR_MALFORMED where it throws or its text is not blk->n bytes long (runs that do not
+ * expand to n + 1 indices; an index >= the number of distinct list entries in a run of
+ * length >= 1; no Nothing, or a second one on the walk).  A run of length 0 indexes nothing,
+ * whatever its value.  blk->primary is a hint: a wrong one costs time, not correctness.
+ * final_list may be permuted, hold duplicates and hold symbols that never occur.
+ * TC_ERR_ARG: sigma > TC_MAX_SIGMA, or a list entry outside -1..255.  sigma == 0 with
+ * n > 0 decodes to the empty sequence (MTF/Internal.hs:202-209): TC_ERR_MALFORMED.
+ * Nothing behind text[n - 1] is written, whatever the block holds. */
 int tc_decode(tc_ctx *ctx, const tc_block *blk, uint8_t *text);
 int tc_decode_dev(tc_ctx *ctx, const tc_block *blk, uint8_t *d_text);
 

@@ -491,17 +491,17 @@ __global__ __launch_bounds__(RLD_NT) void rle_decode_fused_kernel(RleDecArgs a) 
             }
         }
         u64 len[RLD_RPT], mine = 0;
-        if (sizeof(OutT) < sizeof(SymT)) {   // narrowed output: a value that does not fit is out of range anyway
-            bool wide = false;
-#pragma unroll
-            for (int k = 0; k < RLD_RPT; k++) wide |= r0 + k < a.nruns && (u32)(u16)sv[k] > 255u;
-            if (wide) atomicOr(a.err, 0x100u);
-        }
 #pragma unroll
         for (int k = 0; k < RLD_RPT; k++) {
             const bool ok = r0 + k < a.nruns;
             len[k] = !ok ? 0ull : ((a.has_nothing && sv[k] == (SymT)-1) ? 1ull : (u64)c[k]);
             mine += len[k];
+        }
+        if (sizeof(OutT) < sizeof(SymT)) {   // narrowed output: a value that does not fit is out of range anyway --
+            bool wide = false;               // where it is written at all: a run of length 0 indexes nothing
+#pragma unroll
+            for (int k = 0; k < RLD_RPT; k++) wide |= len[k] != 0 && (u32)(u16)sv[k] > 255u;
+            if (wide) atomicOr(a.err, 0x100u);
         }
         const u64 inc = wave_incl_sum64(mine);
         if (l == 63) s_w[w] = inc;
