@@ -119,7 +119,7 @@ def genome_like(n, seed=0x6E0E):
     return t
 
 
-# ---- the device-side generators of the bench's classes leg (tc_generate_dev kinds 2 .. 6, csrc/textcomp.hip), restated in
+# ---- the device-side generators of the bench's classes leg (tc_generate_dev kinds 2 .. 6, csrc/tc_generate.hpp), restated in
 # numpy: the same integer function of (kind, seed, position), so that the oracle can encode what the device generates
 
 def _mix(seed, i):

@@ -91,3 +91,44 @@ def test_direct_copies_when_staging_is_off(ctx):
         assert ctx.encode_container(text) == want
     finally:
         os.environ.pop("TC_HOST_STAGED", None)
+
+
+def test_refused_host_decode_leaves_the_context_usable():
+    """tc_decode frees its device buffers on the way out of a refusal too: a block the fused decode refuses
+    (test_gpu_decode_foreign, M2 on acgtn-4096) gets the same code from the host form, and the same context then
+    decodes and round-trips as if nothing had happened"""
+    import textcomp
+    import oracle as O
+    import block_ref as B
+    from test_gpu_decode_foreign import _dev
+    blk = [b for _, b, exp in B.cases("M2", "acgtn", 4096) if exp == B.MALFORMED][0]
+    text = O.gen_acgtn(0x4097, 4097)
+    with textcomp.Context(0) as c:
+        with pytest.raises(textcomp.TcMalformed) as dev:
+            _dev(c, blk)
+        with pytest.raises(textcomp.TcMalformed) as host:
+            c.decode(blk)
+        assert host.value.code == dev.value.code == textcomp._lib.TC_ERR_MALFORMED
+        assert c.decode(c.encode(text)) == text.tobytes()
+        assert c.decode_container(c.encode_container(text)) == text.tobytes()
+
+
+def test_refused_stream_decode_leaves_the_context_usable():
+    """the stream loops give back their slots and streams on every way out: a damaged second record, then the intact
+    stream, then a capacity refusal of the encode, then the encode again, all on one context"""
+    import textcomp
+    import oracle as O
+    text = O.gen_acgtn(0x3000, 3000)
+    with textcomp.Context(0) as c:
+        blob = c.encode_stream(text, 1000)
+        assert c.stream_info(blob) == (3000, 3)
+        first, second = len(c.encode_stream(text[:1000], 1000)), len(c.encode_stream(text[1000:2000], 1000))
+        bad = bytearray(blob)
+        bad[first + textcomp._lib.TC_CONTAINER_HEADER + (second - textcomp._lib.TC_CONTAINER_HEADER) // 2] ^= 0x10   # payload of record 2
+        with pytest.raises(textcomp.TcMalformed):
+            c.decode_stream(bytes(bad))
+        assert c.decode_stream(blob) == text.tobytes()
+        with pytest.raises(textcomp.TcError) as e:
+            c.encode_stream(text, 1000, cap=len(blob) - 1)
+        assert e.value.code == textcomp._lib.TC_ERR_CAPACITY
+        assert c.encode_stream(text, 1000, cap=len(blob)) == blob

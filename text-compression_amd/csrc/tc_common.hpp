@@ -42,7 +42,7 @@ struct tc_ctx {
     int coding = 0;        // TC_CODING_*: the body the container writers produce (tc_ctx_set_container_coding)
     int num_cus = 0;
     int reserved_cus = 0;  // CUs left to a tc_comm's stream: the partition levels split their work over the others
-    void *hostpipe = nullptr;   // page-locked staging ring + persistent device buffers of the host entry points (textcomp.hip)
+    void *hostpipe = nullptr;   // page-locked staging ring + persistent device buffers of the host entry points (tc_hostio_host.hpp)
     u32 stats_ws_grown = 0;  // how often a chunked workspace grew in place
     u32 lcp_cap = 0;       // short cap of the LCP compare kernel set by tc_dbg_lcp_set_short_cap (0: TC_LCP_SHORT_CAP, tc_lcp.hpp)
     int mtf_fastin_failed = 0;  // the one-kernel MTF + RLE of this encode could not recover a tile's list by its backward scan:
@@ -121,7 +121,7 @@ static inline u32 tc_persistent_grid_for(tc_ctx *ctx, K kernel, int threads, int
     return tc_persistent_grid(ctx, occ < want_per_cu ? occ : want_per_cu);
 }
 // device memory as separately created physical chunks mapped into one address range (what the workspace of a long record
-// is made of: textcomp.hip); *handle releases it.  Returns null when the mapping is not available.
+// is made of: tc_ws_host.hpp); *handle releases it.  Returns null when the mapping is not available.
 void *tc_chunked_alloc(tc_ctx *ctx, size_t bytes, int chunk_log2, void **handle);
 void tc_chunked_free(void *handle);
 void tc_sync_check(tc_ctx *ctx);  // stream sync + device error word check

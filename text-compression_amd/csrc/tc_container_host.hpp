@@ -1,8 +1,7 @@
 // tc_container_host.hpp -- host side of the wire format: the run packers, the container header, the Huffman
-// body, text -> container on the device with its seal kernels, and the helpers of the chunked stream (kernels
+// body, text -> container on the device with its seal kernels, and the index of a chunked stream (kernels
 // of the bodies: tc_pack.hpp, tc_huff.hpp).  Included by textcomp.hip only.
 #pragma once
-#include <thread>
 #include <vector>
 
 #include "tc_encode_host.hpp"
@@ -649,29 +648,8 @@ static void encode_container_device(tc_ctx *ctx, const u8 *d_text, u64 n, u8 *d_
     container_write_device(ctx, &blk, d_out, bytes, pack_base);
 }
 
-// ---- what the chunked stream's two loops (textcomp.hip) stand on ---------------------------------------------------
-// one copy on a stream of its own, made and waited for by a helper thread
-struct CopyJob {
-    std::thread th;
-    hipError_t err = hipSuccess;
-    void start(int device, hipStream_t s, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
-        err = hipSuccess;
-        if (!bytes) return;
-        th = std::thread([this, device, s, dst, src, bytes, kind] {
-            hipError_t e = hipSetDevice(device);
-            if (e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, kind, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            err = e;
-        });
-    }
-    hipError_t join() {
-        if (th.joinable()) th.join();
-        return err;
-    }
-    ~CopyJob() { (void)join(); }
-};
-
-static u64 stream_blocks(u64 n, u64 block) { return n ? (n + block - 1) / block : 1; }
+// ---- the chunked stream as a wire format: the bound of a record's container and the walk over a stream's headers
+// (its two-slot pipeline: tc_hostio_host.hpp) ----------------------------------------------------------------------
 // room for the container of an n-byte record, whatever its alphabet
 static u64 container_bound_any(u64 n) {
     u64 b = 0;

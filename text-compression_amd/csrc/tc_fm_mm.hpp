@@ -42,7 +42,7 @@
 // interval of a pattern longer than log_sigma n is a single row.
 #pragma once
 
-#define FM_MM_MAXK 3   // = TC_FM_MAX_MISMATCH (textcomp.h; static_assert in textcomp.hip)
+#define FM_MM_MAXK 3   // = TC_FM_MAX_MISMATCH (textcomp.h; static_assert in tc_fm_host.hpp)
 
 // fm_occ2 in 32-bit arithmetic: Occ(v, k1) and Occ(v, k2), k1 <= k2 <= N < 2^32, from one line where both positions share
 // it.  Counts below 2^32 need only the low half of a line's ones-before word, and the payload is taken as 14 words of 32
