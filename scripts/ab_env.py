@@ -28,4 +28,4 @@ for spec in sys.argv[1:]:
             os.environ[var] = v
             acc[v].append(step())
     os.environ.pop(var, None)
-    print(var, " | ".join("%s: mean %.3f min %.3f ms" % (v, sum(a) / len(a), min(a)) for v, a in acc.items()), flush=True)
+    print(var, " | ".join("%s: mean %.3f min %.3f max %.3f ms" % (v, sum(a) / len(a), min(a), max(a)) for v, a in acc.items()), flush=True)

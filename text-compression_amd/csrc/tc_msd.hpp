@@ -257,10 +257,13 @@ struct MsdJointRows {
     u8 row[256];   // digit -> row of the LDS table, 0xff: none
     u8 dig[128];   // row -> digit
 };
-template <bool TEXT, bool JOINT>
-__global__ __launch_bounds__(MSD_NT) void msd_count_kernel(MsdLevel L, const u64 *__restrict__ keys,
-                                                           MsdTextDigit td, u32 *__restrict__ joint_out,
-                                                           MsdJointRows jr) {
+// HI (the split layout of level 1, see msd_partition_body): `keys` is the array of the keys' HIGH halves (32 bits a
+// key), which hold both digits of the pair -- half the bytes of the pass; read by 16-byte loads, four keys each.
+template <bool TEXT, bool JOINT, bool HI>
+__device__ __forceinline__ void msd_count_body(const MsdLevel &L, const u64 *__restrict__ keys,
+                                               const MsdTextDigit &td, u32 *__restrict__ joint_out,
+                                               const MsdJointRows &jr) {
+    static_assert(!HI || (!TEXT && JOINT), "the high halves serve the joint count of keys only");
     __shared__ u32 s_cnt[256];
     __shared__ u16 s_lut[TEXT ? 256 : 1];
     __shared__ u32 s_seg[4];   // q, lo, hi, next tile
@@ -350,8 +353,7 @@ __global__ __launch_bounds__(MSD_NT) void msd_count_kernel(MsdLevel L, const u64
                 atomicAdd(&s_cnt[g], 1u);
             }
         } else {
-            auto add = [&](u64 k) {
-                const u32 dd = (u32)(k >> (L.shift - 8)) & 0xffffu;   // digit, next digit
+            auto add_dd = [&](u32 dd) {   // dd: digit, next digit
                 if (JOINT) {
                     // (ONE atomic per key: the digit's own count is the sum of its row of the joint table, taken when
                     // the table is flushed at the segment's end; a digit without a row -- it holds the end marker: one
@@ -366,12 +368,37 @@ __global__ __launch_bounds__(MSD_NT) void msd_count_kernel(MsdLevel L, const u64
                     atomicAdd(&s_cnt[dd >> 8], 1u);
                 }
             };
-            u32 p = lo + tid;
-            for (; p + 3 * MSD_NT < hi; p += 4 * MSD_NT) {
-                const u64 k0 = keys[p], k1 = keys[p + MSD_NT], k2 = keys[p + 2 * MSD_NT], k3 = keys[p + 3 * MSD_NT];
-                add(k0); add(k1); add(k2); add(k3);
+            auto add = [&](u64 k) { add_dd((u32)(k >> (L.shift - 8)) & 0xffffu); };
+            if (HI) {
+                // (both digits lie in the high half: L.shift >= 40, the caller's condition)
+                const u32 *khi = reinterpret_cast<const u32 *>(keys);
+                const u32 hs = (u32)L.shift - 40u;
+                auto add4 = [&](const uint4 v) {
+                    add_dd((v.x >> hs) & 0xffffu); add_dd((v.y >> hs) & 0xffffu);
+                    add_dd((v.z >> hs) & 0xffffu); add_dd((v.w >> hs) & 0xffffu);
+                };
+                // the keys before the first aligned quad one by one, then quads -- four 16-byte loads in flight per
+                // thread (64 bytes; the 64-bit pass has 32) -- then the keys behind the last whole quad
+                const u32 a0 = (lo + 3u) & ~3u, a = a0 < hi ? a0 : hi;
+                if (lo + tid < a) add_dd((khi[lo + tid] >> hs) & 0xffffu);
+                const u32 nq = (hi - a) >> 2;
+                const uint4 *q4 = reinterpret_cast<const uint4 *>(khi + a);
+                u32 i = tid;
+                for (; i + 3 * MSD_NT < nq; i += 4 * MSD_NT) {
+                    const uint4 v0 = q4[i], v1 = q4[i + MSD_NT], v2 = q4[i + 2 * MSD_NT], v3 = q4[i + 3 * MSD_NT];
+                    add4(v0); add4(v1); add4(v2); add4(v3);
+                }
+                for (; i < nq; i += MSD_NT) add4(q4[i]);
+                const u32 p = a + 4 * nq + tid;
+                if (p < hi) add_dd((khi[p] >> hs) & 0xffffu);
+            } else {
+                u32 p = lo + tid;
+                for (; p + 3 * MSD_NT < hi; p += 4 * MSD_NT) {
+                    const u64 k0 = keys[p], k1 = keys[p + MSD_NT], k2 = keys[p + 2 * MSD_NT], k3 = keys[p + 3 * MSD_NT];
+                    add(k0); add(k1); add(k2); add(k3);
+                }
+                for (; p < hi; p += MSD_NT) add(keys[p]);
             }
-            for (; p < hi; p += MSD_NT) add(keys[p]);
         }
         __syncthreads();
         if (JOINT) {
@@ -391,6 +418,20 @@ __global__ __launch_bounds__(MSD_NT) void msd_count_kernel(MsdLevel L, const u64
         }
         // (the next round's barrier orders these resets before the next atomics)
     }
+}
+// (the kernels' names and template parameters are what tests/test_kernel_budgets.py finds them by: a new form of the
+// pass is a kernel of its own beside these, not another parameter)
+template <bool TEXT, bool JOINT>
+__global__ __launch_bounds__(MSD_NT) void msd_count_kernel(MsdLevel L, const u64 *__restrict__ keys,
+                                                           MsdTextDigit td, u32 *__restrict__ joint_out,
+                                                           MsdJointRows jr) {
+    msd_count_body<TEXT, JOINT, false>(L, keys, td, joint_out, jr);
+}
+// the joint count of a level whose input is the split layout: reads khi alone
+__global__ __launch_bounds__(MSD_NT) void msd_count_hi_kernel(MsdLevel L, const u32 *__restrict__ khi,
+                                                              MsdTextDigit td, u32 *__restrict__ joint_out,
+                                                              MsdJointRows jr) {
+    msd_count_body<false, true, true>(L, reinterpret_cast<const u64 *>(khi), td, joint_out, jr);
 }
 
 // ---- counts -> child ranges and per-segment bases ---------------------------------------------
@@ -476,10 +517,16 @@ typedef u32 msd_u32x4 __attribute__((ext_vector_type(4)));
 // (BWT -> MTF -> RLE) needs the last column, which rides in the key's low byte; the suffix START is needed only
 // for the few suffixes that stay tied beyond the key, and those are found again afterwards by one pass over the
 // text (tied_probe_kernel, tc_sa.hpp).  Callers that want the suffix array itself keep VALS = true.
-template <bool KEYGEN, bool VALS = true>
-__global__ __launch_bounds__(MSD_NT) void msd_partition_kernel(MsdLevel L, const u64 *kin, const u32 *vin,
-                                                               u64 *kout, u32 *vout, const u8 *text,
-                                                               RadixKeyGen kg) {
+// SPLIT (the key-only levels 1 and 2 when level 2's joint count is on): level 1 stores every key as two 32-bit halves in
+// two arrays -- shi[p] = key bits 63..32 (fields 0-3), slo[p] = bits 31..0 (fields 4-6 and the last-column byte) -- so
+// that the joint count, which needs bits 55..40 only, reads 4 bytes a suffix instead of 8 (msd_count_hi_kernel).  A
+// store group is still whole requests: 16 keys x 4 bytes = 64 bytes per half.  KEYGEN && SPLIT: (shi, slo) is the OUTPUT
+// and kout is unused; !KEYGEN && SPLIT: (shi, slo) is the INPUT in place of kin, the output is 64-bit keys as ever.
+template <bool KEYGEN, bool VALS, bool SPLIT>
+__device__ __forceinline__ void msd_partition_body(const MsdLevel &L, const u64 *kin, const u32 *vin,
+                                                   u64 *kout, u32 *vout, u32 *shi, u32 *slo, const u8 *text,
+                                                   const RadixKeyGen &kg) {
+    static_assert(!SPLIT || !VALS, "the split layout is the key-only levels'");
     // (no __restrict__ on purpose: loads that may alias the stores keep their place in program order)
     // staging of the tile sorted by digit; the key-generation image overlays it
     __shared__ __attribute__((aligned(16))) u64 s_keys[MSD_TILE];
@@ -595,7 +642,8 @@ __global__ __launch_bounds__(MSD_NT) void msd_partition_kernel(MsdLevel L, const
             key[k] = 0;
             val[k] = 0;
             if (p < f.valid) {
-                key[k] = kin[f.base + p];
+                if (SPLIT) key[k] = (u64)shi[f.base + p] << 32 | slo[f.base + p];
+                else key[k] = kin[f.base + p];
                 if (VALS) val[k] = vin[f.base + p];
             }
         }
@@ -612,17 +660,24 @@ __global__ __launch_bounds__(MSD_NT) void msd_partition_kernel(MsdLevel L, const
         } else {
             const bool safe = tile_safe(nx);
             const u32 nb = safe ? nx.base : 0u;   // (an unsafe or absent next tile: any valid tile)
-            const u32 nv = safe ? nx.valid : (u32)MSD_TILE;
+            // (arrays shorter than a tile: their whole quads only)
+            const u32 nv = safe ? nx.valid : (L.ntot < (u32)MSD_TILE ? L.ntot & ~3u : (u32)MSD_TILE);
 #pragma unroll
             for (int g = 0; g < MSD_ITEMS / 4; g++) {
                 // (a quad wholly past the tile's last pair -- the last tile of a parent -- re-reads the
                 // tile's first quad instead of the next parent's pairs: no HBM traffic for ignored data)
                 u32 gs = (u32)g * (4 * MSD_NT) + 4 * tid;
                 gs = gs < nv ? gs : 0u;
-                const u64 *kp = kin + nb + gs;
                 const u32 *vp = vin + nb + gs;
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(nk4[2 * g]) : "v"(kp) : "memory");
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(nk4[2 * g + 1]) : "v"(kp + 2) : "memory");
+                if (SPLIT) {   // the quad's four high halves, then its four low halves
+                    const u32 *hp = shi + nb + gs, *lp = slo + nb + gs;
+                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(nk4[2 * g]) : "v"(hp) : "memory");
+                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(nk4[2 * g + 1]) : "v"(lp) : "memory");
+                } else {
+                    const u64 *kp = kin + nb + gs;
+                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(nk4[2 * g]) : "v"(kp) : "memory");
+                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(nk4[2 * g + 1]) : "v"(kp + 2) : "memory");
+                }
                 if (VALS) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(nv4[g]) : "v"(vp) : "memory");
             }
         }
@@ -937,8 +992,15 @@ __global__ __launch_bounds__(MSD_NT) void msd_partition_kernel(MsdLevel L, const
         } else {
 #pragma unroll
             for (int k = 0; k < MSD_ITEMS; k++) {
-                const msd_u32x4 q4 = nk4[k >> 1];
-                key[k] = (k & 1) ? ((u64)q4.w << 32 | q4.z) : ((u64)q4.y << 32 | q4.x);
+                if (SPLIT) {
+                    const msd_u32x4 h4 = nk4[2 * (k >> 2)], l4 = nk4[2 * (k >> 2) + 1];
+                    const u32 h = (k & 3) == 0 ? h4.x : (k & 3) == 1 ? h4.y : (k & 3) == 2 ? h4.z : h4.w;
+                    const u32 l = (k & 3) == 0 ? l4.x : (k & 3) == 1 ? l4.y : (k & 3) == 2 ? l4.z : l4.w;
+                    key[k] = (u64)h << 32 | l;
+                } else {
+                    const msd_u32x4 q4 = nk4[k >> 1];
+                    key[k] = (k & 1) ? ((u64)q4.w << 32 | q4.z) : ((u64)q4.y << 32 | q4.x);
+                }
                 if (VALS) {
                     const msd_u32x4 v4 = nv4[k >> 2];
                     val[k] = (k & 3) == 0 ? v4.x : (k & 3) == 1 ? v4.y : (k & 3) == 2 ? v4.z : v4.w;
@@ -980,7 +1042,12 @@ __global__ __launch_bounds__(MSD_NT) void msd_partition_kernel(MsdLevel L, const
                         if (VALS) vv = s_vals[ds + e - r];
                     }
                     if (k > 0 || l >= ph) {
-                        kout[cur + e] = kk;
+                        if (KEYGEN && SPLIT) {
+                            shi[cur + e] = (u32)(kk >> 32);
+                            slo[cur + e] = (u32)kk;
+                        } else {
+                            kout[cur + e] = kk;
+                        }
                         if (VALS) vout[cur + e] = vv;
                     }
                 }
@@ -1023,7 +1090,13 @@ __global__ __launch_bounds__(MSD_NT) void msd_partition_kernel(MsdLevel L, const
                 const u32 d = x / MSD_GROUP, j = x % MSD_GROUP;
                 if (j >= s_ph[d] && j < s_r[d]) {
                     const u32 pos = s_cur[d] + j;
-                    kout[pos] = c_keys[x];
+                    if (KEYGEN && SPLIT) {
+                        const u64 kk = c_keys[x];
+                        shi[pos] = (u32)(kk >> 32);
+                        slo[pos] = (u32)kk;
+                    } else {
+                        kout[pos] = c_keys[x];
+                    }
                     if (VALS) vout[pos] = c_vals[x];
                 }
             }
@@ -1032,6 +1105,22 @@ __global__ __launch_bounds__(MSD_NT) void msd_partition_kernel(MsdLevel L, const
         }
     }
 }
+// (names and template parameters are what tests/test_kernel_budgets.py and scripts/check_asm_prefetch.py find these
+// kernels by: the split layout has kernels of its own, below)
+template <bool KEYGEN, bool VALS = true>
+__global__ __launch_bounds__(MSD_NT) void msd_partition_kernel(MsdLevel L, const u64 *kin, const u32 *vin,
+                                                               u64 *kout, u32 *vout, const u8 *text,
+                                                               RadixKeyGen kg) {
+    msd_partition_body<KEYGEN, VALS, false>(L, kin, vin, kout, vout, nullptr, nullptr, text, kg);
+}
+// key-only levels in the split layout.  KEYGEN (level 1): text -> (khi, klo).  Else (level 2): (khi, klo) -> kout.
+template <bool KEYGEN>
+__global__ __launch_bounds__(MSD_NT) void msd_partition_split_kernel(MsdLevel L, u32 *khi, u32 *klo, u64 *kout,
+                                                                     const u8 *text, RadixKeyGen kg) {
+    msd_partition_body<KEYGEN, false, true>(L, nullptr, nullptr, kout, nullptr, khi, klo, text, kg);
+}
+// elements of one half of the split layout: N rounded up so that klo = khi + npad starts a 128-byte line
+static inline size_t msd_split_npad(size_t N) { return (N + 31) & ~(size_t)31; }
 
 // ---- finish: every level-3 bucket ordered by its remaining key bits ----------------------------------
 // (the equal-mass bin map of the finish kernels: see msd_finish_ko_kernel below)

@@ -58,10 +58,12 @@ struct SaBuffers {
 
 // the MSD round 0 pays from this many suffixes on (level-3 buckets of >= ~64 members on DNA)
 static inline u64 msd_min_n() { return (u64)env_int("TC_SA_MSD_MIN_LOG2", 27) >= 40 ? ~0ull : 1ull << env_int("TC_SA_MSD_MIN_LOG2", 27); }
-static inline bool msd_wanted(u64 N) { return env_int("TC_SA_MSD", 1) != 0 && N >= msd_min_n() && N > 4 * MSD_TILE; }
+// (and from 1024 suffixes on whatever the variable says: the partition kernels' stand-in addresses -- a quad of the arrays,
+// 16 aligned bytes of the text -- must exist; texts of less than a tile are one tile, loaded pair by pair)
+static inline bool msd_wanted(u64 N) { return env_int("TC_SA_MSD", 1) != 0 && N >= msd_min_n() && N >= 1024; }
 
 static size_t sa_carve(Arena &A, u64 N, SaBuffers &b, bool own_v1) {
-    b.k0 = A.get<u64>(N);
+    b.k0 = A.get<u64>(N + 32);   // (+ 32: as two arrays of 32-bit halves -- the split layout of MSD level 1 -- each half is rounded up to a 128-byte line)
     b.k1 = A.get<u64>(N);
     b.v0 = A.get<u32>(N);
     b.v1 = own_v1 ? A.get<u32>(N) : nullptr;
@@ -701,6 +703,12 @@ static Round0Out sa_round0_msd(SaRun &R, const Round0Plan &pl, bool keyonly) {
         }
     }
     const bool joint = R.K.msd_joint != 0 && nrows <= 128;
+    // Split layout (tc_msd.hpp: msd_partition_body; TC_MSD_SPLIT=0: off): key-only levels with the joint count -- level 1
+    // leaves the keys as two arrays of 32-bit halves in k0 (khi at its start, klo npad elements on), the joint count reads
+    // khi alone, level 2 reads both and writes 64-bit keys as ever.  Everything behind level 2 sees no difference.
+    const bool split = keyonly && joint && R.K.msd_split != 0 && MSD_LEVELS == 3;
+    u32 *khi = reinterpret_cast<u32 *>(b.k0), *klo = khi + msd_split_npad(N);
+    ctx->msd_split_used = split ? 1 : 0;
     if (joint) tc_memset_async(ctx, b.msd_joint, 0, (size_t)256 * 256 * 256 * sizeof(u32));
     u32 np = 1;
     for (int l = 0; l < MSD_LEVELS; l++, np *= 256) {
@@ -717,6 +725,7 @@ static Round0Out sa_round0_msd(SaRun &R, const Round0Plan &pl, bool keyonly) {
         TC_LAUNCH_CHECK(ctx);
         if (l == 0) msd_count_kernel<true, false><<<G, MSD_NT, 0, s>>>(ML, nullptr, td, nullptr, jr);
         else if (ML.aligned) { /* counts already in msd_joint */ }
+        else if (joint && l == MSD_LEVELS - 2 && split) msd_count_hi_kernel<<<G, MSD_NT, 0, s>>>(ML, khi, td, b.msd_joint, jr);
         else if (joint && l == MSD_LEVELS - 2) msd_count_kernel<false, true><<<G, MSD_NT, 0, s>>>(ML, kin, td, b.msd_joint, jr);
         else msd_count_kernel<false, false><<<G, MSD_NT, 0, s>>>(ML, kin, td, nullptr, jr);
         TC_LAUNCH_CHECK(ctx);
@@ -724,7 +733,10 @@ static Round0Out sa_round0_msd(SaRun &R, const Round0Plan &pl, bool keyonly) {
         TC_LAUNCH_CHECK(ctx);
         const bool ev = ctx->profile && ctx->pev_used < 16;
         if (ev) TC_HIP(ctx, hipEventRecord(ctx->pev[2 * ctx->pev_used], s));
-        if (keyonly) {
+        if (split && l <= 1) {
+            if (l == 0) msd_partition_split_kernel<true><<<G, MSD_NT, 0, s>>>(ML, khi, klo, nullptr, R.text, kg);
+            else msd_partition_split_kernel<false><<<G, MSD_NT, 0, s>>>(ML, khi, klo, kbuf[1], R.text, kg);
+        } else if (keyonly) {
             if (l == 0) msd_partition_kernel<true, false><<<G, MSD_NT, 0, s>>>(ML, nullptr, nullptr, kbuf[0], nullptr, R.text, kg);
             else msd_partition_kernel<false, false><<<G, MSD_NT, 0, s>>>(ML, kin, nullptr, kbuf[l & 1], nullptr, R.text, kg);
         } else if (l == 0) msd_partition_kernel<true><<<G, MSD_NT, 0, s>>>(ML, nullptr, nullptr, kbuf[0], vbuf[0], R.text, kg);
@@ -999,6 +1011,7 @@ static bool sa_round0(SaRun &R, bool &hopeless, bool &many_ties) {
         }
     }
     if (res == R0_GIVE_WAY) {
+        R.ctx->msd_split_used = 0;
         Round0Out o = sa_round0_lsd(R, pl);
         res = sa_round0_collect(R, o, pl.keyround, many_ties);
     }
@@ -1289,6 +1302,7 @@ static void sa_run(tc_ctx *ctx, SaBuffers &b, const u8 *d_text, u64 n, u32 *d_sa
     R.part_act1_ok = (size_t)((char *)b.act[1][2] - (char *)b.act[1][0]) >= N * sizeof(u64) &&
                      ((uintptr_t)b.act[1][0] & 7) == 0;
     sa_trace_buffers(R);
+    ctx->msd_split_used = 0;
     if (sa_alphabet(R, counts256_out, primary)) return;
 
     const u32 P_full = R.cfg.P;   // fields chosen for the full path (every field is a pass there)

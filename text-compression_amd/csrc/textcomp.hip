@@ -626,6 +626,12 @@ int tc_dbg_lcp_set_short_cap(tc_ctx *ctx, uint32_t cap) {
     return TC_OK;
 }
 
+int tc_dbg_msd_split_used(tc_ctx *ctx, uint32_t *used) {
+    if (!ctx || !used) return TC_ERR_ARG;
+    *used = ctx->msd_split_used ? 1u : 0u;
+    return TC_OK;
+}
+
 int tc_dbg_dispatch_probe(tc_ctx *ctx, uint32_t grid, uint32_t lds_bytes, uint32_t spin_cycles, uint32_t *out6) {
     TC_API_BEGIN(ctx)
     dbg_dispatch_probe_entry(ctx, grid, lds_bytes, spin_cycles, out6);
