@@ -37,6 +37,11 @@ int tc_dbg_lcp_set_short_cap(tc_ctx *ctx, uint32_t cap);
  * the split key layout (csrc/tc_msd.hpp: two arrays of 32-bit key halves; TC_MSD_SPLIT), 0 if not -- the LSD way, levels
  * that move suffix starts, TC_SA_MSD_JOINT=0, or a second run of the levels with suffix starts. */
 int tc_dbg_msd_split_used(tc_ctx *ctx, uint32_t *used);
+/* out[0] = 1 if round 0 of this context's last suffix sort went the MSD way and its aligned level (level 3 with the joint
+ * table) kept the directory of its live parents in LDS (csrc/tc_msd.hpp, csrc/tc_msd_dir.hpp; TC_MSD_DIR), 0 if not -- the
+ * LSD way, TC_SA_MSD_JOINT=0, TC_MSD_DIR=0.  out[1] = the fills of that directory, summed over the workgroups (one per
+ * round of slots a workgroup looked at; 0 where out[0] is 0). */
+int tc_dbg_msd_dir(tc_ctx *ctx, uint32_t out[2]);
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@
 // collision sample say the text is not iid-like (tc_sa_plan.hpp: sa_round0_plan).
 #pragma once
 #include "tc_sa.hpp"
+#include "tc_msd_dir.hpp"
 
 #ifndef MSD_NT
 #define MSD_NT 1024
@@ -85,6 +86,7 @@ struct MsdLevel {
     const u32 *cnt_in;   // [nparents * 256] (aligned levels)
     u32 *flags;          // device word: bit 3 = the joint counts of an aligned level do not add up
     u64 *dbg;            // MSD_PROFILE builds: [16] cycles per phase of workgroup 0 (wave 0; [9]: the last wave)
+    u32 *dirfills;       // device word: fills of the directory of live parents, summed over workgroups (aligned levels, DIR)
 };
 
 #ifdef __HIPCC__
@@ -94,10 +96,11 @@ __device__ __forceinline__ u32 msd_block_of_tile(u32 T, u32 t, u32 G) {
     return (u32)((((u64)t + 1) * G - 1) / T);   // largest b with tile_lo(b) <= t
 }
 
-__global__ void msd_root_kernel(u32 *pstart, u32 *pcnt, u32 N, u32 *maxchild) {
+__global__ void msd_root_kernel(u32 *pstart, u32 *pcnt, u32 N, u32 *maxchild, u32 *dirfills) {
     pstart[0] = 0;
     pcnt[0] = N;
     *maxchild = 0;
+    *dirfills = 0;
 }
 
 // aligned levels: workgroup of parent q, and the first parent of workgroup b
@@ -522,11 +525,23 @@ typedef u32 msd_u32x4 __attribute__((ext_vector_type(4)));
 // that the joint count, which needs bits 55..40 only, reads 4 bytes a suffix instead of 8 (msd_count_hi_kernel).  A
 // store group is still whole requests: 16 keys x 4 bytes = 64 bytes per half.  KEYGEN && SPLIT: (shi, slo) is the OUTPUT
 // and kout is unused; !KEYGEN && SPLIT: (shi, slo) is the INPUT in place of kin, the output is 64-bit keys as ever.
-template <bool KEYGEN, bool VALS, bool SPLIT>
+// DIR (aligned levels only; TC_MSD_DIR=0: off): the end of a segment reads no global memory.  With the plain cursor
+// (msd_cur_info) a boundary between two parents was a chain of dependent loads on the critical path of all 1024 threads --
+// thread 0 walking tpre over the empty slots, then tpre / pstart / pcnt of the parent it found, each wait also draining the
+// wave's store burst; then the two digit rows of seg_init, behind the stores of the carry flush -- 61 boundaries per
+// workgroup at 1 GiB (level 3: 3.76 ms against level 2's 3.45 for the same bytes; 3.26 with this).  Here (i) the
+// workgroup's live parents stand in an LDS directory (tc_msd_dir.hpp), filled by all threads at once -- a batch of
+// slots per round, independent loads, compacted by ballot and popcount -- and
+// thread 0's cursor reads LDS only; it is refilled at an end of a segment when the look-ahead has run past it; (ii) the
+// digit rows of the NEXT live parent are loaded right behind the prefetch of a segment's first tile and put into an LDS
+// shadow behind land() of the same tile, which waits for vmcnt(0) anyway; seg_init at the boundary copies them from there
+// (it falls back to the global rows when the shadow holds another parent: after a refill).
+template <bool KEYGEN, bool VALS, bool SPLIT, bool DIR = false>
 __device__ __forceinline__ void msd_partition_body(const MsdLevel &L, const u64 *kin, const u32 *vin,
                                                    u64 *kout, u32 *vout, u32 *shi, u32 *slo, const u8 *text,
                                                    const RadixKeyGen &kg) {
     static_assert(!SPLIT || !VALS, "the split layout is the key-only levels'");
+    static_assert(!DIR || (!KEYGEN && !SPLIT), "the directory is the aligned level's");
     // (no __restrict__ on purpose: loads that may alias the stores keep their place in program order)
     // staging of the tile sorted by digit; the key-generation image overlays it
     __shared__ __attribute__((aligned(16))) u64 s_keys[MSD_TILE];
@@ -556,14 +571,33 @@ __device__ __forceinline__ void msd_partition_body(const MsdLevel &L, const u64 
     __shared__ __attribute__((aligned(16))) u8 s_kg8[KG_SPLIT ? MSD_TILE + 64 : 16];
     __shared__ u32 s_scan2[2];
     static_assert(MSD_GROUP == 8 || MSD_GROUP == 16 || MSD_GROUP == 32, "group = 8, 16 or 32 pairs");
-    static_assert(((size_t)MSD_TILE * (VALS ? 12 : 8) + 256 * MSD_GROUP * (VALS ? 12 : 8) + 8192 + (KG_SPLIT ? 2 * MSD_TILE + 256 : 0)) * (VALS ? 1 : MSD_BPC) <= 163840, "LDS budget");
+    // DIR: the directory (key-only: the slots of a workgroup at 1 GiB fit four times; with values: what the budget leaves),
+    // the shadow of the next parent's digit rows, and the cursor's few words
+    constexpr u32 DIRCAP = DIR ? (VALS ? 128 : 1024) : 1;
+    __shared__ MsdDirEnt s_dir[DIRCAP];
+    __shared__ u32 s_rseg[DIR ? 256 : 1];
+    __shared__ u64 s_rmask[4];
+    __shared__ u32 s_nq[4], s_dst[6];   // s_dst: [0] filled entries [1] next slot [2] end of the slots [3] pending tiles [4] parent of the shadow [5] scratch
+    static_assert(((size_t)MSD_TILE * (VALS ? 12 : 8) + 256 * MSD_GROUP * (VALS ? 12 : 8) + 8192 + (KG_SPLIT ? 2 * MSD_TILE + 256 : 0) + (DIR ? DIRCAP * sizeof(MsdDirEnt) + 1024 + 128 : 0)) * (VALS ? 1 : MSD_BPC) <= 163840, "LDS budget");
     __shared__ MsdTileInfo s_info[4];
 
     const u32 tid = threadIdx.x, G = gridDim.x, b = msd_logical_wg(blockIdx.x, G);
     if (KEYGEN && tid < 256) s_klut[tid] = kg.lut[tid];
     if (tid < 256) { s_r[tid] = 0; s_ph[tid] = 0; s_cur[tid] = 0; }
     for (u32 i = tid; i < 256 * MSD_SUB; i += MSD_NT) s_cnt[i] = 0;
-    if (tid == 0) {
+    if (DIR) {
+        // the two ends of the workgroup's slots by two threads of different waves (tpre is read here and nowhere else)
+        if (tid == 0 || tid == 64) {
+            const u32 w = tid >> 6;
+            u32 q = 0, tq = 0;
+            if (!(*L.flags & 8u)) {   // bad joint counts: do nothing
+                q = msd_first_parent(L, b + w, G);
+                tq = L.tpre[q];
+            }
+            s_scan2[w] = tq; s_dst[1 + w] = q;
+        }
+        if (tid == 0) { s_dst[0] = 0; s_dst[3] = 0; s_dst[4] = MSD_DIR_NONE; }
+    } else if (tid == 0) {
         u32 ta = 0, tb = 0;
         if (!(L.aligned && (*L.flags & 8u))) msd_block_range(L, b, G, &ta, &tb);   // bad joint counts: do nothing
         s_scan2[0] = ta; s_scan2[1] = tb;
@@ -572,7 +606,54 @@ __device__ __forceinline__ void msd_partition_body(const MsdLevel &L, const u64 
     const u32 t0 = s_scan2[0], t1 = s_scan2[1];
     if (t0 >= t1) return;
     MsdCur cs = {};
-    if (tid == 0) {
+    // DIR: a fill, by all threads (every decision in it is block-uniform).  Nothing filled lies ahead of the cursor when it
+    // is called.  Rounds of MSD_NT slots -- pcnt and pstart of a slot per thread, the live ones compacted in slot order --
+    // until a live parent is found or the slots are used up; what a round finds beyond the capacity waits for the next fill.
+    u32 dir_e = 0, dir_k = 0;   // thread 0: the cursor (MsdDirCur; the rest of it lives in s_dst)
+    auto dir_refill = [&]() {
+        u32 n = 0, qn = s_dst[1];
+        const u32 qe = s_dst[2];
+        while (n == 0 && qn < qe) {
+            const u32 q = qn + tid;
+            const bool in = q < qe;
+            const u32 pc = in ? L.pcnt[q] : 0u, ps = in ? L.pstart[q] : 0u;
+            const u64 m = __ballot(pc != 0);
+            if ((tid & 63) == 0) s_scan[tid >> 6] = (u32)__popcll(m);
+            __syncthreads();
+            u32 before = 0, tot = 0;
+#pragma unroll
+            for (u32 i = 0; i < MSD_NT / 64; i++) {
+                const u32 c = s_scan[i];
+                tot += c;
+                before += i < (tid >> 6) ? c : 0u;
+            }
+            const u32 rank = before + (u32)__popcll(m & ((1ull << (tid & 63)) - 1ull));
+            if (pc != 0 && rank < DIRCAP) { s_dir[rank].q = q; s_dir[rank].ps = ps; s_dir[rank].pc = pc; }
+            if (pc != 0 && rank == DIRCAP) s_dst[5] = q;   // the first live slot that does not fit
+            __syncthreads();
+            if (tot > DIRCAP) { n = DIRCAP; qn = s_dst[5]; }
+            else { n = tot; qn = qe - qn < (u32)MSD_NT ? qe : qn + MSD_NT; }
+            if (tid == 0) atomicAdd(L.dirfills, 1u);
+        }
+        __syncthreads();   // (everyone has read s_dst[1], s_dst[5])
+        if (tid == 0) { s_dst[0] = n; s_dst[1] = qn; s_dst[3] = 0; }
+        dir_e = 0; dir_k = 0;
+    };
+    auto dir_gen = [&](u32 x) {   // thread 0: the description of tile x, from LDS alone
+        MsdDirCur c = {dir_e, dir_k, s_dst[0], s_dst[1], s_dst[2], s_dst[3]};
+        MsdDirTile d;
+        u32 nq;
+        msd_dir_next(s_dir, c, MSD_TILE, &d, &nq);
+        dir_e = c.e; dir_k = c.k; s_dst[3] = c.pend;
+        MsdTileInfo *o = &s_info[(x - t0) & 3u];
+        o->base = d.base; o->valid = d.valid; o->q = d.q; o->last = d.last;
+        s_nq[(x - t0) & 3u] = nq;
+    };
+    if (DIR) {
+        dir_refill();
+        __syncthreads();
+        if (tid == 0) { dir_gen(t0); dir_gen(t0 + 1); dir_gen(t0 + 2); }
+    } else if (tid == 0) {
         msd_cur_init(L, cs, t0);
         msd_cur_info(L, cs, t0, t1, &s_info[0]);
         msd_cur_info(L, cs, t0 + 1, t1, &s_info[1]);
@@ -751,6 +832,13 @@ __device__ __forceinline__ void msd_partition_body(const MsdLevel &L, const u64 
         const u64 m = __ballot(L.ccnt[(size_t)qq * 256 + tid] != 0);
         if ((tid & 63) == 0) s_lmask[tid >> 6] = m;
     };
+    auto seg_init_shadow = [&]() {   // threads < 256; DIR: the same from the shadow of the rows
+        const u32 sb = s_rseg[tid];
+        s_cur[tid] = sb & ~(u32)(MSD_GROUP - 1);
+        s_ph[tid] = sb & (MSD_GROUP - 1);
+        s_r[tid] = sb & (MSD_GROUP - 1);
+        if ((tid & 63) == 0) s_lmask[tid >> 6] = s_rmask[tid >> 6];
+    };
     if (tid < 256) seg_init(s_info[0].q);
     // The first tile comes by ordinary loads.  Their registers then pass through an empty asm: the compiler
     // waits for them HERE and from then on regards them as asm-defined.  Otherwise its wait-count model
@@ -784,6 +872,8 @@ __device__ __forceinline__ void msd_partition_body(const MsdLevel &L, const u64 
         if (tid < 3) gen_group(s_kr, s_kg8, MSD_NT + tid);
     }
 
+    u32 row_s = 0, row_c = 0;   // DIR: the next parent's digit rows on their way to the shadow
+    bool seg_first = true, plain_next = false;   // DIR (block-uniform): first tile of its segment; tile that no prefetch fetched
     for (u32 t = t0; t < t1; t++) {
         const u32 slot = (t - t0) & 3u;
         const MsdTileInfo ti = s_info[slot];
@@ -791,18 +881,37 @@ __device__ __forceinline__ void msd_partition_body(const MsdLevel &L, const u64 
         u64 tq[8];
         tq[0] = __builtin_readcyclecounter();
 #endif
-        if (tid == 0) msd_cur_info(L, cs, t + 3, t1, &s_info[(slot + 3) & 3u]);
+        if (tid == 0) {
+            if (DIR) dir_gen(t + 3);
+            else msd_cur_info(L, cs, t + 3, t1, &s_info[(slot + 3) & 3u]);
+        }
         __syncthreads();   // (B0) s_cnt zeroed; staging free; carries / ranges of this segment in place
 #ifdef MSD_PROFILE
         const u64 t_b0 = __builtin_readcyclecounter();
 #endif
         const MsdTileInfo nx = s_info[(slot + 1) & 3u];
+        // DIR: the descriptions that are pending behind this tile (thread 0 wrote the word before B0 and writes it again
+        // behind B1 at the earliest), and the parent whose rows this tile fetches
+        const u32 dpend = DIR ? s_dst[3] : 0u;
+        const u32 rq = DIR && seg_first ? s_nq[slot] : MSD_DIR_NONE;
+        const bool rows = DIR && rq != MSD_DIR_NONE && tid < 256;
         prefetch(ti, nx);   // tile t + 1: in flight while tile t is ranked and staged
+        if (rows) {
+            // (issued by asm like the prefetch and for its reason: as ordinary loads the compiler gave them a vmcnt wait right
+            // here -- it hoists the test of the count -- which waits for the prefetch as well.  The two registers live across
+            // the loop and are written by these loads alone; land() is their wait.)
+            const u32 *ps = L.seg + ((size_t)rq + b) * 256 + tid, *pc = L.ccnt + (size_t)rq * 256 + tid;
+            asm volatile("global_load_dword %0, %2, off\n\tglobal_load_dword %1, %3, off"
+                         : "+v"(row_s), "+v"(row_c)
+                         : "v"(ps), "v"(pc)
+                         : "memory");
+        }
         if (KEYGEN && kg_edge(ti)) {   // first / last tile: ordinary loads, bounds-checked
             raw = kg_load_plain(ti);
             detach();
         }
-        if (!KEYGEN && t != t0 && !tile_safe(ti)) {   // the tile that reaches past the arrays' end: pair by pair
+        if (!KEYGEN && t != t0 && (!tile_safe(ti) || (DIR && plain_next))) {   // the tile that reaches past the arrays' end
+                                                                                // (or came behind a refill): pair by pair
             load_plain(ti);
             detach();
         }
@@ -985,6 +1094,13 @@ __device__ __forceinline__ void msd_partition_body(const MsdLevel &L, const u64 
 #ifdef MSD_PROFILE
         tq[5] = __builtin_readcyclecounter();
 #endif
+        if (rows) {   // visible behind B3; read at the end of this segment
+            asm volatile("" : "+v"(row_s), "+v"(row_c) : : "memory");
+            s_rseg[tid] = row_s;
+            const u64 m = __ballot(row_c != 0);
+            if ((tid & 63) == 0) s_rmask[tid >> 6] = m;
+            if (tid == 0) s_dst[4] = rq;
+        }
         const bool kg_next = KG_SPLIT && kg_fast(nx);
         if (KEYGEN) {
             raw = nraw;
@@ -1082,6 +1198,9 @@ __device__ __forceinline__ void msd_partition_body(const MsdLevel &L, const u64 
             L.dbg[5] += tq[5] - tq[4]; L.dbg[6] += tq[6] - tq[5]; L.dbg[7] += tq[7] - tq[6]; L.dbg[1] += 1;
         }
 #endif
+#ifdef MSD_PROFILE
+        const u64 t_end0 = __builtin_readcyclecounter();
+#endif
         if (ti.last) {
             // end of the segment: the carries go to their exact places (partial lines, once per
             // segment and digit); then the next segment's ranges are taken
@@ -1101,8 +1220,30 @@ __device__ __forceinline__ void msd_partition_body(const MsdLevel &L, const u64 
                 }
             }
             __syncthreads();
-            if (t + 1 < t1 && tid < 256) seg_init(s_info[(slot + 1) & 3u].q);
+            if (DIR) {
+                plain_next = false;
+                if (dpend) {   // the look-ahead ran past the directory: fill it, and ask again for what was pending
+                    dir_refill();
+                    __syncthreads();
+                    if (tid == 0)
+                        for (u32 x = t + 4 - dpend; x <= t + 3; x++) dir_gen(x);
+                    __syncthreads();
+                    plain_next = dpend == 3;   // tile t + 1 was not known when this tile prefetched
+                }
+                if (t + 1 < t1 && tid < 256) {
+                    const u32 q2 = s_info[(slot + 1) & 3u].q;
+                    if (s_dst[4] == q2) seg_init_shadow();
+                    else seg_init(q2);
+                }
+            } else if (t + 1 < t1 && tid < 256) seg_init(s_info[(slot + 1) & 3u].q);
         }
+#ifdef MSD_PROFILE
+        if (b == 0 && tid == 0 && L.dbg && ti.last) {   // [12] end of a segment (flush, barriers, the next segment's ranges)  [13] how many
+            L.dbg[12] += __builtin_readcyclecounter() - t_end0;
+            L.dbg[13] += 1;
+        }
+#endif
+        seg_first = ti.last != 0;
     }
 }
 // (names and template parameters are what tests/test_kernel_budgets.py and scripts/check_asm_prefetch.py find these
@@ -1118,6 +1259,12 @@ template <bool KEYGEN>
 __global__ __launch_bounds__(MSD_NT) void msd_partition_split_kernel(MsdLevel L, u32 *khi, u32 *klo, u64 *kout,
                                                                      const u8 *text, RadixKeyGen kg) {
     msd_partition_body<KEYGEN, false, true>(L, nullptr, nullptr, kout, nullptr, khi, klo, text, kg);
+}
+// the aligned level with the directory of live parents (msd_partition_body, DIR)
+template <bool VALS>
+__global__ __launch_bounds__(MSD_NT) void msd_partition_dir_kernel(MsdLevel L, const u64 *kin, const u32 *vin, u64 *kout,
+                                                                   u32 *vout, RadixKeyGen kg) {
+    msd_partition_body<false, VALS, false, true>(L, kin, vin, kout, vout, nullptr, nullptr, nullptr, kg);
 }
 // elements of one half of the split layout: N rounded up so that klo = khi + npad starts a 128-byte line
 static inline size_t msd_split_npad(size_t N) { return (N + 31) & ~(size_t)31; }

@@ -145,6 +145,7 @@ enum SaSlot {
     SA_SLOT_ERR = 62,         // (host only) the device error word as ticket_check read it
     SA_SLOT_MSD_PROF = 64,    // (device only, MSD_PROFILE) 16 words per MSD level
     SA_SLOT_MSDK_PROF = 112,  // (device only, MSDK_PROFILE) 10 words
+    SA_SLOT_MSD_DIR = 122,    // (device only) low half: directory fills of the aligned MSD level, summed over workgroups
 };
 static inline u32 sa_slot_lo(const tc_ctx *ctx, int slot) { return (u32)(ctx->h_scalars[slot] & 0xffffffffu); }
 static inline u32 sa_slot_hi(const tc_ctx *ctx, int slot) { return (u32)(ctx->h_scalars[slot] >> 32); }
@@ -450,11 +451,26 @@ static void msd_profile_dump(tc_ctx *ctx) {   // cycles per phase of workgroup 0
         fprintf(stderr, "   level %d, S1 alone per tile: wave 0 %llu, last wave %llu cycles; slowest wave B0 -> before B1 %llu, B0 -> prefetch issued %llu\n", l + 1,
                 (unsigned long long)(h[16 * l + 8] / (h[16 * l + 1] | 1)), (unsigned long long)(h[16 * l + 9] / (h[16 * l + 1] | 1)),
                 (unsigned long long)(h[16 * l + 10] / (h[16 * l + 1] | 1)), (unsigned long long)(h[16 * l + 11] / (h[16 * l + 1] | 1)));
+    for (int l = 0; l < MSD_LEVELS; l++)
+        fprintf(stderr, "   level %d, ends of segments: %llu, %llu cycles each (flush, barriers, next ranges; outside the per-tile stamps)\n", l + 1,
+                (unsigned long long)h[16 * l + 13], (unsigned long long)(h[16 * l + 12] / (h[16 * l + 13] | 1)));
     tc_memset_async(ctx, ctx->d_scalars + SA_SLOT_MSD_PROF, 0, sizeof h);
 }
 #else
 static inline void msd_profile_dump(tc_ctx *) {}
 #endif
+
+// tc_dbg_msd_dir: whether the last sort's aligned level kept its directory, and the fills the device counted
+static void sa_dbg_msd_dir(tc_ctx *ctx, uint32_t out[2]) {
+    u64 w = 0;
+    out[0] = ctx->msd_dir_used ? 1u : 0u;
+    out[1] = 0;
+    if (ctx->msd_dir_used) {   // (the word is the last sort's: msd_root_kernel zeroes it)
+        tc_d2h(ctx, &w, ctx->d_scalars + SA_SLOT_MSD_DIR, sizeof w);
+        TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        out[1] = (u32)(w & 0xffffffffu);
+    }
+}
 
 // ---- shared steps ----------------------------------------------------------------------------------------------
 // group_kernel over sorted (keys, vals) as `ga` describes them; fills in the text, the outputs and the look-back words.
@@ -674,7 +690,7 @@ static Round0Out sa_round0_msd(SaRun &R, const Round0Plan &pl, bool keyonly) {
         G = (u32)(ctx->num_cus - ctx->reserved_cus) * MSD_BPC;   // (CUs left to the exchange: tc_comm_create)
     if (R.K.msd_grid > 0 && (u32)R.K.msd_grid < G) G = (u32)R.K.msd_grid;
     u32 *maxchild = sa_dev_slot(ctx, SA_SLOT_MAXCHILD);
-    msd_root_kernel<<<1, 1, 0, s>>>(b.msd_pstart[0], b.msd_pcnt[0], N, maxchild);
+    msd_root_kernel<<<1, 1, 0, s>>>(b.msd_pstart[0], b.msd_pcnt[0], N, maxchild, sa_dev_slot(ctx, SA_SLOT_MSD_DIR));
     TC_LAUNCH_CHECK(ctx);
     // level 1 writes (k0, v0); level 2 (k1, sa); level 3 (k0, v0); the finish reads (k0, v0)
     // and writes sa / L
@@ -709,6 +725,9 @@ static Round0Out sa_round0_msd(SaRun &R, const Round0Plan &pl, bool keyonly) {
     const bool split = keyonly && joint && R.K.msd_split != 0 && MSD_LEVELS == 3;
     u32 *khi = reinterpret_cast<u32 *>(b.k0), *klo = khi + msd_split_npad(N);
     ctx->msd_split_used = split ? 1 : 0;
+    // Directory of live parents (tc_msd.hpp: msd_partition_body, DIR; TC_MSD_DIR=0: off): the aligned level only
+    const bool dir = joint && R.K.msd_dir != 0;
+    ctx->msd_dir_used = dir ? 1 : 0;
     if (joint) tc_memset_async(ctx, b.msd_joint, 0, (size_t)256 * 256 * 256 * sizeof(u32));
     u32 np = 1;
     for (int l = 0; l < MSD_LEVELS; l++, np *= 256) {
@@ -719,6 +738,7 @@ static Round0Out sa_round0_msd(SaRun &R, const Round0Plan &pl, bool keyonly) {
         ML.aligned = (joint && l == MSD_LEVELS - 1) ? 1 : 0;
         ML.ntot = N; ML.cnt_in = b.msd_joint; ML.flags = counters + 1;
         ML.dbg = ctx->d_scalars + SA_SLOT_MSD_PROF + 16 * l;
+        ML.dirfills = sa_dev_slot(ctx, SA_SLOT_MSD_DIR);
         const u64 *kin = l ? kbuf[(l - 1) & 1] : nullptr;
         const u32 *vin = l ? vbuf[(l - 1) & 1] : nullptr;
         msd_prep_kernel<<<1, 1024, 0, s>>>(ML.pcnt, np, b.msd_tpre[l]);
@@ -736,6 +756,9 @@ static Round0Out sa_round0_msd(SaRun &R, const Round0Plan &pl, bool keyonly) {
         if (split && l <= 1) {
             if (l == 0) msd_partition_split_kernel<true><<<G, MSD_NT, 0, s>>>(ML, khi, klo, nullptr, R.text, kg);
             else msd_partition_split_kernel<false><<<G, MSD_NT, 0, s>>>(ML, khi, klo, kbuf[1], R.text, kg);
+        } else if (dir && ML.aligned) {
+            if (keyonly) msd_partition_dir_kernel<false><<<G, MSD_NT, 0, s>>>(ML, kin, nullptr, kbuf[l & 1], nullptr, kg);
+            else msd_partition_dir_kernel<true><<<G, MSD_NT, 0, s>>>(ML, kin, vin, kbuf[l & 1], vbuf[l & 1], kg);
         } else if (keyonly) {
             if (l == 0) msd_partition_kernel<true, false><<<G, MSD_NT, 0, s>>>(ML, nullptr, nullptr, kbuf[0], nullptr, R.text, kg);
             else msd_partition_kernel<false, false><<<G, MSD_NT, 0, s>>>(ML, kin, nullptr, kbuf[l & 1], nullptr, R.text, kg);
@@ -1012,6 +1035,7 @@ static bool sa_round0(SaRun &R, bool &hopeless, bool &many_ties) {
     }
     if (res == R0_GIVE_WAY) {
         R.ctx->msd_split_used = 0;
+        R.ctx->msd_dir_used = 0;
         Round0Out o = sa_round0_lsd(R, pl);
         res = sa_round0_collect(R, o, pl.keyround, many_ties);
     }
@@ -1303,6 +1327,7 @@ static void sa_run(tc_ctx *ctx, SaBuffers &b, const u8 *d_text, u64 n, u32 *d_sa
                      ((uintptr_t)b.act[1][0] & 7) == 0;
     sa_trace_buffers(R);
     ctx->msd_split_used = 0;
+    ctx->msd_dir_used = 0;
     if (sa_alphabet(R, counts256_out, primary)) return;
 
     const u32 P_full = R.cfg.P;   // fields chosen for the full path (every field is a pass there)

@@ -632,6 +632,13 @@ int tc_dbg_msd_split_used(tc_ctx *ctx, uint32_t *used) {
     return TC_OK;
 }
 
+int tc_dbg_msd_dir(tc_ctx *ctx, uint32_t out[2]) {
+    TC_API_BEGIN(ctx)
+    if (!out) TC_FAIL(ctx, TC_ERR_ARG, "out is null");
+    sa_dbg_msd_dir(ctx, out);
+    TC_API_END(ctx)
+}
+
 int tc_dbg_dispatch_probe(tc_ctx *ctx, uint32_t grid, uint32_t lds_bytes, uint32_t spin_cycles, uint32_t *out6) {
     TC_API_BEGIN(ctx)
     dbg_dispatch_probe_entry(ctx, grid, lds_bytes, spin_cycles, out6);
