@@ -42,6 +42,21 @@ int tc_dbg_msd_split_used(tc_ctx *ctx, uint32_t *used);
  * LSD way, TC_SA_MSD_JOINT=0, TC_MSD_DIR=0.  out[1] = the fills of that directory, summed over the workgroups (one per
  * round of slots a workgroup looked at; 0 where out[0] is 0). */
 int tc_dbg_msd_dir(tc_ctx *ctx, uint32_t out[2]);
+/* The sort of one doubling round (seg_sort_pairs, csrc/tc_sa_host.hpp; kernels in csrc/tc_seg.hpp) on the caller's pairs,
+ * staged through the context's workspace with the run and tile tables a text of m suffixes gets.  keys[i] = grp << 32 | rank,
+ * grp non-decreasing, rank < 2^rbits (rbits 1 .. 32); 1 <= m <= 2^24; all host arrays.  On return keys / vals hold the
+ * result: inside every run of equal grp the members ordered by rank.  Members with equal keys come in no defined order.
+ * levels[2L], levels[2L + 1] = the long runs (above 1024 members) and the 4096-member tiles the host read back before
+ * partition level L (L < 8); zeros after the last.  TC_ERR_ARG: a null pointer, m or rbits out of range, a grp that
+ * decreases, a rank of more than rbits bits -- nothing ran.  TC_ERR_INTERNAL: runs left after 8 levels. */
+int tc_dbg_seg_sort(tc_ctx *ctx, uint64_t *keys, uint32_t *vals, uint32_t m, int rbits, uint32_t levels[16]);
+/* tied_small_kernel<mode> (csrc/tc_seg.hpp: one workgroup, the same network) on 1 <= m <= 4096 members; all host arrays.
+ * mode 0: (slot, idx, grp) sorted by slot in place, entries with slot = 0xffffffff last; t_idx / t_rank / tpos ignored.
+ * mode 1: slot is not looked at; idx distinct; t_idx = idx sorted, t_rank[c] = grp of the member at row c, tpos[k] = the row
+ * of member k -- as table_build_kernel (csrc/tc_sa.hpp) defines them; slot / idx / grp unchanged.
+ * TC_ERR_ARG: another mode, m out of range, a null pointer among those the mode uses. */
+int tc_dbg_tied_small(tc_ctx *ctx, int mode, uint32_t *slot, uint32_t *idx, uint32_t *grp, uint32_t m,
+                      uint32_t *t_idx, uint32_t *t_rank, uint32_t *tpos);
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,9 @@
 // tc_dbg_host.hpp -- the calibration and debug interface (include/textcomp_debug.h): the kernels that measure the memory
 // system without any of the pipeline's work, and the bodies of the tc_dbg_* calls.  Included by textcomp.hip only, after
-// tc_container_host.hpp (checksum64_device) and tc_ws_host.hpp.
+// tc_container_host.hpp (checksum64_device), tc_encode_host.hpp (seg_sort_pairs, seg_carve) and tc_ws_host.hpp.
 #pragma once
 #include "tc_container_host.hpp"
+#include "tc_encode_host.hpp"
 #include "tc_radix_host.hpp"
 
 // ------------------------------------------------------------ calibration kernels
@@ -228,5 +229,49 @@ static void dbg_sort_bench_entry(tc_ctx *ctx, u64 n, int key_bits, int iters, in
     }
     ctx->profile = saved;
     *ms_per_pass = launches ? total / launches : 0;
+    tc_sync_check(ctx);
+}
+
+// ------------------------------------------------------------ the segmented sort and the one-workgroup network on the caller's data
+// tc_dbg_seg_sort: seg_sort_pairs (tc_sa_host.hpp) as a doubling round calls it, on pairs staged through the workspace,
+// with the tables a text of m suffixes gets (seg_carve).  No kernel of its own.
+static void dbg_seg_sort_entry(tc_ctx *ctx, u64 *keys, u32 *vals, u32 m, int rbits, u32 *levels) {
+    if (!keys || !vals || !levels || m < 1 || m > (1u << 24) || rbits < 1 || rbits > 32) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    for (u32 i = 0; i < m; i++) {
+        if (i && (keys[i] >> 32) < (keys[i - 1] >> 32)) TC_FAIL(ctx, TC_ERR_ARG, "grp decreases at member %u", i);
+        if (rbits < 32 && ((u32)keys[i] >> rbits) != 0) TC_FAIL(ctx, TC_ERR_ARG, "rank of member %u has more than %d bits", i, rbits);
+    }
+    SegBuffers g;
+    u64 *kx = nullptr, *ky = nullptr;
+    u32 *vx = nullptr, *vy = nullptr;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+        kx = A.get<u64>(m); ky = A.get<u64>(m);
+        vx = A.get<u32>(m); vy = A.get<u32>(m);
+        seg_carve(A, m, g);
+    });
+    tc_h2d(ctx, kx, keys, (size_t)m * sizeof(u64));
+    tc_h2d(ctx, vx, vals, (size_t)m * sizeof(u32));
+    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    seg_sort_pairs(ctx, g, kx, vx, ky, vy, m, rbits, levels);
+    tc_d2h(ctx, keys, kx, (size_t)m * sizeof(u64));
+    tc_d2h(ctx, vals, vx, (size_t)m * sizeof(u32));
+    tc_sync_check(ctx);
+}
+// tc_dbg_tied_small: tied_small_kernel<mode> (tc_seg.hpp) as sa_order_tied (mode 0) and the sparse rank table (mode 1) launch it
+static void dbg_tied_small_entry(tc_ctx *ctx, int mode, u32 *slot, u32 *idx, u32 *grp, u32 m, u32 *t_idx, u32 *t_rank, u32 *tpos) {
+    if ((mode != 0 && mode != 1) || !slot || !idx || !grp || m < 1 || m > SEG_W) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    if (mode == 1 && (!t_idx || !t_rank || !tpos)) TC_FAIL(ctx, TC_ERR_ARG, "mode 1 needs t_idx, t_rank and tpos");
+    u32 *d[6] = {};
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+        for (int q = 0; q < 6; q++) d[q] = A.get<u32>(m);
+    });
+    u32 *const h_in[3] = {slot, idx, grp};
+    for (int q = 0; q < 3; q++) tc_h2d(ctx, d[q], h_in[q], (size_t)m * sizeof(u32));
+    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (mode == 0) tied_small_kernel<0><<<1, SEG_NT, 0, ctx->stream>>>(d[0], d[1], d[2], m, nullptr, nullptr, nullptr);
+    else tied_small_kernel<1><<<1, SEG_NT, 0, ctx->stream>>>(d[0], d[1], d[2], m, d[3], d[4], d[5]);
+    TC_LAUNCH_CHECK(ctx);
+    u32 *const h_out[3] = {mode == 0 ? slot : t_idx, mode == 0 ? idx : t_rank, mode == 0 ? grp : tpos};
+    for (int q = 0; q < 3; q++) tc_d2h(ctx, h_out[q], d[mode == 0 ? q : 3 + q], (size_t)m * sizeof(u32));
     tc_sync_check(ctx);
 }

@@ -62,6 +62,25 @@ static inline u64 msd_min_n() { return (u64)env_int("TC_SA_MSD_MIN_LOG2", 27) >=
 // 16 aligned bytes of the text -- must exist; texts of less than a tile are one tile, loaded pair by pair)
 static inline bool msd_wanted(u64 N) { return env_int("TC_SA_MSD", 1) != 0 && N >= msd_min_n() && N >= 1024; }
 
+// The tables of the segmented sort (tc_seg.hpp) for N slots, in the order sa_carve has always carved them; the debug entry
+// tc_dbg_seg_sort carves the same for its m pairs, so a test runs with the cap_runs / cap_tiles of a text of m suffixes.
+static void seg_carve(Arena &A, u64 N, SegBuffers &g) {
+    g.cap_runs = (size_t)(N / SEG_CAP + 2);
+    g.cap_tiles = (size_t)(N / SEG_PT + 2) + g.cap_runs;
+    g.segbits = A.get<u64>(seg_bit_words(N));
+    g.ybits = A.get<u64>(seg_bit_words(N));
+    for (int q = 0; q < 2; q++) {
+        g.lstart[q] = A.get<u32>(g.cap_runs);
+        g.lsize[q] = A.get<u32>(g.cap_runs);
+        g.ltbase[q] = A.get<u32>(g.cap_runs);
+        g.lshift[q] = A.get<u32>(g.cap_runs);
+    }
+    g.tile_seg = A.get<u32>(g.cap_tiles);
+    g.hist = A.get<u32>(g.cap_runs * 256);
+    g.mm = A.get<u32>(g.cap_runs * 2);
+    g.counters = A.get<u32>(64);
+}
+
 static size_t sa_carve(Arena &A, u64 N, SaBuffers &b, bool own_v1) {
     b.k0 = A.get<u64>(N + 32);   // (+ 32: as two arrays of 32-bit halves -- the split layout of MSD level 1 -- each half is rounded up to a 128-byte line)
     b.k1 = A.get<u64>(N);
@@ -87,23 +106,7 @@ static size_t sa_carve(Arena &A, u64 N, SaBuffers &b, bool own_v1) {
     b.rstatus = A.get<u64>(radix_status_words(N));
     b.gstatus = A.get<u64>(2 * (size_t)tc_cdiv(N, GRP_TILE) + 4);
     b.counts = A.get<u32>(260);
-    {
-        SegBuffers &g = b.seg;
-        g.cap_runs = (size_t)(N / SEG_CAP + 2);
-        g.cap_tiles = (size_t)(N / SEG_PT + 2) + g.cap_runs;
-        g.segbits = A.get<u64>(seg_bit_words(N));
-        g.ybits = A.get<u64>(seg_bit_words(N));
-        for (int q = 0; q < 2; q++) {
-            g.lstart[q] = A.get<u32>(g.cap_runs);
-            g.lsize[q] = A.get<u32>(g.cap_runs);
-            g.ltbase[q] = A.get<u32>(g.cap_runs);
-            g.lshift[q] = A.get<u32>(g.cap_runs);
-        }
-        g.tile_seg = A.get<u32>(g.cap_tiles);
-        g.hist = A.get<u32>(g.cap_runs * 256);
-        g.mm = A.get<u32>(g.cap_runs * 2);
-        g.counters = A.get<u32>(64);
-    }
+    seg_carve(A, N, b.seg);
     for (int l = 0; l <= MSD_LEVELS; l++) b.msd_pstart[l] = b.msd_pcnt[l] = nullptr;
     if (msd_wanted(N)) {
         b.msd_grid = 256 * MSD_BPC;   // fixed for the carve; the launch uses min(this, CUs x workgroups per CU)
@@ -169,9 +172,12 @@ static inline void seg_profile_dump(tc_ctx *, u32) {}
 
 // The sort of one doubling round (tc_seg.hpp): keys (grp << 32 | rank, grp non-decreasing) and values, m members, ranks
 // below 2^rbits.  The result is in (kx, vx); (ky, vy) is scratch of the same size.  One host synchronisation per
-// partition level that has long runs (none: one, for the count of long runs).
-static void seg_sort_pairs(tc_ctx *ctx, SegBuffers &g, u64 *kx, u32 *vx, u64 *ky, u32 *vy, u32 m, int rbits) {
+// partition level that has long runs (none: one, for the count of long runs).  levels (host, 16 words, optional; tests):
+// [2L], [2L + 1] = the long runs and tiles read back before level L, zeros after the last.
+static void seg_sort_pairs(tc_ctx *ctx, SegBuffers &g, u64 *kx, u32 *vx, u64 *ky, u32 *vy, u32 m, int rbits,
+                           u32 *levels = nullptr) {
     hipStream_t s = ctx->stream;
+    if (levels) memset(levels, 0, 16 * sizeof(u32));
     const u32 nwords = (u32)seg_bit_words(m);
     TC_HIP(ctx, hipMemsetAsync(g.ybits, 0, (size_t)nwords * sizeof(u64), s));
     TC_HIP(ctx, hipMemsetAsync(g.counters, 0, 8 * sizeof(u32), s));
@@ -189,6 +195,7 @@ static void seg_sort_pairs(tc_ctx *ctx, SegBuffers &g, u64 *kx, u32 *vx, u64 *ky
         TC_HIP(ctx, hipStreamSynchronize(s));
         const u32 S = sa_slot_lo(ctx, SA_SLOT_SEG), T = sa_slot_hi(ctx, SA_SLOT_SEG);
         if (S == 0) break;
+        if (levels && L < nlev) { levels[2 * L] = S; levels[2 * L + 1] = T; }
         if (L >= nlev) TC_FAIL(ctx, TC_ERR_INTERNAL, "segmented sort: %u runs still unsorted after %d levels", S, nlev);
         if (S > g.cap_runs || T > g.cap_tiles) TC_FAIL(ctx, TC_ERR_INTERNAL, "segmented sort: %u long runs / %u tiles exceed the tables", S, T);
         const int nxt = cur ^ 1;

@@ -651,4 +651,17 @@ int tc_dbg_sort_bench(tc_ctx *ctx, uint64_t n, int key_bits, int iters, int chec
     TC_API_END(ctx)
 }
 
+int tc_dbg_seg_sort(tc_ctx *ctx, uint64_t *keys, uint32_t *vals, uint32_t m, int rbits, uint32_t levels[16]) {
+    TC_API_BEGIN(ctx)
+    dbg_seg_sort_entry(ctx, keys, vals, m, rbits, levels);
+    TC_API_END(ctx)
+}
+
+int tc_dbg_tied_small(tc_ctx *ctx, int mode, uint32_t *slot, uint32_t *idx, uint32_t *grp, uint32_t m, uint32_t *t_idx,
+                      uint32_t *t_rank, uint32_t *tpos) {
+    TC_API_BEGIN(ctx)
+    dbg_tied_small_entry(ctx, mode, slot, idx, grp, m, t_idx, t_rank, tpos);
+    TC_API_END(ctx)
+}
+
 }  // extern "C"
