@@ -42,6 +42,13 @@ int tc_dbg_msd_split_used(tc_ctx *ctx, uint32_t *used);
  * LSD way, TC_SA_MSD_JOINT=0, TC_MSD_DIR=0.  out[1] = the fills of that directory, summed over the workgroups (one per
  * round of slots a workgroup looked at; 0 where out[0] is 0). */
 int tc_dbg_msd_dir(tc_ctx *ctx, uint32_t out[2]);
+/* What the splitter walks of this context's last inverse BWT (a decode runs one; csrc/tc_ibwt.hpp, ibwt_walk_rank_copy in
+ * csrc/tc_decode_host.hpp) did.  out[0] = the attempts run: 1, or 2 when the walks of the first wanted more extra splitter
+ * slots than there are and were repeated the old way; 0 if no walk ran (a column without a Nothing).  Of the last attempt:
+ * out[1] = the records that overflowed (their segments are walked a second time; TC_IBWT_REWALK=1 marks every record so),
+ * out[2] = the extra slots asked for by walks whose record filled up (TC_IBWT_SEGCAP lowers that fill; more than the
+ * K / 32 + 256 slots of K splitters only in a first attempt that was then repeated). */
+int tc_dbg_ibwt_walk(tc_ctx *ctx, uint32_t out[3]);
 /* The sort of one doubling round (seg_sort_pairs, csrc/tc_sa_host.hpp; kernels in csrc/tc_seg.hpp) on the caller's pairs,
  * staged through the context's workspace with the run and tile tables a text of m suffixes gets.  keys[i] = grp << 32 | rank,
  * grp non-decreasing, rank < 2^rbits (rbits 1 .. 32); 1 <= m <= 2^24; all host arrays.  On return keys / vals hold the

@@ -121,7 +121,19 @@ def test_ibwt_path_selectors(ctx, env, monkeypatch):
     dedicated scatter; every recorded segment treated as overflowed and walked again; small alphabets
     by positions instead of by LF over the packed last column; the inverse MTF of a small alphabet on the
     byte-list kernels instead of the nibble ones; records that count as full early, so that walks continue in extra
-    splitter slots -- 1024 -- or use them up and are repeated the old way -- 64) decode to the same text."""
+    splitter slots -- 1024 -- or use them up and are repeated the old way -- 64) decode to the same text.
+
+    And the walks of the first text went the way the setting asks for (tc_dbg_ibwt_walk of include/textcomp_debug.h:
+    attempts run, records that overflowed, extra slots taken).  It is iid ACGTN of n = 2^20: K = 4097 splitters, one row
+    in 256, and K / 32 + 256 = 384 extra slots.  Default: a record longer than 4096 has probability about e^-16, so one
+    attempt, nothing overflowed, no slot taken.  TC_IBWT_SEGCAP=1024: a walk passes 1024 rows without a splitter with
+    probability (255/256)^1024 = 0.018, about 75 extensions, a fifth of the slots.  TC_IBWT_SEGCAP=64: (255/256)^64 =
+    0.78 of the 4097 walks want a slot, far more than there are: a second attempt.  TC_IBWT_REWALK=1: only the old way,
+    every record marked as overflowed.  The walk by positions (TC_IBWT_LF=0) traces the same cycle; the other selectors
+    do not touch the walks."""
+    import ctypes as C
+    ctx.lib.tc_dbg_ibwt_walk.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    ctx.lib.tc_dbg_ibwt_walk.restype = C.c_int
     rng = np.random.default_rng(5)
     texts = [O.gen_acgtn(31, 1 << 20).tobytes(), O.gen_ascii(32, 200000).tobytes(),
              bytes(rng.integers(0, 256, 100000, dtype=np.uint8)),
@@ -130,8 +142,21 @@ def test_ibwt_path_selectors(ctx, env, monkeypatch):
     blks = [ctx.encode(t) for t in texts]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    for t, blk in zip(texts, blks):
+    for i, (t, blk) in enumerate(zip(texts, blks)):
         assert ctx.decode(blk) == t
+        if i == 0:
+            out = (C.c_uint32 * 3)()
+            assert ctx.lib.tc_dbg_ibwt_walk(ctx.handle, out) == 0
+            attempts, overflowed, taken = out[0], out[1], out[2]
+            print("tc_dbg_ibwt_walk: attempts=%d overflowed=%d taken=%d" % (attempts, overflowed, taken))
+            if env.get("TC_IBWT_REWALK") == "1":
+                assert attempts == 1 and overflowed > 0
+            elif env.get("TC_IBWT_SEGCAP") == "64":
+                assert attempts == 2
+            elif env.get("TC_IBWT_SEGCAP") == "1024":
+                assert attempts == 1 and 0 < taken <= 384
+            else:
+                assert (attempts, taken, overflowed) == (1, 0, 0)
 
 
 def test_fused_decode_rejects_inconsistent_block(ctx):

@@ -47,6 +47,9 @@ struct tc_ctx {
     u32 lcp_cap = 0;       // short cap of the LCP compare kernel set by tc_dbg_lcp_set_short_cap (0: TC_LCP_SHORT_CAP, tc_lcp.hpp)
     int msd_dir_used = 0;    // the last suffix sort's aligned MSD level ran with the directory of live parents (tc_dbg_msd_dir)
     int msd_split_used = 0;  // the last suffix sort's MSD levels 1 and 2 used the split key layout (tc_dbg_msd_split_used)
+    // the last inverse BWT's walks (ibwt_walk_rank_copy; tc_dbg_ibwt_walk): attempts run, and of the last of them the
+    // records that overflowed and the extra splitter slots taken
+    u32 ibwt_attempts = 0, ibwt_overflowed = 0, ibwt_extra_taken = 0;
     int mtf_fastin_failed = 0;  // the one-kernel MTF + RLE of this encode could not recover a tile's list by its backward scan:
                                 // the two-stage path that follows starts with the summaries (the same scan would fail again)
     int live_comms = 0;    // communicators created on this context and not yet destroyed
@@ -85,17 +88,21 @@ struct TcFail {
 
 // Bump allocator over the ctx workspace.  A top-level call first sizes its need
 // with Arena(nullptr) (dry run), grows the workspace once, then carves for real.
+// A stage whose buffers are dead is overlaid by the next: rewind(mark) carves from `mark` again; `peak`, the
+// furthest any carve reached, is what the dry run's workspace is sized by.
 struct Arena {
     char *base;
-    size_t off = 0;
+    size_t off = 0, peak = 0;
     explicit Arena(char *b) : base(b) {}
     template <class T>
     T *get(size_t count) {
         size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);
         T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
         off += bytes;
+        if (off > peak) peak = off;
         return p;
     }
+    void rewind(size_t mark) { off = mark; }
 };
 
 void tc_ws_reserve(tc_ctx *ctx, size_t bytes);
@@ -106,7 +113,7 @@ template <class F>
 static inline void tc_ws_plan(tc_ctx *ctx, size_t base, F &&fn) {
     Arena dry(nullptr);
     fn(dry, true);
-    tc_ws_reserve(ctx, base + dry.off);
+    tc_ws_reserve(ctx, base + dry.peak);
     Arena A(ctx->ws + base);
     fn(A, false);
 }

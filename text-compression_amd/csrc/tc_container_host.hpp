@@ -536,8 +536,7 @@ static void encode_container_device(tc_ctx *ctx, const u8 *d_text, u64 n, u8 *d_
     };
     tc_ws_plan(ctx, 0, [&](Arena &A, bool dry) {
         u16 *d_idx = nullptr;
-        size_t end_sa = 0;
-        BwtAcc acc = encode_sa_stage(ctx, A, dry, d_text, n, 16, &d_idx, &primary, counts257, &end_sa);
+        BwtAcc acc = encode_sa_stage(ctx, A, dry, d_text, n, 16, &d_idx, &primary, counts257);
         bool idx8 = false;
         // a record over <= 6 symbols: MTF, RLE and the wire format in ONE kernel (tc_pack.hpp, mtf_rle_kernel<true>);
         // its scratch first (the dry run does not know sigma yet)
@@ -618,7 +617,7 @@ static void encode_container_device(tc_ctx *ctx, const u8 *d_text, u64 n, u8 *d_
             seal(a.totals, esc);
         } else if (!one_kernel) {   // the run arrays, for the packers or the Huffman writer
             u64 total = 0;
-            A.off = rle_mark;
+            A.rewind(rle_mark);
             if (idx8) {
                 U8Acc iacc{reinterpret_cast<const u8 *>(d_idx)};
                 rle_encode_device<U8Acc, u16>(ctx, A, iacc, N, r_cnt, r_val, N + 2, &total, false, sigma <= 16);
@@ -631,7 +630,6 @@ static void encode_container_device(tc_ctx *ctx, const u8 *d_text, u64 n, u8 *d_
             blk.run_count = r_cnt; blk.run_value = r_val;
             for (u32 i = 0; i < sigma; i++) blk.final_list[i] = final_list[i];
         }
-        if (A.off < end_sa) A.off = end_sa;
     });
     tc_sync_check(ctx);
     encode_stage_times(ctx);

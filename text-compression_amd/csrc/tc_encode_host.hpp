@@ -410,9 +410,9 @@ static bool mtf_rle_device(tc_ctx *ctx, Arena &A, BwtAcc acc, u64 N, const u32 *
 // The front of a fused encode, dry or for real: carves the last column and the index stream (N + idx_pad
 // elements: what the caller's later stages read behind it), sorts the suffixes between events 0 and 1, and
 // rewinds the arena to behind the two -- the suffix-sort buffers are dead, MTF / RLE scratch overlays them.
-// *end_sa: how far the sort reached (the caller's arena ends no lower).  Returns the accessor of the last column.
+// Returns the accessor of the last column.
 static BwtAcc encode_sa_stage(tc_ctx *ctx, Arena &A, bool dry, const u8 *d_text, u64 n, u64 idx_pad, u16 **d_idx,
-                              u64 *primary, u32 *counts257, size_t *end_sa) {
+                              u64 *primary, u32 *counts257) {
     const u64 N = n + 1;
     u32 counts[256];
     u8 *d_L = A.get<u8>(N + 16);
@@ -420,8 +420,7 @@ static BwtAcc encode_sa_stage(tc_ctx *ctx, Arena &A, bool dry, const u8 *d_text,
     const size_t mark = A.off;
     if (!dry) TC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     sa_build(ctx, A, d_text, n, nullptr, d_L, primary, counts, dry);
-    *end_sa = A.off;
-    A.off = mark;
+    A.rewind(mark);
     if (!dry) {
         TC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
         counts257[0] = 1;
@@ -450,15 +449,13 @@ static void encode_device(tc_ctx *ctx, const u8 *d_text, u64 n, tc_block *out, u
     hipStream_t s = ctx->stream;
     tc_ws_plan(ctx, 0, [&](Arena &A, bool dry) {
         u16 *d_idx = nullptr;
-        size_t end_sa = 0;
-        BwtAcc acc = encode_sa_stage(ctx, A, dry, d_text, n, 0, &d_idx, &primary, counts257, &end_sa);
+        BwtAcc acc = encode_sa_stage(ctx, A, dry, d_text, n, 0, &d_idx, &primary, counts257);
         // small alphabets: the index stream between the two stages is one byte per symbol (the
         // same buffer, half used)
         bool idx8 = false;
         if (mtf_rle_device(ctx, A, acc, N, counts257, out, cap, &total, &sigma, dry)) {   // (sigma <= 8: one kernel)
             TC_HIP(ctx, hipEventRecord(ctx->ev[2], s));
             TC_HIP(ctx, hipEventRecord(ctx->ev[3], s));
-            if (A.off < end_sa) A.off = end_sa;
             return;
         }
         mtf_encode_device<BwtAcc>(ctx, A, acc, N, dry ? nullptr : counts257, d_idx,
@@ -472,7 +469,6 @@ static void encode_device(tc_ctx *ctx, const u8 *d_text, u64 n, tc_block *out, u
             rle_encode_device<U16Acc, u16>(ctx, A, iacc, N, out->run_count, out->run_value, cap, &total, dry);
         }
         if (!dry) TC_HIP(ctx, hipEventRecord(ctx->ev[3], s));
-        if (A.off < end_sa) A.off = end_sa;
     });
     tc_sync_check(ctx);
     out->n = n; out->primary = primary; out->sigma = sigma; out->nruns = total;

@@ -26,7 +26,7 @@ static void bwt_host(tc_ctx *ctx, const u8 *text, u64 n, u8 *L, u32 *sa, u64 *pr
     u32 *d_sa;
     Arena dry(nullptr);
     plan(dry, true, d_text, d_L, d_sa);
-    tc_ws_reserve(ctx, dry.off);
+    tc_ws_reserve(ctx, dry.peak);
     // carve input first, upload, then run (the upload between the reserve and the run is why this is no tc_ws_plan)
     {
         Arena A0(ctx->ws);

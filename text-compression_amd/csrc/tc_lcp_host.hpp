@@ -115,14 +115,12 @@ static void lcp_array_host_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 *sa, u3
         const size_t mark = A.off;
         u8 *d_L = A.get<u8>(N + 16);
         sa_build(ctx, A, d_text, n, d_sa, d_L, &primary, nullptr, dry);
-        const size_t end_sa = A.off;
-        A.off = mark;
+        A.rewind(mark);
         W.carve(ctx, A, n);
-        if (A.off < end_sa) A.off = end_sa;
     };
     Arena dry(nullptr);
     plan(dry, true);
-    tc_ws_reserve(ctx, dry.off);
+    tc_ws_reserve(ctx, dry.peak);
     // the text is the first carve: upload it between the reserve and the run, as bwt_host does
     {
         Arena A0(ctx->ws);

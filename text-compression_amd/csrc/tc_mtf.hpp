@@ -1759,6 +1759,11 @@ __global__ __launch_bounds__(MTF_NT) void imtf_nib_apply_kernel(const IT *__rest
         }
     }
 }
+// the byte codes that kernel writes (OT = u8: the fused decode of a small alphabet) as symbols after all
+__global__ __launch_bounds__(256) void codes_to_syms_kernel(const u8 *__restrict__ codes, u64 N, SymTab tab,
+                                                            i16 *__restrict__ out) {
+    for (u64 j = (u64)blockIdx.x * 256 + threadIdx.x; j < N; j += (u64)gridDim.x * 256) out[j] = tab.v[codes[j]];
+}
 
 // ---- which general path?  The lane chunks cost ~ rank / 4 list words per symbol, the wave chunks a
 // constant; on large alphabets with uniformly spread symbols (average rank ~ sigma / 2) the wave

@@ -639,6 +639,14 @@ int tc_dbg_msd_dir(tc_ctx *ctx, uint32_t out[2]) {
     TC_API_END(ctx)
 }
 
+int tc_dbg_ibwt_walk(tc_ctx *ctx, uint32_t out[3]) {
+    if (!ctx || !out) return TC_ERR_ARG;
+    out[0] = ctx->ibwt_attempts;
+    out[1] = ctx->ibwt_overflowed;
+    out[2] = ctx->ibwt_extra_taken;
+    return TC_OK;
+}
+
 int tc_dbg_dispatch_probe(tc_ctx *ctx, uint32_t grid, uint32_t lds_bytes, uint32_t spin_cycles, uint32_t *out6) {
     TC_API_BEGIN(ctx)
     dbg_dispatch_probe_entry(ctx, grid, lds_bytes, spin_cycles, out6);
