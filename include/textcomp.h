@@ -384,6 +384,7 @@ int tc_fm_build_sampled_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint
 uint32_t tc_fm_sa_rate(const tc_fm *fm);
 /* device bytes the index holds: part 0 = everything, part 1 = the locate part alone (L + SA, or L + marks + samples),
  * part 2 = the extract part alone (the text samples of tc_fm_build_self: 4 * (n / text_rate + 1); 0 without them; part 0
+ * includes it), part 3 = the LCP part alone (tc_fm_build_lcp: 4 * (N + the words of the min tree); 0 without it; part 0
  * includes it); the sizes asked of the allocator, without its rounding.  0 for the empty index or any other part. */
 uint64_t tc_fm_device_bytes(const tc_fm *fm, int part);
 /* The same index with TEXT SAMPLES as well, so that it can answer what stands at a text position (extract) and the text
@@ -520,6 +521,57 @@ int tc_fm_unfactorize(tc_ctx *ctx, const tc_fm *fm, const uint64_t *fac_offs, co
                       uint64_t npat, uint64_t *out_offs, uint8_t *out, uint64_t *nbytes);
 int tc_fm_unfactorize_dev(tc_ctx *ctx, const tc_fm *fm, const uint64_t *d_fac_offs, const uint64_t *d_fac_pos,
                           const uint32_t *d_fac_len, uint64_t npat, uint64_t *d_out_offs, uint8_t *d_out, uint64_t *nbytes);
+/* Matching statistics and maximal exact matches (an addition to the reference's surface, as factorize is).  Where
+ * tc_fm_count asks whether the whole pattern occurs and tc_fm_factorize for one greedy parse, this asks, for EVERY position
+ * of a pattern, how long a match starts there and where it occurs: what an aligner, a read classifier or a similarity
+ * search seeds from.  Patterns as in tc_fm_count: pattern j = pats[offs[j] .. offs[j+1]).
+ * THE INDEX needs an LCP part: tc_fm_build_lcp is tc_fm_build_self plus
+ *   lcp      uint32 lcp[N]: exactly the array tc_lcp_array_dev defines (lcp[0] = 0) -- 4 bytes per text byte, which doubles
+ *            the locate part of a full index
+ *   lmin     a min tree over it with fan-out 64: level 1 entry b = min lcp[64 b .. 64 b + 64), level k + 1 over level k
+ *            the same way, up to the first level of at most 64 entries; every level rounded up to a multiple of 4 words,
+ *            less than N / 63 + 4 per level words in all
+ * sa_rate as in tc_fm_build_sampled; text_rate 0 (no text samples) or as in tc_fm_build_self; anything else: TC_ERR_ARG
+ * (*out = NULL).  n = 0 gives the empty index.  tc_fm_has_lcp: 1 / 0.  The LCP part is NOT exported: tc_fm_export_dev of
+ * such an index ships, byte for byte, what it ships for the same index built without the part, and an import never has
+ * one.  Every other call answers on such an index what it answers without the part.
+ * MATCHING STATISTICS.  For a pattern p of length m and every 0 <= i < m, at index offs[j] + i of the result arrays:
+ *   ms_len   the largest l such that p[i .. i+l) occurs in the text (inside it, never over its end); l = 0 means that the
+ *            byte p[i] does not occur in the text
+ *   ms_pos   the 1-based text position, as tc_fm_locate answers them, of that string's occurrence in the FIRST
+ *            suffix-array row of its interval -- the convention of tc_fm_factorize; 0 where l = 0
+ *   ms_occ   the number of text occurrences of p[i .. i+l), the interval's width; 0 where l = 0
+ * ms_pos and ms_occ may each be NULL; ms_len must not.  The answer is fully determined: the same through the host and _dev
+ * entries, and on a full and a sampled index of one text, with or without text samples.
+ * MAXIMAL EXACT MATCHES of pattern p with min_len >= 1 are the triples (i, ms_pos[i], ms_len[i]) with ms_len[i] >= min_len
+ * and (i = 0 or ms_len[i-1] <= ms_len[i]).  ms_len[i-1] <= ms_len[i] + 1 always holds, so the second condition says exactly
+ * that the match cannot be extended to the left; by the definition of ms_len it cannot be extended to the right either.
+ * These are the matches not contained in a longer match of the same pattern.  The MEMs of one pattern are stored in
+ * increasing i: mem_start = i (0-based in the pattern), mem_pos, mem_len.  mem_offs[npat + 1] (out) delimits each pattern's
+ * MEMs; *nmem: in = capacity of the three arrays, out = total.  A capacity that is too small: TC_ERR_CAPACITY, *nmem = the
+ * needed total, nothing written to the three arrays.  mem_start = mem_pos = mem_len = NULL with capacity 0 is the sizes-only
+ * form: TC_OK, mem_offs and the total written.  All occurrences of a MEM: tc_fm_locate on the substring.
+ * ERRORS AND EDGES.  A null index or null buffers: TC_ERR_ARG.  A non-empty index without the LCP part (tc_fm_has_lcp 0:
+ * every other build call, every import): TC_ERR_ARG.  min_len = 0: TC_ERR_ARG.  npat = 0: TC_OK.  The empty index answers
+ * all zeros and no MEMs.  The _dev forms take everything in HBM (nmem is a host word); the host forms are those calls
+ * between a copy in and a copy out.  Scratch comes from the calling ctx: any number of ctxs may query one tc_fm at once.
+ * Cost: one lane per pattern, one dependent random 64-byte line per pattern symbol (single-symbol steps: a two-symbol step
+ * does not yield the interval of the position between), one 4-byte store per symbol and array, and where a step fails a
+ * shrink to the parent interval: two LCP reads and two searches in the min tree of at most 2 * 64 words per level each,
+ * whatever the text.  On a sampled index one locate walk per position follows when ms_pos is asked for
+ * (tc_fm_mems: per MEM). */
+int tc_fm_build_lcp(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, tc_fm **out);
+int tc_fm_build_lcp_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, tc_fm **out);
+int tc_fm_has_lcp(const tc_fm *fm);
+int tc_fm_match_stats(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat,
+                      uint32_t *ms_len, uint64_t *ms_pos, uint32_t *ms_occ);
+int tc_fm_match_stats_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat,
+                          uint32_t *d_ms_len, uint64_t *d_ms_pos, uint32_t *d_ms_occ);
+int tc_fm_mems(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat, uint32_t min_len,
+               uint64_t *mem_offs, uint64_t *mem_start, uint64_t *mem_pos, uint32_t *mem_len, uint64_t *nmem);
+int tc_fm_mems_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat,
+                   uint32_t min_len, uint64_t *d_mem_offs, uint64_t *d_mem_start, uint64_t *d_mem_pos, uint32_t *d_mem_len,
+                   uint64_t *nmem);
 /* seqToCc / seqFromFMIndex views for the Haskell shim: present symbols (sorted,
  * Nothing first) with C[c]; and L / primary. */
 int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, uint64_t *c_val,

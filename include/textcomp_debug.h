@@ -33,6 +33,11 @@ int tc_dbg_dispatch_probe(tc_ctx *ctx, uint32_t grid, uint32_t lds_bytes, uint32
  * workgroup each) for the later tc_lcp_array / tc_lcp_array_dev calls of this context: a multiple of 16 in 16 .. 65536,
  * or 0 for the library's TC_LCP_SHORT_CAP.  The results do not depend on it; scripts/lcp_bench.py sweeps it. */
 int tc_dbg_lcp_set_short_cap(tc_ctx *ctx, uint32_t cap);
+/* The fan-out of the min tree over the LCP array (csrc/tc_fm_ms.hpp) of the indexes the later tc_fm_build_lcp /
+ * tc_fm_build_lcp_dev calls of this context make: 4, 8, 16 or 64 (the library's FM_LCP_FANOUT); anything else is
+ * TC_ERR_ARG.  The fan-out is stored in the index; the results do not depend on it.  It exists so that tests reach every
+ * level of the tree at a thousand rows. */
+int tc_dbg_fm_set_lcp_fanout(tc_ctx *ctx, uint32_t fanout);
 /* *used = 1 if round 0 of this context's last suffix sort (an encode runs one) went the MSD way with levels 1 and 2 in
  * the split key layout (csrc/tc_msd.hpp: two arrays of 32-bit key halves; TC_MSD_SPLIT), 0 if not -- the LSD way, levels
  * that move suffix starts, TC_SA_MSD_JOINT=0, or a second run of the levels with suffix starts. */

@@ -1,4 +1,4 @@
-// tc_fm_host.hpp -- FM-index: build, batched count, locate, extract, factorize.
+// tc_fm_host.hpp -- FM-index: build, batched count, locate, extract, factorize, matching statistics.
 //
 // Replaces (reference FMIndex/Internal.hs) seqToCc :275-316 (C[c], there derived
 // from an O(n^2) rotation matrix, BWT/Internal.hs:209-241; here a byte histogram),
@@ -24,9 +24,11 @@
 // is the same.  Cost: sigma^2 / 7 bytes per text byte (3.6 N for ACGTN).
 #pragma once
 #include "tc_decode_host.hpp"
+#include "tc_lcp_host.hpp"   // lcp_device: the LCP part of an index (tc_fm_build_lcp)
 
 #define FM_LINE_BITS 448  // 7 words of payload per 64-byte line
 #define FM_PAIR_SIGMA 5   // pair vectors for texts of at most this many byte values (25 vectors)
+#define FM_LCP_FANOUT 64  // fan-out of the min tree over the LCP array (tc_dbg_fm_set_lcp_fanout builds 4, 8 or 16 for the tests)
 
 struct tc_fm {
     int device = 0;
@@ -55,6 +57,12 @@ struct tc_fm {
     u32 text_rate = 0;
     u32 *d_isa = nullptr;     // [nisa]
     u64 nisa = 0;             // n / text_rate + 1
+    // the LCP part (tc_fm_build_lcp; never exported or imported): d_lcp = the array tc_lcp_array_dev defines over the N rows,
+    // d_lmin = the min tree over it (tc_fm_ms.hpp: fm_ms_tree_shape gives the levels), fan-out 2^lcp_fan_log2
+    u32 *d_lcp = nullptr;     // [N]
+    u32 *d_lmin = nullptr;    // [lmin_words]
+    u64 lmin_words = 0;
+    u32 lcp_fan_log2 = 0;
 };
 
 #ifdef __HIPCC__
@@ -619,6 +627,7 @@ __global__ __launch_bounds__(256) void fm_extract_walk_kernel(const u64 *__restr
 
 #include "tc_fm_mm.hpp"   // fm_mm_kernel: count / locate within Hamming distance k
 #include "tc_fm_factor.hpp"   // fm_factor_kernel: the longest-match parse; the small kernels of its inverse
+#include "tc_fm_ms.hpp"   // fm_ms_kernel: matching statistics; the min tree over the LCP array; the small kernels of the MEMs
 
 #endif  // __HIPCC__
 
@@ -648,6 +657,8 @@ static void fm_release(tc_fm *fm) {
     if (fm->d_marks) (void)hipFree(fm->d_marks);
     if (fm->d_samples) (void)hipFree(fm->d_samples);
     if (fm->d_isa) (void)hipFree(fm->d_isa);
+    if (fm->d_lcp) (void)hipFree(fm->d_lcp);
+    if (fm->d_lmin) (void)hipFree(fm->d_lmin);
     if (fm->d_bits) (void)hipFree(fm->d_bits);
     if (fm->bits2_chunks) tc_chunked_free(fm->bits2_chunks);
     else if (fm->d_bits2) (void)hipFree(fm->d_bits2);
@@ -675,9 +686,12 @@ static void fm_alloc_bits2(tc_ctx *ctx, tc_fm *fm, size_t bytes) {
 // sa_rate 1: the index owns the full suffix array.  sa_rate k > 1: the suffix array lives in the context's workspace for the
 // duration of the call (the same peak: the 4 N bytes are carved there instead of allocated) and the index keeps marks + samples.
 // text_rate k >= 1: the index also keeps the text samples (d_isa), scattered from the same suffix array before it goes.
+// with_lcp: the index also keeps the LCP array and its min tree, made by lcp_device while the text and the full suffix array
+// are still there (both in the workspace on a sampled index); the LCP scratch overlays the sort's buffers, which are dead by
+// then, as in lcp_array_host_entry, so the one dry run sizes the peak of both.
 static inline u32 fm_log2(u32 v) { return 31u - (u32)__builtin_clz(v); }   // v: a power of two
 static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 *text_dev = nullptr, u32 sa_rate = 1,
-                              u32 text_rate = 0) {
+                              u32 text_rate = 0, bool with_lcp = false) {
     tc_fm *fm = new tc_fm();
     fm->device = ctx->device;
     fm->n = n;
@@ -692,6 +706,15 @@ static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 
         TC_HIP(ctx, hipMalloc((void **)&fm->d_tab, 768 * sizeof(u32)));
         u8 *d_text = nullptr;
         u32 *d_sa = fm->d_sa;
+        u32 tree_off[FM_MS_MAXLEV + 1], tree_cnt[FM_MS_MAXLEV + 1], tree_words = 0, tree_levels = 0;
+        LcpScratch lcp_ws;
+        if (with_lcp) {
+            fm->lcp_fan_log2 = fm_log2(ctx->fm_lcp_fanout ? ctx->fm_lcp_fanout : FM_LCP_FANOUT);
+            tree_levels = fm_ms_tree_shape((u32)N, fm->lcp_fan_log2, tree_off, tree_cnt, &tree_words);
+            fm->lmin_words = tree_words;
+            TC_HIP(ctx, hipMalloc((void **)&fm->d_lcp, N * sizeof(u32)));
+            TC_HIP(ctx, hipMalloc((void **)&fm->d_lmin, (size_t)tree_words * sizeof(u32)));
+        }
         auto plan = [&](Arena &A, bool dry) {
             if (sampled) {   // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
                 u32 *p = A.get<u32>(N);
@@ -703,11 +726,27 @@ static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 
                 d_text = A.get<u8>(n + 16);
                 if (!dry) tc_h2d(ctx, d_text, text_host, n);
             }
+            const size_t mark = A.off;
             sa_build(ctx, A, d_text, n, d_sa, fm->d_L, &fm->primary, fm->counts, dry);
+            if (with_lcp) {
+                A.rewind(mark);
+                lcp_ws.carve(ctx, A, n);
+            }
         };
         ctx->stats = tc_stats{};
         ctx->stats.n = n; ctx->stats.N = N;
         tc_ws_plan(ctx, 0, plan);
+        if (with_lcp) {
+            lcp_device(ctx, lcp_ws, d_text, n, d_sa, fm->d_lcp);
+            const u32 *src = fm->d_lcp;
+            for (u32 k = 1; k <= tree_levels; k++) {   // one small kernel per level, each over the one below
+                u32 *dst = fm->d_lmin + tree_off[k];
+                fm_lmin_kernel<<<tc_cdiv(((u64)tree_cnt[k] + 3) & ~(u64)3, 256), 256, 0, s>>>(src, tree_cnt[k - 1], fm->lcp_fan_log2, dst,
+                                                                                            tree_cnt[k]);
+                TC_LAUNCH_CHECK(ctx);
+                src = dst;
+            }
+        }
         // C[c] = #symbols of text.'$' smaller than c ('$' = Nothing counts once)
         u32 tab[768];
         const u32 sig = fm_make_tab(fm->counts, tab, fm->sym_of_code);
@@ -811,32 +850,35 @@ static tc_fm *fm_new_empty(tc_ctx *ctx) {
     return fm;
 }
 
-// the six tc_fm_build*: text_host or text_dev is the text (the other is null); rates = how many of (sa_rate, text_rate) are
-// the caller's and therefore validated -- 0: tc_fm_build, 1: tc_fm_build_sampled, 2: tc_fm_build_self
+// the eight tc_fm_build*: text_host or text_dev is the text (the other is null); rates = how many of (sa_rate, text_rate) are
+// the caller's and therefore validated -- 0: tc_fm_build, 1: tc_fm_build_sampled, 2: tc_fm_build_self and tc_fm_build_lcp
+// (lcp: with the LCP part; there text_rate may also be 0, no text samples)
 static void fm_build_entry(tc_ctx *ctx, const u8 *text_host, const u8 *text_dev, u64 n, u32 sa_rate, u32 text_rate, int rates,
-                           tc_fm **out) {
+                           tc_fm **out, bool lcp = false) {
     static const char *const kBadArg[3] = {"bad argument", "bad argument (sa_rate: a power of two, 1 .. %d)",
                                            "bad argument (sa_rate, text_rate: powers of two, 1 .. %d)"};
     if (out) *out = nullptr;
-    if (!out || n > TC_MAX_N || (rates >= 1 && !fm_rate_ok(sa_rate)) || (rates >= 2 && !fm_rate_ok(text_rate)))
+    if (!out || n > TC_MAX_N || (rates >= 1 && !fm_rate_ok(sa_rate)) || (rates >= 2 && !fm_rate_ok(text_rate) && !(lcp && text_rate == 0)))
         TC_FAIL(ctx, TC_ERR_ARG, kBadArg[rates], TC_FM_MAX_SA_RATE);
     if (n == 0) {
         *out = fm_new_empty(ctx);
         return;
     }
     if (!text_host && !text_dev) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    *out = fm_build_device(ctx, text_host, n, text_dev, sa_rate, text_rate);
+    *out = fm_build_device(ctx, text_host, n, text_dev, sa_rate, text_rate, lcp);
 }
 
 static u64 fm_device_bytes(const tc_fm *fm, int part) {
-    if (!fm || fm->n == 0 || part < 0 || part > 2) return 0;
+    if (!fm || fm->n == 0 || part < 0 || part > 3) return 0;
     const u64 ext = fm->text_rate ? fm->nisa * sizeof(u32) : 0;
     if (part == 2) return ext;
+    const u64 lcp = fm->d_lcp ? (fm->N + fm->lmin_words) * sizeof(u32) : 0;
+    if (part == 3) return lcp;
     u64 loc = 0;
     if (fm->sa_rate == 1) loc = (fm->N + 16) + fm->N * sizeof(u32);
     else if (fm->sa_rate > 1) loc = (fm->N + 16) + fm->lines * 64 + fm->nsamples * sizeof(u32);
     if (part == 1) return loc;
-    u64 b = loc + ext + 768 * sizeof(u32) + (u64)fm->sigma_bytes * fm->lines * 64;
+    u64 b = loc + ext + lcp + 768 * sizeof(u32) + (u64)fm->sigma_bytes * fm->lines * 64;
     if (fm->d_bits2) b += (u64)fm->sigma_bytes * fm->sigma_bytes * fm->lines * 64 + FM_PAIR_SIGMA * FM_PAIR_SIGMA * sizeof(u32);
     return b;
 }
@@ -1495,5 +1537,135 @@ static void fm_unfactor_entry(tc_ctx *ctx, const tc_fm *fm, const u64 *fac_offs,
         TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu bytes, have %llu", (unsigned long long)need, (unsigned long long)cap);
     }
     if (!dev && need) tc_d2h(ctx, out, d_out, need);
+    tc_sync_check(ctx);
+}
+
+// ---- matching statistics / maximal exact matches (the kernels: tc_fm_ms.hpp) ----------------------------------------------
+// the number of pattern bytes of a batch, offs[npat] (the result arrays of the matching statistics have that many entries)
+static u64 fm_pattern_bytes(tc_ctx *ctx, const u64 *offs, u64 npat, bool dev) {
+    if (!dev) return offs[npat];
+    tc_d2h(ctx, &ctx->h_scalars[8], offs + npat, sizeof(u64));
+    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ctx->h_scalars[8];
+}
+
+// fm_ms_kernel over a batch: d_len[offs[p] + i] for every position of every pattern, and d_pos / d_occ likewise where they
+// are not null -- d_pos holds positions on a full index, rows on a sampled one (the caller walks what it keeps)
+static void fm_ms_pass(tc_ctx *ctx, const tc_fm *fm, const u8 *d_pats, const u64 *d_offs, u64 npat, u32 *d_len, u64 *d_pos,
+                       u32 *d_occ) {
+    const u32 grid = tc_cdiv(npat, 256);
+    hipStream_t s = ctx->stream;
+#define FM_MS_LAUNCH(P)                                                                                                     \
+    fm_ms_kernel<P><<<grid, 256, 0, s>>>(fm->d_bits, fm->lines, fm->d_tab, (u32)fm->N, fm->d_lcp, fm->d_lmin, fm->lcp_fan_log2, \
+                                         fm->d_sa, d_pats, d_offs, npat, d_len, d_pos, d_occ)
+    if (d_pos || d_occ) FM_MS_LAUNCH(true); else FM_MS_LAUNCH(false);
+#undef FM_MS_LAUNCH
+    TC_LAUNCH_CHECK(ctx);
+}
+
+// the walk of a sampled index over `total` (row, length) entries: rows of entries with length > 0 become positions
+static void fm_rows_to_positions(tc_ctx *ctx, const tc_fm *fm, u64 total, u64 *d_pos, const u32 *d_len) {
+    fm_factor_walk_kernel<<<tc_cdiv(total, 256), 256, 0, ctx->stream>>>(fm->d_bits, fm->d_marks, fm->lines, fm->d_tab,
+                                                                       fm->sigma_bytes, fm->d_L, fm->d_samples, fm->nsamples,
+                                                                       fm->N, fm->primary, fm->sa_rate, total, d_pos, d_len,
+                                                                       ctx->d_err);
+    TC_LAUNCH_CHECK(ctx);
+}
+
+// tc_fm_match_stats, tc_fm_match_stats_dev (ms_pos and ms_occ may each be null)
+static void fm_match_stats_entry(tc_ctx *ctx, const tc_fm *fm, const u8 *pats, const u64 *offs, u64 npat, u32 *ms_len,
+                                 u64 *ms_pos, u32 *ms_occ, bool dev) {
+    if (!fm) TC_FAIL(ctx, TC_ERR_ARG, "null index");
+    if (npat == 0) return;
+    if (!pats || !offs || !ms_len) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (fm->n && !fm->d_lcp) TC_FAIL(ctx, TC_ERR_ARG, "this index holds no LCP part (build it with tc_fm_build_lcp; an import never has one)");
+    const u64 total = fm_pattern_bytes(ctx, offs, npat, dev);
+    if (total == 0) return;
+    if (fm->n == 0) {
+        fm_zero_result(ctx, ms_len, total * sizeof(u32), dev);
+        if (ms_pos) fm_zero_result(ctx, ms_pos, total * sizeof(u64), dev);
+        if (ms_occ) fm_zero_result(ctx, ms_occ, total * sizeof(u32), dev);
+        return;
+    }
+    FmPatterns P;
+    u32 *d_len = ms_len, *d_occ = ms_occ;
+    u64 *d_pos = ms_pos;
+    if (!dev) {
+        tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+            P.carve(A, offs, npat);
+            d_len = A.get<u32>(total);
+            d_pos = ms_pos ? A.get<u64>(total) : nullptr;
+            d_occ = ms_occ ? A.get<u32>(total) : nullptr;
+        });
+        P.upload(ctx, pats, offs, npat);
+    }
+    fm_ms_pass(ctx, fm, dev ? pats : P.d_pats, dev ? offs : P.d_offs, npat, d_len, d_pos, d_occ);
+    if (d_pos && fm->sa_rate > 1) fm_rows_to_positions(ctx, fm, total, d_pos, d_len);
+    if (!dev) {
+        tc_d2h(ctx, ms_len, d_len, total * sizeof(u32));
+        if (ms_pos) tc_d2h(ctx, ms_pos, d_pos, total * sizeof(u64));
+        if (ms_occ) tc_d2h(ctx, ms_occ, d_occ, total * sizeof(u32));
+    }
+    tc_sync_check(ctx);
+}
+
+// tc_fm_mems, tc_fm_mems_dev: the matching statistics into the context's scratch, the MEMs of every pattern counted, the
+// scan of the counts (mem_offs[0 .. npat], the last entry the total), the capacity check on the host, the fill and -- on a
+// sampled index -- the walk over the MEM list only.  mem_start = mem_pos = mem_len = null with capacity 0 is the sizes-only
+// form (the matching statistics are then lengths only).  When the total exceeds the capacity nothing is written to the
+// three arrays.
+static void fm_mems_entry(tc_ctx *ctx, const tc_fm *fm, const u8 *pats, const u64 *offs, u64 npat, u32 min_len, u64 *mem_offs,
+                          u64 *mem_start, u64 *mem_pos, u32 *mem_len, u64 *nmem, bool dev) {
+    if (!fm || !nmem) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
+    const u64 cap = *nmem;
+    *nmem = 0;
+    if (min_len == 0) TC_FAIL(ctx, TC_ERR_ARG, "min_len = 0 (a match has at least one byte)");
+    if (npat == 0) return;
+    const bool sizes_only = !mem_start && !mem_pos && !mem_len && cap == 0;
+    if (!pats || !offs || !mem_offs || (!sizes_only && (!mem_start || !mem_pos || !mem_len))) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
+    if (fm->n && !fm->d_lcp) TC_FAIL(ctx, TC_ERR_ARG, "this index holds no LCP part (build it with tc_fm_build_lcp; an import never has one)");
+    if (fm->n == 0) return fm_zero_result(ctx, mem_offs, (npat + 1) * sizeof(u64), dev);
+    const u64 total = fm_pattern_bytes(ctx, offs, npat, dev);
+    FmLocateScratch W;
+    FmPatterns P;
+    u32 *d_mslen = nullptr, *d_mlen = mem_len;
+    u64 *d_mspos = nullptr, *d_moffs = mem_offs, *d_mstart = mem_start, *d_mpos = mem_pos;
+    tc_ws_plan(ctx, 0, [&](Arena &A, bool) {
+        if (!dev) P.carve(A, offs, npat);
+        W.carve(A, npat, false);
+        d_mslen = A.get<u32>(total + 1);
+        d_mspos = sizes_only ? nullptr : A.get<u64>(total + 1);
+        if (!dev) {
+            d_moffs = A.get<u64>(npat + 1);
+            d_mstart = A.get<u64>(cap + 1);
+            d_mpos = A.get<u64>(cap + 1);
+            d_mlen = A.get<u32>(cap + 1);
+        }
+    });
+    if (!dev) P.upload(ctx, pats, offs, npat);
+    const u8 *d_pats = dev ? pats : P.d_pats;
+    const u64 *d_offs = dev ? offs : P.d_offs;
+    hipStream_t s = ctx->stream;
+    const u32 grid = tc_cdiv(npat, 256);
+    fm_ms_pass(ctx, fm, d_pats, d_offs, npat, d_mslen, d_mspos, nullptr);
+    fm_mem_count_kernel<<<grid, 256, 0, s>>>(d_mslen, d_offs, npat, min_len, W.d_cnt);
+    TC_LAUNCH_CHECK(ctx);
+    const u64 need = fm_offsets_of_counts(ctx, W, npat, d_moffs);
+    *nmem = need;
+    if (!dev) tc_d2h(ctx, mem_offs, d_moffs, (npat + 1) * sizeof(u64));
+    if (need > cap && !sizes_only) {
+        tc_sync_check(ctx);
+        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu MEM slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
+    }
+    if (need && !sizes_only) {
+        fm_mem_fill_kernel<<<grid, 256, 0, s>>>(d_mslen, d_mspos, d_offs, npat, min_len, d_moffs, d_mstart, d_mpos, d_mlen);
+        TC_LAUNCH_CHECK(ctx);
+        if (fm->sa_rate > 1) fm_rows_to_positions(ctx, fm, need, d_mpos, d_mlen);
+        if (!dev) {
+            tc_d2h(ctx, mem_start, d_mstart, need * sizeof(u64));
+            tc_d2h(ctx, mem_pos, d_mpos, need * sizeof(u64));
+            tc_d2h(ctx, mem_len, d_mlen, need * sizeof(u32));
+        }
+    }
     tc_sync_check(ctx);
 }

@@ -1,6 +1,6 @@
 // tc_lcp_host.hpp -- host side of the LCP array (tc_lcp.hpp has the kernels and the algorithm): scratch, the launch
 // sequence, and the bodies of tc_suffix_array_dev / tc_lcp_array_dev / tc_lcp_array / tc_lcp_summary_dev.  Included by
-// textcomp.hip only, after tc_encode_host.hpp (sa_build, the copy helpers).
+// tc_fm_host.hpp (lcp_device makes the LCP part of an index) and textcomp.hip, after tc_encode_host.hpp (sa_build, the copy helpers).
 #pragma once
 #include "tc_lcp.hpp"
 

@@ -431,6 +431,19 @@ int tc_fm_build_self_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_
     TC_API_END(ctx)
 }
 
+int tc_fm_build_lcp(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, tc_fm **out) {
+    TC_API_BEGIN(ctx)
+    fm_build_entry(ctx, text, nullptr, n, sa_rate, text_rate, 2, out, true);
+    TC_API_END(ctx)
+}
+
+int tc_fm_build_lcp_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, tc_fm **out) {
+    TC_API_BEGIN(ctx)
+    fm_build_entry(ctx, nullptr, d_text, n, sa_rate, text_rate, 2, out, true);
+    TC_API_END(ctx)
+}
+
+int tc_fm_has_lcp(const tc_fm *fm) { return fm && fm->d_lcp ? 1 : 0; }
 uint32_t tc_fm_sa_rate(const tc_fm *fm) { return fm ? fm->sa_rate : 0; }
 uint32_t tc_fm_text_rate(const tc_fm *fm) { return fm ? fm->text_rate : 0; }
 uint64_t tc_fm_device_bytes(const tc_fm *fm, int part) { return fm_device_bytes(fm, part); }
@@ -550,6 +563,35 @@ int tc_fm_unfactorize_dev(tc_ctx *ctx, const tc_fm *fm, const uint64_t *d_fac_of
     TC_API_END(ctx)
 }
 
+// ---- matching statistics / maximal exact matches (the kernels: tc_fm_ms.hpp) -------------
+int tc_fm_match_stats(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat, uint32_t *ms_len,
+                      uint64_t *ms_pos, uint32_t *ms_occ) {
+    TC_API_BEGIN(ctx)
+    fm_match_stats_entry(ctx, fm, pats, offs, npat, ms_len, ms_pos, ms_occ, false);
+    TC_API_END(ctx)
+}
+
+int tc_fm_match_stats_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat,
+                          uint32_t *d_ms_len, uint64_t *d_ms_pos, uint32_t *d_ms_occ) {
+    TC_API_BEGIN(ctx)
+    fm_match_stats_entry(ctx, fm, d_pats, d_offs, npat, d_ms_len, d_ms_pos, d_ms_occ, true);
+    TC_API_END(ctx)
+}
+
+int tc_fm_mems(tc_ctx *ctx, const tc_fm *fm, const uint8_t *pats, const uint64_t *offs, uint64_t npat, uint32_t min_len,
+               uint64_t *mem_offs, uint64_t *mem_start, uint64_t *mem_pos, uint32_t *mem_len, uint64_t *nmem) {
+    TC_API_BEGIN(ctx)
+    fm_mems_entry(ctx, fm, pats, offs, npat, min_len, mem_offs, mem_start, mem_pos, mem_len, nmem, false);
+    TC_API_END(ctx)
+}
+
+int tc_fm_mems_dev(tc_ctx *ctx, const tc_fm *fm, const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint32_t min_len,
+                   uint64_t *d_mem_offs, uint64_t *d_mem_start, uint64_t *d_mem_pos, uint32_t *d_mem_len, uint64_t *nmem) {
+    TC_API_BEGIN(ctx)
+    fm_mems_entry(ctx, fm, d_pats, d_offs, npat, min_len, d_mem_offs, d_mem_start, d_mem_pos, d_mem_len, nmem, true);
+    TC_API_END(ctx)
+}
+
 int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, uint64_t *c_val,
                uint64_t *primary) {
     return fm_info(fm, N, sigma, c_sym, c_val, primary);
@@ -623,6 +665,16 @@ int tc_dbg_lcp_set_short_cap(tc_ctx *ctx, uint32_t cap) {
         return TC_ERR_ARG;
     }
     ctx->lcp_cap = cap;
+    return TC_OK;
+}
+
+int tc_dbg_fm_set_lcp_fanout(tc_ctx *ctx, uint32_t fanout) {
+    if (!ctx) return TC_ERR_ARG;
+    if (fanout != 4 && fanout != 8 && fanout != 16 && fanout != 64) {
+        ctx->err = "the fan-out of the LCP min tree is 4, 8, 16 or 64";
+        return TC_ERR_ARG;
+    }
+    ctx->fm_lcp_fanout = fanout;
     return TC_OK;
 }
 

@@ -11,6 +11,7 @@
 //   MTF ByteString           -> struct MTF { indices; final list }
 //   Seq (ByteString, Maybe Int) -> std::vector<std::pair<std::string, std::optional<int64_t>>>
 #pragma once
+#include <array>
 #include <cstdint>
 #include <optional>
 #include <stdexcept>
@@ -366,6 +367,105 @@ inline FactorizeResult bytestringFMIndexFactorizeP(const std::vector<std::string
     return bytestringFMIndexFactorizeS(pats, input);
 }
 
+// Not in the reference: matching statistics and maximal exact matches (textcomp.h).  For every position i of every pattern
+// the length of the longest match that starts there, the 1-based text position of its occurrence in the first
+// suffix-array row and the number of its occurrences -- (0, 0, 0) where the byte does not occur -- flat, pattern after
+// pattern (pattern j's entries are [offs[j], offs[j + 1])); the MEMs are the matches of at least min_len bytes that are
+// contained in no longer match of the same pattern, per pattern in increasing start.  The index must hold the LCP part.
+struct MatchStats {
+    std::vector<uint64_t> offs, pos;    // offs [npat + 1]: the pattern offsets
+    std::vector<uint32_t> len, occ;
+};
+struct Mems {
+    std::vector<uint64_t> offs, start, pos;     // offs [npat + 1]: pattern i's MEMs are [offs[i], offs[i + 1])
+    std::vector<uint32_t> len;
+};
+namespace detail {
+inline MatchStats matchStats(const tc_fm *fm, const std::vector<std::string> &pats) {
+    MatchStats r;
+    r.offs.assign(pats.size() + 1, 0);
+    if (pats.empty()) return r;
+    const std::string flat = packPatterns(pats, r.offs);
+    const uint64_t total = r.offs.back();
+    r.pos.assign(total + 1, 0);
+    r.len.assign(total + 1, 0);
+    r.occ.assign(total + 1, 0);
+    Context::check(tc_fm_match_stats(Context::get(), fm, (const uint8_t *)flat.data(), r.offs.data(), pats.size(), r.len.data(),
+                                     r.pos.data(), r.occ.data()));
+    r.pos.resize(total);
+    r.len.resize(total);
+    r.occ.resize(total);
+    return r;
+}
+inline Mems mems(const tc_fm *fm, const std::vector<std::string> &pats, uint32_t min_len) {
+    Mems r;
+    r.offs.assign(pats.size() + 1, 0);
+    if (pats.empty()) return r;
+    std::vector<uint64_t> offs;
+    const std::string flat = packPatterns(pats, offs);
+    uint64_t nm = 0;        // the sizes-only form first: the total
+    Context::check(tc_fm_mems(Context::get(), fm, (const uint8_t *)flat.data(), offs.data(), pats.size(), min_len, r.offs.data(),
+                              nullptr, nullptr, nullptr, &nm));
+    r.start.resize(nm);
+    r.pos.resize(nm);
+    r.len.resize(nm);
+    if (nm)
+        Context::check(tc_fm_mems(Context::get(), fm, (const uint8_t *)flat.data(), offs.data(), pats.size(), min_len,
+                                  r.offs.data(), r.start.data(), r.pos.data(), r.len.data(), &nm));
+    return r;
+}
+}  // namespace detail
+// per pattern its (len, pos, occ) triples, one per position
+using MatchStatsResult = std::vector<std::pair<std::string, std::vector<std::array<uint64_t, 3>>>>;
+inline MatchStatsResult bytestringFMIndexMatchStatsS(const std::vector<std::string> &pats, const std::string &input) {
+    MatchStatsResult out;
+    if (pats.empty()) return out;
+    tc_fm *fm = nullptr;
+    Context::check(tc_fm_build_lcp(Context::get(), (const uint8_t *)input.data(), input.size(), 1, 0, &fm));
+    MatchStats r;
+    try {
+        r = detail::matchStats(fm, pats);
+    } catch (...) {
+        tc_fm_free(fm);
+        throw;
+    }
+    tc_fm_free(fm);
+    for (size_t i = 0; i < pats.size(); i++) {
+        std::vector<std::array<uint64_t, 3>> v;
+        for (uint64_t t = r.offs[i]; t < r.offs[i + 1]; t++) v.push_back({(uint64_t)r.len[t], r.pos[t], (uint64_t)r.occ[t]});
+        out.emplace_back(pats[i], std::move(v));
+    }
+    return out;
+}
+inline MatchStatsResult bytestringFMIndexMatchStatsP(const std::vector<std::string> &pats, const std::string &input) {
+    return bytestringFMIndexMatchStatsS(pats, input);
+}
+// per pattern its (start, pos, len) triples, start 0-based in the pattern
+using MemsResult = std::vector<std::pair<std::string, std::vector<std::array<uint64_t, 3>>>>;
+inline MemsResult bytestringFMIndexMemsS(const std::vector<std::string> &pats, const std::string &input, uint32_t min_len = 1) {
+    MemsResult out;
+    if (pats.empty()) return out;
+    tc_fm *fm = nullptr;
+    Context::check(tc_fm_build_lcp(Context::get(), (const uint8_t *)input.data(), input.size(), 1, 0, &fm));
+    Mems r;
+    try {
+        r = detail::mems(fm, pats, min_len);
+    } catch (...) {
+        tc_fm_free(fm);
+        throw;
+    }
+    tc_fm_free(fm);
+    for (size_t i = 0; i < pats.size(); i++) {
+        std::vector<std::array<uint64_t, 3>> v;
+        for (uint64_t t = r.offs[i]; t < r.offs[i + 1]; t++) v.push_back({r.start[t], r.pos[t], (uint64_t)r.len[t]});
+        out.emplace_back(pats[i], std::move(v));
+    }
+    return out;
+}
+inline MemsResult bytestringFMIndexMemsP(const std::vector<std::string> &pats, const std::string &input, uint32_t min_len = 1) {
+    return bytestringFMIndexMemsS(pats, input, min_len);
+}
+
 // Not in the reference: an index that is kept between queries, optionally with a sampled suffix array (sa_rate > 1: every
 // sa_rate-th entry is kept and locate walks the LF mapping to the next one; textcomp.h), queried with everything in HBM.
 class Index {
@@ -384,12 +484,21 @@ class Index {
     Index(const uint8_t *d_text, uint64_t n, uint32_t sa_rate, uint32_t text_rate) {
         Context::check(tc_fm_build_self_dev(Context::get(), d_text, n, sa_rate, text_rate, &fm_));
     }
+    // with the LCP part (text_rate: 0 or a power of two): the index answers matchStats / mems
+    struct WithLcp {};
+    Index(const std::string &text, uint32_t sa_rate, uint32_t text_rate, WithLcp) {
+        Context::check(tc_fm_build_lcp(Context::get(), (const uint8_t *)text.data(), text.size(), sa_rate, text_rate, &fm_));
+    }
+    Index(const uint8_t *d_text, uint64_t n, uint32_t sa_rate, uint32_t text_rate, WithLcp) {
+        Context::check(tc_fm_build_lcp_dev(Context::get(), d_text, n, sa_rate, text_rate, &fm_));
+    }
     Index(const Index &) = delete;
     Index &operator=(const Index &) = delete;
     ~Index() { tc_fm_free(fm_); }
     uint32_t saRate() const { return tc_fm_sa_rate(fm_); }
     uint32_t textRate() const { return tc_fm_text_rate(fm_); }
-    // part 0: the whole index, part 1: its locate part alone, part 2: its extract part alone
+    bool hasLcp() const { return tc_fm_has_lcp(fm_) != 0; }
+    // part 0: the whole index, part 1: its locate part alone, part 2: its extract part alone, part 3: its LCP part alone
     uint64_t deviceBytes(int part = 0) const { return tc_fm_device_bytes(fm_, part); }
     // d_pats / d_offs [npat + 1] / d_hit_offs [npat + 1] / d_hits [cap]: device arrays.  Returns the number of hits; when it
     // exceeds cap nothing was written to d_hits and the caller repeats the call with that capacity.
@@ -459,6 +568,24 @@ class Index {
         int rc = tc_fm_unfactorize_dev(Context::get(), fm_, d_fac_offs, d_fac_pos, d_fac_len, npat, d_out_offs, d_out, &nb);
         if (rc != TC_ERR_CAPACITY) Context::check(rc);
         return nb;
+    }
+    // matching statistics and maximal exact matches on an index with the LCP part (bytestringFMIndexMatchStatsS / ...MemsS
+    // on the kept index), and the same with everything in HBM: d_ms_len [offs[npat]] and, each or null, d_ms_pos / d_ms_occ;
+    // d_mem_offs [npat + 1], d_mem_start / d_mem_pos / d_mem_len [cap] -- memsDev returns the total; when it exceeds cap
+    // nothing was written to the three arrays and the caller repeats the call with it
+    MatchStats matchStats(const std::vector<std::string> &pats) const { return detail::matchStats(fm_, pats); }
+    Mems mems(const std::vector<std::string> &pats, uint32_t min_len = 1) const { return detail::mems(fm_, pats, min_len); }
+    void matchStatsDev(const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint32_t *d_ms_len, uint64_t *d_ms_pos,
+                       uint32_t *d_ms_occ) const {
+        Context::check(tc_fm_match_stats_dev(Context::get(), fm_, d_pats, d_offs, npat, d_ms_len, d_ms_pos, d_ms_occ));
+    }
+    uint64_t memsDev(const uint8_t *d_pats, const uint64_t *d_offs, uint64_t npat, uint32_t min_len, uint64_t *d_mem_offs,
+                     uint64_t *d_mem_start, uint64_t *d_mem_pos, uint32_t *d_mem_len, uint64_t cap) const {
+        uint64_t nm = cap;
+        int rc = tc_fm_mems_dev(Context::get(), fm_, d_pats, d_offs, npat, min_len, d_mem_offs, d_mem_start, d_mem_pos, d_mem_len,
+                                &nm);
+        if (rc != TC_ERR_CAPACITY) Context::check(rc);
+        return nm;
     }
     const tc_fm *handle() const { return fm_; }
 

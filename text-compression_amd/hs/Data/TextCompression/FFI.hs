@@ -98,6 +98,23 @@ foreign import ccall safe "tc_fm_unfactorize"
   c_tc_fm_unfactorize :: Ptr TcCtx -> Ptr TcFm -> Ptr Word64 -> Ptr Word64 -> Ptr Word32 -> Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
 foreign import ccall safe "tc_fm_unfactorize_dev"
   c_tc_fm_unfactorize_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word64 -> Ptr Word64 -> Ptr Word32 -> Word64 -> Ptr Word64 -> Ptr Word8 -> Ptr Word64 -> IO Int32
+-- matching statistics and maximal exact matches on an index with the LCP part (tc_fm_build_lcp: sa_rate, then text_rate
+-- or 0; no counterpart in the reference): per pattern position the longest match's length, first-row position and
+-- occurrences (the last two may be nullPtr); the MEMs as offsets and (start, position, length), the three nullPtr with
+-- capacity 0 asks for the sizes alone
+foreign import ccall safe "tc_fm_build_lcp"
+  c_tc_fm_build_lcp :: Ptr TcCtx -> Ptr Word8 -> Word64 -> Word32 -> Word32 -> Ptr (Ptr TcFm) -> IO Int32
+foreign import ccall safe "tc_fm_build_lcp_dev"
+  c_tc_fm_build_lcp_dev :: Ptr TcCtx -> Ptr Word8 -> Word64 -> Word32 -> Word32 -> Ptr (Ptr TcFm) -> IO Int32
+foreign import ccall unsafe "tc_fm_has_lcp" c_tc_fm_has_lcp :: Ptr TcFm -> Int32
+foreign import ccall safe "tc_fm_match_stats"
+  c_tc_fm_match_stats :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Ptr Word32 -> Ptr Word64 -> Ptr Word32 -> IO Int32
+foreign import ccall safe "tc_fm_match_stats_dev"
+  c_tc_fm_match_stats_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Ptr Word32 -> Ptr Word64 -> Ptr Word32 -> IO Int32
+foreign import ccall safe "tc_fm_mems"
+  c_tc_fm_mems :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Word32 -> Ptr Word64 -> Ptr Word64 -> Ptr Word64 -> Ptr Word32 -> Ptr Word64 -> IO Int32
+foreign import ccall safe "tc_fm_mems_dev"
+  c_tc_fm_mems_dev :: Ptr TcCtx -> Ptr TcFm -> Ptr Word8 -> Ptr Word64 -> Word64 -> Word32 -> Ptr Word64 -> Ptr Word64 -> Ptr Word64 -> Ptr Word32 -> Ptr Word64 -> IO Int32
 -- stored / shipped form (no counterpart in the reference): one record, or any length cut into records
 foreign import ccall unsafe "tc_container_bound"
   c_tc_container_bound :: Word64 -> Word32 -> Word64

@@ -20,6 +20,7 @@ module Data.TextCompression.GPU
   , bytestringFMIndexCountMismatchS, bytestringFMIndexCountMismatchP
   , bytestringFMIndexLocateMismatchS, bytestringFMIndexLocateMismatchP
   , bytestringFMIndexFactorizeS, bytestringFMIndexFactorizeP
+  , bytestringFMIndexMatchStatsS, bytestringFMIndexMatchStatsP, bytestringFMIndexMemsS, bytestringFMIndexMemsP
   ) where
 
 import Control.Concurrent.MVar (MVar, newMVar, modifyMVar_, withMVar)
@@ -399,3 +400,69 @@ bytestringFMIndexFactorizeS pats input
 
 bytestringFMIndexFactorizeP :: [BS.ByteString] -> BS.ByteString -> IO (Seq (BS.ByteString, Seq (Int, Int)))
 bytestringFMIndexFactorizeP pats input = pure (bytestringFMIndexFactorizeS pats input)
+
+-- | Not in the reference: matching statistics.  For every position of each pattern (length, position, occurrences) of the
+-- longest match that starts there: the 1-based text position of its occurrence in the first suffix-array row and the
+-- number of its occurrences; (0, 0, 0) where the byte does not occur in the text.  The index is built with its LCP part
+-- (tc_fm_build_lcp, full suffix array, no text samples); one device call.
+bytestringFMIndexMatchStatsS :: [BS.ByteString] -> BS.ByteString -> Seq (BS.ByteString, Seq (Int, Int, Int))
+bytestringFMIndexMatchStatsS pats input
+  | null pats = DS.Empty
+  | otherwise = unsafePerformIO $ withCtx $ \ctx ->
+      BSU.unsafeUseAsCStringLen input $ \(p, n) -> alloca $ \ph -> do
+        c_tc_fm_build_lcp ctx (castPtr p) (fromIntegral n) 1 0 ph >>= check ctx
+        fm <- peek ph
+        let np    = length pats
+            flat  = BS.concat pats `BS.snoc` 0
+            offs  = scanl (+) 0 (map (fromIntegral . BS.length) pats)
+            total = sum (map BS.length pats)
+        rows <- BSU.unsafeUseAsCString flat $ \fp -> withArray offs $ \op ->
+          allocaArray (max 1 total) $ \ml -> allocaArray (max 1 total) $ \mp -> allocaArray (max 1 total) $ \mo -> do
+            rc <- c_tc_fm_match_stats ctx fm (castPtr fp) op (fromIntegral np) ml mp mo
+            c_tc_fm_free fm
+            check ctx rc
+            ls <- map fromIntegral <$> peekArray total ml
+            as <- map fromIntegral <$> peekArray total mp
+            cs <- map fromIntegral <$> peekArray total mo
+            pure (zip3 ls as cs)
+        let os     = map fromIntegral offs :: [Int]
+            slices = [ take (e - a) (drop a rows) | (a, e) <- zip os (tail os) ]
+        pure . DS.fromList $ [ (q, DS.fromList r) | (q, r) <- zip pats slices ]
+
+bytestringFMIndexMatchStatsP :: [BS.ByteString] -> BS.ByteString -> IO (Seq (BS.ByteString, Seq (Int, Int, Int)))
+bytestringFMIndexMatchStatsP pats input = pure (bytestringFMIndexMatchStatsS pats input)
+
+-- | Not in the reference: the maximal exact matches of at least minLen bytes of each pattern, as (start, position,
+-- length) in increasing start (0-based in the pattern): the matches that are contained in no longer match of the same
+-- pattern.  Two device calls: tc_fm_mems in its sizes-only form, then with room for the matches.
+bytestringFMIndexMemsS :: Int -> [BS.ByteString] -> BS.ByteString -> Seq (BS.ByteString, Seq (Int, Int, Int))
+bytestringFMIndexMemsS minLen pats input
+  | null pats = DS.Empty
+  | otherwise = unsafePerformIO $ withCtx $ \ctx ->
+      BSU.unsafeUseAsCStringLen input $ \(p, n) -> alloca $ \ph -> do
+        c_tc_fm_build_lcp ctx (castPtr p) (fromIntegral n) 1 0 ph >>= check ctx
+        fm <- peek ph
+        let np   = length pats
+            flat = BS.concat pats `BS.snoc` 0
+            offs = scanl (+) 0 (map (fromIntegral . BS.length) pats)
+        (os, ms) <- BSU.unsafeUseAsCString flat $ \fp -> withArray offs $ \op ->
+          allocaArray (np + 1) $ \mo -> with 0 $ \nm -> do
+            rc0 <- c_tc_fm_mems ctx fm (castPtr fp) op (fromIntegral np) (fromIntegral minLen) mo nullPtr nullPtr nullPtr nm
+            when (rc0 /= 0) (c_tc_fm_free fm)
+            check ctx rc0
+            total <- fromIntegral <$> peek nm
+            allocaArray (max 1 total) $ \mst -> allocaArray (max 1 total) $ \mpos -> allocaArray (max 1 total) $ \mlen -> do
+              rc <- if total == 0 then pure 0
+                    else c_tc_fm_mems ctx fm (castPtr fp) op (fromIntegral np) (fromIntegral minLen) mo mst mpos mlen nm
+              c_tc_fm_free fm
+              check ctx rc
+              os <- map fromIntegral <$> peekArray (np + 1) mo
+              ss <- map fromIntegral <$> peekArray total mst
+              as <- map fromIntegral <$> peekArray total mpos
+              ls <- map fromIntegral <$> peekArray total mlen
+              pure (os, zip3 ss as ls)
+        let slices = [ take (e - a) (drop a ms) | (a, e) <- zip os (tail os) ]
+        pure . DS.fromList $ [ (q, DS.fromList m) | (q, m) <- zip pats slices ]
+
+bytestringFMIndexMemsP :: Int -> [BS.ByteString] -> BS.ByteString -> IO (Seq (BS.ByteString, Seq (Int, Int, Int)))
+bytestringFMIndexMemsP minLen pats input = pure (bytestringFMIndexMemsS minLen pats input)

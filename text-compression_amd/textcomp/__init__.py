@@ -412,19 +412,22 @@ class Context:
         return out[:got.value].tobytes()
 
     # ----------------------------------------------------------- FM-index
-    def fm_build(self, text, sa_rate=1, text_rate=0):
+    def fm_build(self, text, sa_rate=1, text_rate=0, lcp=False):
         """sa_rate > 1 (a power of two up to TC_FM_MAX_SA_RATE): keep every sa_rate-th suffix-array entry only
         (tc_fm_build_sampled); locate answers the same hits by walking the LF mapping.  text_rate > 0 (a power of two
         up to TC_FM_MAX_SA_RATE): also keep the row of every text_rate-th text position (tc_fm_build_self), so that
-        extract can read text ranges back from the index"""
-        return FMIndexHandle(self, text, sa_rate=sa_rate, text_rate=text_rate)
+        extract can read text ranges back from the index.  lcp: also keep the LCP array and its min tree
+        (tc_fm_build_lcp), so that match_stats and mems work"""
+        return FMIndexHandle(self, text, sa_rate=sa_rate, text_rate=text_rate, lcp=lcp)
 
-    def fm_build_dev(self, d_text, sa_rate=1, text_rate=0):
+    def fm_build_dev(self, d_text, sa_rate=1, text_rate=0, lcp=False):
         """index of a text that already lies in HBM (a torch uint8 tensor on this context's device): tc_fm_build_dev /
-        tc_fm_build_sampled_dev / tc_fm_build_self_dev"""
+        tc_fm_build_sampled_dev / tc_fm_build_self_dev / tc_fm_build_lcp_dev"""
         h = C.c_void_p()
         p = C.c_void_p(d_text.data_ptr()) if d_text.numel() else None
-        if text_rate:
+        if lcp:
+            self._check(self.lib.tc_fm_build_lcp_dev(self.handle, p, d_text.numel(), int(sa_rate), int(text_rate), C.byref(h)))
+        elif text_rate:
             self._check(self.lib.tc_fm_build_self_dev(self.handle, p, d_text.numel(), int(sa_rate), int(text_rate), C.byref(h)))
         elif sa_rate == 1:
             self._check(self.lib.tc_fm_build_dev(self.handle, p, d_text.numel(), C.byref(h)))
@@ -436,14 +439,16 @@ class Context:
 class FMIndexHandle:
     """`tc_fm`: the device-resident FM-index of one text."""
 
-    def __init__(self, ctx, text, _handle=None, _n=0, sa_rate=1, text_rate=0):
+    def __init__(self, ctx, text, _handle=None, _n=0, sa_rate=1, text_rate=0, lcp=False):
         self._ctx = ctx
         if _handle is not None:      # an index that arrived from another GPU (textcomp.fmshard)
             self._h, self.n = _handle, _n
             return
         t = _u8(text)
         h = C.c_void_p()
-        if text_rate:
+        if lcp:
+            ctx._check(ctx.lib.tc_fm_build_lcp(ctx.handle, _ptr(t) if len(t) else None, len(t), int(sa_rate), int(text_rate), C.byref(h)))
+        elif text_rate:
             ctx._check(ctx.lib.tc_fm_build_self(ctx.handle, _ptr(t) if len(t) else None, len(t), int(sa_rate), int(text_rate), C.byref(h)))
         elif sa_rate == 1:
             ctx._check(ctx.lib.tc_fm_build(ctx.handle, _ptr(t) if len(t) else None, len(t), C.byref(h)))
@@ -462,8 +467,14 @@ class FMIndexHandle:
         """k >= 1: the row of every k-th text position is kept (extract works); 0: no text samples"""
         return int(self._ctx.lib.tc_fm_text_rate(self._h))
 
+    @property
+    def has_lcp(self):
+        """True: the index holds the LCP part (built with lcp=True), match_stats and mems work"""
+        return bool(self._ctx.lib.tc_fm_has_lcp(self._h))
+
     def device_bytes(self, part=0):
-        """device bytes the index holds: part 0 = everything, 1 = the locate part alone, 2 = the extract part alone"""
+        """device bytes the index holds: part 0 = everything, 1 = the locate part alone, 2 = the extract part alone,
+        3 = the LCP part alone"""
         return int(self._ctx.lib.tc_fm_device_bytes(self._h, int(part)))
 
     def extract(self, starts, lens):
@@ -790,6 +801,91 @@ class FMIndexHandle:
             cap = max(int(nb.value), 1)
         ctx._check(rc)
         return offs, out[:int(nb.value)]
+
+    def match_stats(self, pats, pos=True, occ=True):
+        """matching statistics of each pattern on an index with the LCP part -> (ms_len uint32, ms_pos uint64 or None,
+        ms_occ uint32 or None), each [total pattern bytes]: entry offs[j] + i is, for position i of pattern j, the length
+        of the longest match that starts there, the 1-based text position of its occurrence in the first suffix-array
+        row, and the number of its occurrences (0, 0, 0: the byte does not occur): tc_fm_match_stats"""
+        ctx = self._ctx
+        flat, offs = self._pack(pats)
+        total = int(offs[-1])
+        ms_len = np.zeros(total, np.uint32)
+        ms_pos = np.zeros(total, np.uint64) if pos else None
+        ms_occ = np.zeros(total, np.uint32) if occ else None
+        if len(pats):
+            ctx._check(ctx.lib.tc_fm_match_stats(ctx.handle, self._h, _ptr(flat), _ptr(offs), len(pats), _ptr(ms_len),
+                                                 _ptr(ms_pos) if pos else None, _ptr(ms_occ) if occ else None))
+        return ms_len, ms_pos, ms_occ
+
+    def match_stats_dev(self, d_pats, d_offs, npat, total, pos=True, occ=True):
+        """patterns resident on the device (as count_dev; total = offs[npat], the pattern bytes) -> (ms_len int32 tensor,
+        ms_pos int64 tensor or None, ms_occ int32 tensor or None), each [total], on the device: tc_fm_match_stats_dev"""
+        import torch
+        ctx = self._ctx
+        dev = d_pats.device
+        ms_len = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)[:total]
+        ms_pos = torch.zeros(max(total, 1), dtype=torch.int64, device=dev)[:total] if pos else None
+        ms_occ = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)[:total] if occ else None
+        torch.cuda.synchronize()
+        if npat:
+            ctx._check(ctx.lib.tc_fm_match_stats_dev(ctx.handle, self._h, C.c_void_p(d_pats.data_ptr()), C.c_void_p(d_offs.data_ptr()),
+                                                     npat, C.c_void_p(ms_len.data_ptr()),
+                                                     C.c_void_p(ms_pos.data_ptr()) if pos else None,
+                                                     C.c_void_p(ms_occ.data_ptr()) if occ else None))
+        return ms_len, ms_pos, ms_occ
+
+    def mems(self, pats, min_len=1):
+        """the maximal exact matches of at least min_len bytes of each pattern on an index with the LCP part ->
+        (mem_offs uint64 [npat + 1], mem_start uint64 [total], mem_pos uint64 [total], mem_len uint32 [total]): pattern
+        j's MEMs are [mem_offs[j], mem_offs[j + 1]), in increasing start (0-based in the pattern); mem_pos is the 1-based
+        text position of the occurrence in the first suffix-array row: tc_fm_mems"""
+        ctx = self._ctx
+        npat = len(pats)
+        moffs = np.zeros(npat + 1, np.uint64)
+        if npat == 0:
+            return moffs, np.empty(0, np.uint64), np.empty(0, np.uint64), np.empty(0, np.uint32)
+        flat, offs = self._pack(pats)
+        cap = 1 << 16
+        while True:
+            mstart, mpos, mlen = np.empty(cap, np.uint64), np.empty(cap, np.uint64), np.empty(cap, np.uint32)
+            nm = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_mems(ctx.handle, self._h, _ptr(flat), _ptr(offs), npat, int(min_len), _ptr(moffs), _ptr(mstart),
+                                    _ptr(mpos), _ptr(mlen), C.byref(nm))
+            if rc == _lib.TC_ERR_CAPACITY and int(nm.value) > cap:
+                cap = int(nm.value)
+                continue
+            ctx._check(rc)
+            break
+        k = int(nm.value)
+        return moffs, mstart[:k].copy(), mpos[:k].copy(), mlen[:k].copy()
+
+    def mems_dev(self, d_pats, d_offs, npat, min_len=1, cap=None):
+        """patterns resident on the device (as count_dev) -> (mem_offs int64 tensor [npat + 1], mem_start int64 tensor
+        [total], mem_pos int64 tensor [total], mem_len int32 tensor [total]), all on the device: tc_fm_mems_dev"""
+        import torch
+        ctx = self._ctx
+        dev = d_pats.device
+        moffs = torch.zeros(npat + 1, dtype=torch.int64, device=dev)
+        if npat == 0:
+            z = torch.zeros(0, dtype=torch.int64, device=dev)
+            return moffs, z, z.clone(), torch.zeros(0, dtype=torch.int32, device=dev)
+        cap = max(int(cap) if cap is not None else 4 * npat, 1)
+        for _ in range(2):
+            mstart = torch.empty(cap, dtype=torch.int64, device=dev)
+            mpos = torch.empty(cap, dtype=torch.int64, device=dev)
+            mlen = torch.empty(cap, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
+            nm = C.c_uint64(cap)
+            rc = ctx.lib.tc_fm_mems_dev(ctx.handle, self._h, C.c_void_p(d_pats.data_ptr()), C.c_void_p(d_offs.data_ptr()), npat,
+                                        int(min_len), C.c_void_p(moffs.data_ptr()), C.c_void_p(mstart.data_ptr()),
+                                        C.c_void_p(mpos.data_ptr()), C.c_void_p(mlen.data_ptr()), C.byref(nm))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nm.value), 1)
+        ctx._check(rc)
+        k = int(nm.value)
+        return moffs, mstart[:k], mpos[:k], mlen[:k]
 
     def info(self):
         ctx = self._ctx

@@ -127,6 +127,13 @@ SYMBOLS = [
     ("tc_fm_factorize_dev", _INT, [_P, _P, _P, _P, _U64, _P, _P, _P, _PU64]),
     ("tc_fm_unfactorize", _INT, [_P, _P, _P, _P, _P, _U64, _P, _P, _PU64]),
     ("tc_fm_unfactorize_dev", _INT, [_P, _P, _P, _P, _P, _U64, _P, _P, _PU64]),
+    ("tc_fm_build_lcp", _INT, [_P, _P, _U64, _U32, _U32, C.POINTER(_P)]),
+    ("tc_fm_build_lcp_dev", _INT, [_P, _P, _U64, _U32, _U32, C.POINTER(_P)]),
+    ("tc_fm_has_lcp", _INT, [_P]),
+    ("tc_fm_match_stats", _INT, [_P, _P, _P, _P, _U64, _P, _P, _P]),
+    ("tc_fm_match_stats_dev", _INT, [_P, _P, _P, _P, _U64, _P, _P, _P]),
+    ("tc_fm_mems", _INT, [_P, _P, _P, _P, _U64, _U32, _P, _P, _P, _P, _PU64]),
+    ("tc_fm_mems_dev", _INT, [_P, _P, _P, _P, _U64, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_fm_info", _INT, [_P, _PU64, _PU32, _P, _P, _PU64]),
     ("tc_comm_unique_id", _INT, [_P, _P]),
     ("tc_comm_create", _INT, [_P, _P, _INT, _INT, C.POINTER(_P)]),

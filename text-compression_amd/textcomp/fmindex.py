@@ -97,6 +97,49 @@ def bytestringFMIndexFactorizeP(pats, text, ctx=None):
     return bytestringFMIndexFactorizeS(pats, text, ctx)
 
 
+# ---- matching statistics and maximal exact matches (no counterpart in the reference) ----
+def bytestringFMIndexMatchStatsS(pats, text, ctx=None):
+    """[(pattern, [(len, pos, occ)])]: for every position of each pattern the length of the longest match that starts
+    there, the 1-based text position of its occurrence in the first suffix-array row and the number of its occurrences;
+    (0, 0, 0) where the byte does not occur in the text.  Empty pattern list => empty result; against an empty text every
+    entry is (0, 0, 0)."""
+    if len(pats) == 0:
+        return []
+    fm = (ctx or default_context()).fm_build(text, lcp=True)
+    try:
+        ms_len, ms_pos, ms_occ = fm.match_stats(pats)
+    finally:
+        fm.close()
+    out, o = [], 0
+    for p in pats:
+        out.append((p, [(int(ms_len[o + i]), int(ms_pos[o + i]), int(ms_occ[o + i])) for i in range(len(p))]))
+        o += len(p)
+    return out
+
+
+def bytestringFMIndexMatchStatsP(pats, text, ctx=None):
+    """the same values in the same order: the batch is one launch either way"""
+    return bytestringFMIndexMatchStatsS(pats, text, ctx)
+
+
+def bytestringFMIndexMemsS(pats, text, min_len=1, ctx=None):
+    """[(pattern, [(start, pos, len)])]: the maximal exact matches of at least min_len bytes of each pattern, in
+    increasing start (0-based in the pattern); pos as in bytestringFMIndexMatchStatsS."""
+    if len(pats) == 0:
+        return []
+    fm = (ctx or default_context()).fm_build(text, lcp=True)
+    try:
+        moffs, mstart, mpos, mlen = fm.mems(pats, min_len)
+    finally:
+        fm.close()
+    return [(p, [(int(mstart[k]), int(mpos[k]), int(mlen[k])) for k in range(int(moffs[i]), int(moffs[i + 1]))])
+            for i, p in enumerate(pats)]
+
+
+def bytestringFMIndexMemsP(pats, text, min_len=1, ctx=None):
+    return bytestringFMIndexMemsS(pats, text, min_len, ctx)
+
+
 # ---- Text instantiations (FMIndex.hs:385-403,436-462,503-530,570-599) ----------------------------
 # The index is built over the UTF-8 bytes, each turned into a Text by decodeUtf8 . BS.singleton
 # (ASCII only, an exception otherwise); patterns are split into characters.  For ASCII input that is
@@ -221,3 +264,27 @@ def textFMIndexFactorizeS(pats, text, ctx=None):
 
 def textFMIndexFactorizeP(pats, text, ctx=None):
     return textFMIndexFactorizeS(pats, text, ctx)
+
+
+def textFMIndexMatchStatsS(pats, text, ctx=None):
+    """bytestringFMIndexMatchStatsS over the UTF-8 bytes (ASCII only, as the other text... variants)."""
+    if len(pats) == 0:
+        return []
+    res = bytestringFMIndexMatchStatsS([p.encode("utf-8") for p in pats], _ascii_bytes(text), ctx)
+    return [(p, f) for p, (_, f) in zip(pats, res)]
+
+
+def textFMIndexMatchStatsP(pats, text, ctx=None):
+    return textFMIndexMatchStatsS(pats, text, ctx)
+
+
+def textFMIndexMemsS(pats, text, min_len=1, ctx=None):
+    """bytestringFMIndexMemsS over the UTF-8 bytes (ASCII only)."""
+    if len(pats) == 0:
+        return []
+    res = bytestringFMIndexMemsS([p.encode("utf-8") for p in pats], _ascii_bytes(text), min_len, ctx)
+    return [(p, f) for p, (_, f) in zip(pats, res)]
+
+
+def textFMIndexMemsP(pats, text, min_len=1, ctx=None):
+    return textFMIndexMemsS(pats, text, min_len, ctx)
