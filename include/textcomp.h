@@ -173,6 +173,36 @@ int tc_lcp_array(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *sa, uin
  * holds it (rows row-1 and row of the suffix array are the longest repeat), *sum = the sum of all entries (the text
  * has n(n+1)/2 - sum distinct substrings).  N == 0: TC_ERR_ARG. */
 int tc_lcp_summary_dev(tc_ctx *ctx, const uint32_t *d_lcp, uint64_t N, uint32_t *max_lcp, uint64_t *row, uint64_t *sum);
+/* ---- the LZ77 parse of a text against itself (not part of the reference's surface) ----
+ * lcp(i, j) = the length of the longest common prefix of text[i..n) and text[j..n); the end of the text matches nothing.
+ * THE LPF ARRAY, n entries, all positions 0-based: lpf[i] = the maximum of lcp(i, j) over j < i (0 for i = 0); the source
+ * may overlap the phrase (j + lpf[i] > i is allowed).  src[i]: among the suffixes that start before i, suffix i has two
+ * lexicographic neighbours -- the largest that is smaller and the smallest that is larger (in suffix-array order the end
+ * of the text sorts first); src[i] is the start of the one that shares the longer prefix with suffix i, on a tie of the
+ * smaller one, and 0 where lpf[i] = 0.  src (d_src) may be NULL.
+ * THE PARSE is greedy, left to right: at position i, lpf[i] = 0 gives the literal phrase (ph_src = text[i], ph_len = 0)
+ * and i += 1; otherwise the copy phrase (ph_src = src[i], ph_len = lpf[i]) and i += lpf[i].  ph_len = 0 marks literals, as
+ * in tc_fm_factorize.  The empty text has 0 phrases; 64 times "a" parses to (97, 0), (0, 63).  *nph: in = capacity of
+ * the two arrays, out = the phrase count.  A capacity that is too small: TC_ERR_CAPACITY, *nph = the needed count, nothing
+ * written to the arrays.  ph_src = ph_len = NULL with capacity 0 is the sizes-only form: TC_OK, the count written.
+ * THE INVERSE: a copy phrase that starts at output position s copies text[ph_src + k] to text[s + k] for k = 0 .. len - 1
+ * in increasing order, so an overlapping source is well defined; tc_lz_unparse(tc_lz_parse(text)) = text for every byte
+ * string.  *nbytes: in = capacity of text, out = the bytes; too small: TC_ERR_CAPACITY, *nbytes = the needed count, nothing
+ * written; text = NULL with capacity 0 is the sizes-only form.  A bad phrase list -- a copy with ph_src >= its own start
+ * position, a literal with ph_src > 255, a total above TC_MAX_N -- is TC_ERR_ARG with nothing written to text.
+ * ERRORS AND EDGES.  Null buffers or n > TC_MAX_N: TC_ERR_ARG.  n = 0: TC_OK, 0 phrases, nothing read or written.
+ * nph = 0: 0 bytes.  The parse and LPF calls take the text only: the suffix array, the LCP array and all scratch (20 bytes
+ * per text byte behind the sort: sa 4, lcp 4, (lpf, src) 8, the tiles' exits 4; the sort's own need where that is larger)
+ * live in the calling ctx's workspace.
+ * The _dev forms take every array in HBM; nph and nbytes stay host words.  The unparse scratch is at most 24 bytes per phrase
+ * and 8 bytes per byte of the text (not of the capacity). */
+int tc_lpf_array(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *lpf, uint32_t *src);
+int tc_lpf_array_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_lpf, uint32_t *d_src);
+int tc_lz_parse(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *ph_src, uint32_t *ph_len, uint64_t *nph);
+int tc_lz_parse_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_ph_src, uint32_t *d_ph_len, uint64_t *nph);
+int tc_lz_unparse(tc_ctx *ctx, const uint32_t *ph_src, const uint32_t *ph_len, uint64_t nph, uint8_t *text, uint64_t *nbytes);
+int tc_lz_unparse_dev(tc_ctx *ctx, const uint32_t *d_ph_src, const uint32_t *d_ph_len, uint64_t nph, uint8_t *d_text,
+                      uint64_t *nbytes);
 
 /* bytestringFromWord8BWT (BWT.hs:108-110) = fromBWT (:93-104) + sortTB
  * (BWT/Internal.hs:144-149) + magicInverseBWT (:163-200), for a well-formed BWT

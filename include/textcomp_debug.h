@@ -38,6 +38,11 @@ int tc_dbg_lcp_set_short_cap(tc_ctx *ctx, uint32_t cap);
  * TC_ERR_ARG.  The fan-out is stored in the index; the results do not depend on it.  It exists so that tests reach every
  * level of the tree at a thousand rows. */
 int tc_dbg_fm_set_lcp_fanout(tc_ctx *ctx, uint32_t fanout);
+/* The positions per tile of the phrase-start steps of the later tc_lz_parse / tc_lz_parse_dev calls of this context
+ * (csrc/tc_lz.hpp): a power of two in 64 .. 16384, or 0 for the library's LZ_TILE; anything else is TC_ERR_ARG.  The
+ * results do not depend on it.  It exists so that tests reach tile boundaries at a few thousand bytes.  (The two min
+ * trees of those calls have the fan-out tc_dbg_fm_set_lcp_fanout set.) */
+int tc_dbg_lz_set_tile(tc_ctx *ctx, uint32_t tile);
 /* *used = 1 if round 0 of this context's last suffix sort (an encode runs one) went the MSD way with levels 1 and 2 in
  * the split key layout (csrc/tc_msd.hpp: two arrays of 32-bit key halves; TC_MSD_SPLIT), 0 if not -- the LSD way, levels
  * that move suffix starts, TC_SA_MSD_JOINT=0, or a second run of the levels with suffix starts. */

@@ -46,6 +46,7 @@ struct tc_ctx {
     u32 stats_ws_grown = 0;  // how often a chunked workspace grew in place
     u32 lcp_cap = 0;       // short cap of the LCP compare kernel set by tc_dbg_lcp_set_short_cap (0: TC_LCP_SHORT_CAP, tc_lcp.hpp)
     u32 fm_lcp_fanout = 0; // fan-out of the min tree of the indexes tc_fm_build_lcp makes on this context, set by tc_dbg_fm_set_lcp_fanout (0: FM_LCP_FANOUT, tc_fm_host.hpp)
+    u32 lz_tile = 0;       // positions per tile of the LZ77 parse, set by tc_dbg_lz_set_tile (0: LZ_TILE, tc_lz.hpp)
     int msd_dir_used = 0;    // the last suffix sort's aligned MSD level ran with the directory of live parents (tc_dbg_msd_dir)
     int msd_split_used = 0;  // the last suffix sort's MSD levels 1 and 2 used the split key layout (tc_dbg_msd_split_used)
     // the last inverse BWT's walks (ibwt_walk_rank_copy; tc_dbg_ibwt_walk): attempts run, and of the last of them the

@@ -7,6 +7,7 @@
 #include "tc_ws_host.hpp"
 #include "tc_fm_host.hpp"
 #include "tc_lcp_host.hpp"
+#include "tc_lz_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -169,6 +170,44 @@ int tc_lcp_array(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *sa, uin
 int tc_lcp_summary_dev(tc_ctx *ctx, const uint32_t *d_lcp, uint64_t N, uint32_t *max_lcp, uint64_t *row, uint64_t *sum) {
     TC_API_BEGIN(ctx)
     lcp_summary_entry(ctx, d_lcp, N, max_lcp, row, sum);
+    TC_API_END(ctx)
+}
+
+// the LPF array, the LZ77 parse of a text against itself and its inverse (no counterpart in the reference): tc_lz_host.hpp
+int tc_lpf_array(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *lpf, uint32_t *src) {
+    TC_API_BEGIN(ctx)
+    lpf_array_entry(ctx, text, n, lpf, src, false);
+    TC_API_END(ctx)
+}
+
+int tc_lpf_array_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_lpf, uint32_t *d_src) {
+    TC_API_BEGIN(ctx)
+    lpf_array_entry(ctx, d_text, n, d_lpf, d_src, true);
+    TC_API_END(ctx)
+}
+
+int tc_lz_parse(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *ph_src, uint32_t *ph_len, uint64_t *nph) {
+    TC_API_BEGIN(ctx)
+    lz_parse_entry(ctx, text, n, ph_src, ph_len, nph, false);
+    TC_API_END(ctx)
+}
+
+int tc_lz_parse_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_ph_src, uint32_t *d_ph_len, uint64_t *nph) {
+    TC_API_BEGIN(ctx)
+    lz_parse_entry(ctx, d_text, n, d_ph_src, d_ph_len, nph, true);
+    TC_API_END(ctx)
+}
+
+int tc_lz_unparse(tc_ctx *ctx, const uint32_t *ph_src, const uint32_t *ph_len, uint64_t nph, uint8_t *text, uint64_t *nbytes) {
+    TC_API_BEGIN(ctx)
+    lz_unparse_entry(ctx, ph_src, ph_len, nph, text, nbytes, false);
+    TC_API_END(ctx)
+}
+
+int tc_lz_unparse_dev(tc_ctx *ctx, const uint32_t *d_ph_src, const uint32_t *d_ph_len, uint64_t nph, uint8_t *d_text,
+                      uint64_t *nbytes) {
+    TC_API_BEGIN(ctx)
+    lz_unparse_entry(ctx, d_ph_src, d_ph_len, nph, d_text, nbytes, true);
     TC_API_END(ctx)
 }
 
@@ -675,6 +714,16 @@ int tc_dbg_fm_set_lcp_fanout(tc_ctx *ctx, uint32_t fanout) {
         return TC_ERR_ARG;
     }
     ctx->fm_lcp_fanout = fanout;
+    return TC_OK;
+}
+
+int tc_dbg_lz_set_tile(tc_ctx *ctx, uint32_t tile) {
+    if (!ctx) return TC_ERR_ARG;
+    if (tile != 0 && (tile < 64 || tile > LZ_TILE_MAX || (tile & (tile - 1)) != 0)) {
+        ctx->err = "the tile of the LZ77 parse is a power of two in 64 .. 16384, or 0";
+        return TC_ERR_ARG;
+    }
+    ctx->lz_tile = tile;
     return TC_OK;
 }
 

@@ -207,6 +207,117 @@ class Context:
         _, d_lcp = self._esa_dev(text)
         return n * (n + 1) // 2 - self.lcp_summary_dev(d_lcp)[2]
 
+    # ------------------------------------- LPF array, LZ77 parse of a text against itself, and its inverse
+    def lpf_array(self, text):
+        """-> (lpf, src), two uint32 arrays of n entries, 0-based: lpf[i] = the longest prefix of text[i:] that also starts
+        at some j < i (the source may overlap), src[i] = such a j (0 where lpf[i] = 0): tc_lpf_array"""
+        t = _u8(text)
+        lpf = np.empty(len(t), np.uint32)
+        src = np.empty(len(t), np.uint32)
+        if len(t) == 0:
+            return lpf, src
+        self._check(self._lib.tc_lpf_array(self._h, _ptr(t) if len(t) else None, len(t), _ptr(lpf), _ptr(src)))
+        return lpf, src
+
+    def lz_phrase_count(self, text):
+        """the number z of phrases of the LZ77 parse of text (the sizes-only form of tc_lz_parse)"""
+        t = _u8(text)
+        nph = C.c_uint64(0)
+        self._check(self._lib.tc_lz_parse(self._h, _ptr(t) if len(t) else None, len(t), None, None, C.byref(nph)))
+        return int(nph.value)
+
+    def lz_parse(self, text):
+        """the greedy left-to-right LZ77 parse of text against itself -> (ph_src, ph_len), two uint32 arrays of z entries:
+        a copy is (0-based source position, length >= 1), a literal (byte value, 0): tc_lz_parse"""
+        t = _u8(text)
+        cap = max(self.lz_phrase_count(t), 1)
+        ph_src = np.empty(cap, np.uint32)
+        ph_len = np.empty(cap, np.uint32)
+        nph = C.c_uint64(cap)
+        self._check(self._lib.tc_lz_parse(self._h, _ptr(t) if len(t) else None, len(t), _ptr(ph_src), _ptr(ph_len), C.byref(nph)))
+        return ph_src[:int(nph.value)].copy(), ph_len[:int(nph.value)].copy()
+
+    def lz_unparse(self, ph_src, ph_len):
+        """the inverse of lz_parse -> bytes: tc_lz_unparse.  TcError (TC_ERR_ARG) for a list no parse is."""
+        ps = np.ascontiguousarray(ph_src, dtype=np.uint32)
+        pl = np.ascontiguousarray(ph_len, dtype=np.uint32)
+        if ps.ndim != 1 or ps.shape != pl.shape:
+            raise ValueError("ph_src and ph_len of one length")
+        nph = len(ps)
+        if nph == 0:
+            return b""
+        nb = C.c_uint64(0)
+        self._check(self._lib.tc_lz_unparse(self._h, _ptr(ps), _ptr(pl), nph, None, C.byref(nb)))
+        out = np.empty(int(nb.value), np.uint8)
+        self._check(self._lib.tc_lz_unparse(self._h, _ptr(ps), _ptr(pl), nph, _ptr(out), C.byref(nb)))
+        return out[:int(nb.value)].tobytes()
+
+    def lpf_array_dev(self, d_text, src=True):
+        """text resident in HBM (a torch uint8 tensor on this context's device) -> (lpf, src), two int32 tensors of n
+        entries on the device (src None when not asked for): tc_lpf_array_dev"""
+        import torch
+        n = d_text.numel()
+        d_lpf = torch.empty(n, dtype=torch.int32, device=d_text.device)
+        d_src = torch.empty(n, dtype=torch.int32, device=d_text.device) if src else None
+        if n == 0:
+            return d_lpf, d_src
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_lpf_array_dev(self._h, C.c_void_p(d_text.data_ptr()) if n else None, n,
+                                               C.c_void_p(d_lpf.data_ptr()), C.c_void_p(d_src.data_ptr()) if src else None))
+        return d_lpf, d_src
+
+    def lz_parse_dev(self, d_text, cap=None):
+        """text resident in HBM -> (ph_src, ph_len), two int32 tensors of z entries on the device: tc_lz_parse_dev.  cap:
+        the phrase slots to try first (None: the sizes-only form runs first)"""
+        import torch
+        n = d_text.numel()
+        pt = C.c_void_p(d_text.data_ptr()) if n else None
+        torch.cuda.synchronize()
+        if cap is None:
+            nph = C.c_uint64(0)
+            self._check(self._lib.tc_lz_parse_dev(self._h, pt, n, None, None, C.byref(nph)))
+            cap = int(nph.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            ph_src = torch.empty(cap, dtype=torch.int32, device=d_text.device)
+            ph_len = torch.empty(cap, dtype=torch.int32, device=d_text.device)
+            torch.cuda.synchronize()
+            nph = C.c_uint64(cap)
+            rc = self._lib.tc_lz_parse_dev(self._h, pt, n, C.c_void_p(ph_src.data_ptr()), C.c_void_p(ph_len.data_ptr()), C.byref(nph))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nph.value), 1)
+        self._check(rc)
+        return ph_src[:int(nph.value)], ph_len[:int(nph.value)]
+
+    def lz_unparse_dev(self, d_ph_src, d_ph_len, cap=None):
+        """a phrase list resident in HBM (two 32-bit tensors of one length) -> the text, a uint8 tensor on the device:
+        tc_lz_unparse_dev.  cap: the bytes to try first (None: the sizes-only form runs first)"""
+        import torch
+        if d_ph_src.numel() != d_ph_len.numel() or d_ph_src.element_size() != 4 or d_ph_len.element_size() != 4:
+            raise ValueError("d_ph_src and d_ph_len must hold the same number of 32-bit entries")
+        nph = d_ph_src.numel()
+        dev = d_ph_src.device
+        if nph == 0:
+            return torch.zeros(0, dtype=torch.uint8, device=dev)
+        ps, pl = C.c_void_p(d_ph_src.data_ptr()), C.c_void_p(d_ph_len.data_ptr())
+        torch.cuda.synchronize()
+        if cap is None:
+            nb = C.c_uint64(0)
+            self._check(self._lib.tc_lz_unparse_dev(self._h, ps, pl, nph, None, C.byref(nb)))
+            cap = int(nb.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            nb = C.c_uint64(cap)
+            rc = self._lib.tc_lz_unparse_dev(self._h, ps, pl, nph, C.c_void_p(out.data_ptr()), C.byref(nb))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nb.value), 1)
+        self._check(rc)
+        return out[:int(nb.value)]
+
     def bwt_decode(self, L, primary):
         L = _u8(L)
         N = len(L)

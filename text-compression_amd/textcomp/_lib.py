@@ -75,6 +75,12 @@ SYMBOLS = [
     ("tc_lcp_array_dev", _INT, [_P, _P, _U64, _P, _P]),
     ("tc_lcp_array", _INT, [_P, _P, _U64, _P, _P]),
     ("tc_lcp_summary_dev", _INT, [_P, _P, _U64, _PU32, _PU64, _PU64]),
+    ("tc_lpf_array", _INT, [_P, _P, _U64, _P, _P]),
+    ("tc_lpf_array_dev", _INT, [_P, _P, _U64, _P, _P]),
+    ("tc_lz_parse", _INT, [_P, _P, _U64, _P, _P, _PU64]),
+    ("tc_lz_parse_dev", _INT, [_P, _P, _U64, _P, _P, _PU64]),
+    ("tc_lz_unparse", _INT, [_P, _P, _P, _U64, _P, _PU64]),
+    ("tc_lz_unparse_dev", _INT, [_P, _P, _P, _U64, _P, _PU64]),
     ("tc_bwt_decode", _INT, [_P, _P, _U64, _U64, _P]),
     ("tc_bwt_decode_sym", _INT, [_P, _P, _U64, _P, _PU64]),
     ("tc_mtf_encode", _INT, [_P, _P, _U64, _I64, _P, _P, _PU32]),
