@@ -203,6 +203,39 @@ int tc_lz_parse_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_
 int tc_lz_unparse(tc_ctx *ctx, const uint32_t *ph_src, const uint32_t *ph_len, uint64_t nph, uint8_t *text, uint64_t *nbytes);
 int tc_lz_unparse_dev(tc_ctx *ctx, const uint32_t *d_ph_src, const uint32_t *d_ph_len, uint64_t nph, uint8_t *d_text,
                       uint64_t *nbytes);
+/* ---- the maximal and supermaximal repeats of a text (not part of the reference's surface) ----
+ * N = n + 1 rows; sa and lcp as tc_lcp_array defines them (row 0 is the empty suffix, the end of the text matches
+ * nothing).  left(r) = text[sa[r] - 1], and Nothing -- which differs from every byte -- for the one row with sa[r] = 0.
+ * A REPEAT is a string of length l >= 1 that occurs at least twice; occurrences may overlap.  It is MAXIMAL if extending
+ * all its occurrences by one byte to the right does not keep them all equal (the end of the text counts as a byte that
+ * differs from everything), and the same to the left (the start of the text).  In rows: an LCP interval [lb, rb], lb < rb,
+ * l = min lcp[lb+1 .. rb] >= 1, lcp[lb] < l, rb = N - 1 or lcp[rb+1] < l, whose left(lb .. rb) are not all equal.  It is
+ * SUPERMAXIMAL if it is a substring of no other maximal repeat: lcp[k] = l for every k in lb+1 .. rb and left(lb .. rb)
+ * pairwise distinct, so it occurs at most 257 times.  "mississippi": maximal i x4, issi x2, p x2, s x4; supermaximal issi, p.
+ * OUTPUT, per repeat: rep_row = lb, rep_pos = sa[lb] (0-based: the occurrence whose suffix sorts first), rep_len = l,
+ * rep_occ = rb - lb + 1; all occurrences of repeat k are sa[rep_row[k] .. rep_row[k] + rep_occ[k]).  sa (n + 1 entries)
+ * and rep_row may each be NULL.  ORDER: every interval is reported once, from its representative row j = the smallest
+ * row in (lb, rb] with lcp[j] = l, in increasing j.  That is deterministic and, for equal lb, decreasing len; it is NOT
+ * sorted by lb.  "aaabaab" has sa = 7 0 4 1 5 2 6 3 and lcp = 0 0 2 3 1 2 0 1; its maximal repeats are the three
+ * intervals [1, 3] of "aa" (j = 2), [2, 3] of "aab" (j = 3) and [1, 5] of "a" (j = 4), so rep_row = 1, 2, 1,
+ * rep_len = 2, 3, 1, rep_occ = 3, 2, 5 and rep_pos = 0, 4, 0.
+ * FILTERS: only repeats with len >= min_len and occ >= min_occ are reported.  min_len = 0, min_occ < 2 or a kind other
+ * than the two: TC_ERR_ARG.
+ * *nrep: in = capacity of the four arrays, out = the count.  Too small: TC_ERR_CAPACITY, *nrep = the needed count, nothing
+ * written to the four arrays (sa, when given, may already be written).  rep_pos = rep_len = rep_occ = NULL with
+ * capacity 0 is the sizes-only form: TC_OK, the count written.  A text of n bytes has fewer than n maximal repeats, so
+ * capacity n is always enough.
+ * ERRORS AND EDGES.  Null buffers or n > TC_MAX_N: TC_ERR_ARG.  n = 0: TC_OK, 0 repeats, nothing read; sa, when given,
+ * receives its one entry 0.  The calls take the text only: the suffix array, the LCP array, the last column and all
+ * scratch (25 bytes per text byte behind the sort: sa 4, lcp 4, last column 1, the packed rows 8, the left-context change
+ * counts 8; the sort's own need where that is larger) live in the calling ctx's workspace.  The _dev form takes every
+ * array in HBM; nrep stays a host word. */
+#define TC_REPEAT_MAXIMAL 0
+#define TC_REPEAT_SUPERMAXIMAL 1
+int tc_repeats(tc_ctx *ctx, const uint8_t *text, uint64_t n, int kind, uint32_t min_len, uint32_t min_occ,
+               uint32_t *sa, uint32_t *rep_pos, uint32_t *rep_len, uint32_t *rep_occ, uint32_t *rep_row, uint64_t *nrep);
+int tc_repeats_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, int kind, uint32_t min_len, uint32_t min_occ,
+                   uint32_t *d_sa, uint32_t *d_rep_pos, uint32_t *d_rep_len, uint32_t *d_rep_occ, uint32_t *d_rep_row, uint64_t *nrep);
 
 /* bytestringFromWord8BWT (BWT.hs:108-110) = fromBWT (:93-104) + sortTB
  * (BWT/Internal.hs:144-149) + magicInverseBWT (:163-200), for a well-formed BWT

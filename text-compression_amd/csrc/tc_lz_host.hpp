@@ -38,8 +38,10 @@ struct LzWork {
     }
 };
 
-// the min tree over src[0 .. N) into lmin, one small kernel per level, each over the one below
-static void lz_build_tree(tc_ctx *ctx, const LzWork &W, const u32 *src, u32 *lmin) {
+// the min tree over src[0 .. N) into lmin, one small kernel per level, each over the one below (Work: LzWork, or the
+// RepWork of tc_rep_host.hpp -- what holds lf and the tree's shape)
+template <class Work>
+static void lz_build_tree(tc_ctx *ctx, const Work &W, const u32 *src, u32 *lmin) {
     for (u32 k = 1; k <= W.tree_levels; k++) {
         u32 *dst = lmin + W.tree_off[k];
         fm_lmin_kernel<<<tc_cdiv(((u64)W.tree_cnt[k] + 3) & ~(u64)3, 256), 256, 0, ctx->stream>>>(src, W.tree_cnt[k - 1], W.lf, dst,

@@ -8,6 +8,7 @@
 #include "tc_fm_host.hpp"
 #include "tc_lcp_host.hpp"
 #include "tc_lz_host.hpp"
+#include "tc_rep_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -208,6 +209,21 @@ int tc_lz_unparse_dev(tc_ctx *ctx, const uint32_t *d_ph_src, const uint32_t *d_p
                       uint64_t *nbytes) {
     TC_API_BEGIN(ctx)
     lz_unparse_entry(ctx, d_ph_src, d_ph_len, nph, d_text, nbytes, true);
+    TC_API_END(ctx)
+}
+
+// the maximal and supermaximal repeats of a text (no counterpart in the reference): tc_rep_host.hpp
+int tc_repeats(tc_ctx *ctx, const uint8_t *text, uint64_t n, int kind, uint32_t min_len, uint32_t min_occ, uint32_t *sa,
+               uint32_t *rep_pos, uint32_t *rep_len, uint32_t *rep_occ, uint32_t *rep_row, uint64_t *nrep) {
+    TC_API_BEGIN(ctx)
+    repeats_entry(ctx, text, n, kind, min_len, min_occ, sa, rep_pos, rep_len, rep_occ, rep_row, nrep, false);
+    TC_API_END(ctx)
+}
+
+int tc_repeats_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, int kind, uint32_t min_len, uint32_t min_occ, uint32_t *d_sa,
+                   uint32_t *d_rep_pos, uint32_t *d_rep_len, uint32_t *d_rep_occ, uint32_t *d_rep_row, uint64_t *nrep) {
+    TC_API_BEGIN(ctx)
+    repeats_entry(ctx, d_text, n, kind, min_len, min_occ, d_sa, d_rep_pos, d_rep_len, d_rep_occ, d_rep_row, nrep, true);
     TC_API_END(ctx)
 }
 

@@ -1,0 +1,212 @@
+// Stand-alone host check of the repeats kernel (csrc/tc_rep.hpp), meant to be built with a host sanitizer:
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I text-compression_amd/csrc
+//       text-compression_amd/host/check/rep_kernels.cpp -o rep_kernels && ./rep_kernels
+// TC_FM_MS_HOST_CHECK compiles rep_row_kernel and the two row searches of csrc/tc_fm_ms.hpp it calls as plain C++, as
+// host/check/lz_kernels.cpp does for the LPF kernel: the HIP keywords defined away, a workgroup of one lane, the lanes of a
+// grid run one after another.  Everything is built naively here -- suffixes sorted directly, the LCP array by comparing
+// neighbours, the last column from the text, the change counts by a running sum, the min tree by fm_lmin_kernel level over
+// level at fan-outs 4 and 64 -- in heap blocks of exactly the rows the library's arrays hold, so a read one element outside
+// any of them stops the run.  Every row's packed word, for both kinds and several filters, is compared with what one stack
+// walk over the LCP array says: the walk closes every LCP interval, the left contexts are compared directly, and the
+// interval is booked at its representative row.  Texts: unary, periodic (2, 3, 7), Fibonacci, random over 1, 2, 4 and 256
+// letters, a text followed by its copy, lengths 1 .. 2200, and the two 257-occurrence texts of the device tests.  The
+// flag, count and fill kernels need a workgroup scan or a device scan: they are checked on the device only.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <random>
+#include <string>
+#include <vector>
+
+#define TC_FM_MS_HOST_CHECK
+#include "tc_rep.hpp"
+
+#define EXPECT(cond)                                                              \
+    do {                                                                          \
+        if (!(cond)) {                                                            \
+            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
+            std::exit(1);                                                         \
+        }                                                                         \
+    } while (0)
+
+template <class F>
+static void launch(u64 grid, F &&kernel) {
+    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
+}
+template <class T>
+static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
+
+typedef std::vector<u8> Bytes;
+
+// ---- the enhanced suffix array of a text, naively, in blocks of the library's sizes --------------------------------------
+struct Esa {
+    u32 n = 0, N = 0, primary = 0;
+    std::vector<u32> sa;
+    std::vector<int> left;                      // -1: Nothing
+    std::unique_ptr<u32[]> lcp;
+    std::unique_ptr<u8[]> L;
+    std::unique_ptr<u64[]> chg;
+};
+static void build_esa(Esa &e, const Bytes &text) {
+    const u32 n = e.n = (u32)text.size(), N = e.N = n + 1;
+    e.sa.resize(N);
+    for (u32 i = 0; i < N; i++) e.sa[i] = i;
+    std::sort(e.sa.begin(), e.sa.end(), [&](u32 x, u32 y) {     // the empty suffix first: a proper prefix sorts first
+        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
+        return c ? c < 0 : x > y;
+    });
+    e.lcp = block<u32>(N);
+    e.L = block<u8>(N);
+    e.chg = block<u64>(N);
+    e.left.assign(N, -1);
+    for (u32 j = 0; j < N; j++) {
+        u32 l = 0;
+        if (j) {
+            const u32 a = e.sa[j - 1], b = e.sa[j];
+            while (a + l < n && b + l < n && text[a + l] == text[b + l]) l++;
+        }
+        e.lcp[j] = l;
+        if (e.sa[j] == 0) e.primary = j;
+        e.left[j] = e.sa[j] ? (int)text[e.sa[j] - 1] : -1;
+        e.L[j] = e.sa[j] ? text[e.sa[j] - 1] : (u8)0;             // the sentinel slot holds byte 0, as sa_build writes it
+        e.chg[j] = j ? e.chg[j - 1] + (e.left[j] != e.left[j - 1] ? 1u : 0u) : 0u;
+    }
+}
+
+// ---- what the stack walk says: want[j] = occ << 32 | lb where row j represents a reported interval ------------------------
+static std::vector<u64> by_stack_walk(const Esa &e, bool super, u32 min_len, u32 min_occ) {
+    std::vector<u64> want(e.N, 0);
+    struct Open { u32 l, lb; };
+    std::vector<Open> stack{{0, 0}};
+    auto close = [&](u32 l, u32 lb, u32 rb) {
+        const u32 occ = rb - lb + 1;
+        if (l < min_len || occ < min_occ) return;
+        bool flat = true, differ = false, twice = false, seen[257] = {};
+        for (u32 k = lb; k <= rb; k++) {
+            if (k > lb && e.lcp[k] != l) flat = false;
+            if (e.left[k] != e.left[lb]) differ = true;
+            if (seen[e.left[k] + 1]) twice = true;
+            seen[e.left[k] + 1] = true;
+        }
+        if (super ? !(flat && !twice) : !differ) return;
+        u32 j = lb + 1;
+        while (e.lcp[j] != l) j++;
+        EXPECT(j <= rb && want[j] == 0);
+        want[j] = (u64)occ << 32 | lb;
+    };
+    for (u32 r = 1; r <= e.N; r++) {
+        const u32 v = r < e.N ? e.lcp[r] : 0;
+        u32 lb = r - 1;
+        while (stack.back().l > v) {
+            const Open o = stack.back();
+            stack.pop_back();
+            lb = o.lb;
+            close(o.l, o.lb, r - 1);
+        }
+        if (stack.back().l < v) stack.push_back({v, lb});
+    }
+    return want;
+}
+
+static u64 g_texts = 0, g_rows = 0, g_repeats = 0, g_super = 0;
+static void check_text(const Bytes &text, u32 lf) {
+    Esa e;
+    build_esa(e, text);
+    const u32 N = e.N;
+    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1], words;
+    const u32 nlev = fm_ms_tree_shape(N, lf, off, cnt, &words);
+    auto lmin = block<u32>(words);
+    const u32 *src = e.lcp.get();
+    for (u32 k = 1; k <= nlev; k++) {
+        u32 *dst = lmin.get() + off[k];
+        launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], lf, dst, cnt[k]); });
+        src = dst;
+    }
+    auto pack = block<u64>(N);
+    const u32 filters[][2] = {{1, 2}, {2, 2}, {1, 3}, {3, 4}, {20, 2}, {1, 257}, {1, 258}};
+    for (int super = 0; super < 2; super++)
+        for (const auto &f : filters) {
+            for (u32 j = 0; j < N; j++) pack[j] = ~0ull;
+            if (super)
+                launch(N, [&] { rep_row_kernel<true>(e.lcp.get(), lmin.get(), N, lf, e.chg.get(), e.L.get(), e.primary, f[0], f[1], pack.get()); });
+            else
+                launch(N, [&] { rep_row_kernel<false>(e.lcp.get(), lmin.get(), N, lf, e.chg.get(), e.L.get(), e.primary, f[0], f[1], pack.get()); });
+            const std::vector<u64> want = by_stack_walk(e, super != 0, f[0], f[1]);
+            u64 found = 0;
+            for (u32 j = 0; j < N; j++) {
+                EXPECT(pack[j] == want[j]);
+                found += want[j] ? 1 : 0;
+            }
+            EXPECT(found < std::max(e.n, 1u));      // fewer than n maximal repeats
+            (super ? g_super : g_repeats) += found;
+            g_rows += N;
+        }
+    g_texts++;
+}
+
+static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
+    Bytes t(n);
+    for (u8 &b : t) b = sigma == 256 ? (u8)rng() : (u8)("ACGT"[rng() % sigma]);
+    return t;
+}
+static Bytes periodic(u32 n, u32 p) {
+    Bytes t(n);
+    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
+    return t;
+}
+static Bytes fibonacci(u32 n) {
+    std::string a = "A", b = "AB";
+    while (b.size() < n) {
+        const std::string c = b + a;
+        a = b;
+        b = c;
+    }
+    return Bytes(b.begin(), b.begin() + n);
+}
+// w = 01 02 03, then (c, w) for c = 0 .. 255: 257 occurrences of w, every left context another one (Nothing among them).
+// doubled >= 0: the byte in front of the last w is `doubled`, so one left context occurs twice.
+static Bytes many_left(int doubled) {
+    const Bytes w{1, 2, 3};
+    Bytes t = w;
+    for (int c = 0; c < 256; c++) {
+        t.push_back((u8)(c == 255 && doubled >= 0 ? doubled : c));
+        t.insert(t.end(), w.begin(), w.end());
+    }
+    return t;
+}
+// the packed word of the interval of w = 01 02 03 under the supermaximal kind (0: not reported)
+static u64 super_word_of_w(const Bytes &text, u32 lf) {
+    Esa e;
+    build_esa(e, text);
+    const std::vector<u64> want = by_stack_walk(e, true, 1, 2);
+    check_text(text, lf);
+    for (u32 j = 1; j < e.N; j++)
+        if (want[j] && e.lcp[j] == 3 && text[e.sa[j]] == 1) return want[j];
+    return 0;
+}
+
+int main() {
+    std::mt19937 rng(0x7e9);
+    for (u32 lf : {2u, 6u}) {
+        for (u32 n : {1u, 2u, 3u, 8u, 63u, 64u, 65u, 257u, 258u, 300u, 1100u, 2200u}) {
+            check_text(Bytes(n, 'A'), lf);
+            for (u32 p : {2u, 3u, 7u}) check_text(periodic(n, p), lf);
+            check_text(fibonacci(n), lf);
+            for (u32 sigma : {1u, 2u, 4u, 256u}) check_text(random_text(rng, n, sigma), lf);
+            if (n > 1100) continue;
+            Bytes twice = random_text(rng, n, 4);   // a text followed by its own copy; a text whose last byte is new
+            twice.insert(twice.end(), twice.begin(), twice.end());
+            check_text(twice, lf);
+            twice.back() = 'Z';
+            check_text(twice, lf);
+        }
+        EXPECT(super_word_of_w(many_left(-1), lf) >> 32 == 257);    // the most the bitmap can see
+        EXPECT(super_word_of_w(many_left(7), lf) == 0);
+    }
+    EXPECT(g_repeats > 0 && g_super > 0);
+    std::printf("ok: the repeats of %llu texts, %llu rows: %llu maximal, %llu supermaximal\n", (unsigned long long)g_texts,
+                (unsigned long long)g_rows, (unsigned long long)g_repeats, (unsigned long long)g_super);
+    return 0;
+}

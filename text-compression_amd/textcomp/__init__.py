@@ -318,6 +318,60 @@ class Context:
         self._check(rc)
         return out[:int(nb.value)]
 
+    # ------------------------------------- maximal and supermaximal repeats of a text
+    def repeat_count(self, text, min_len=1, min_occ=2, supermaximal=False):
+        """the number of (super)maximal repeats of text with len >= min_len and occ >= min_occ (the sizes-only form of
+        tc_repeats)"""
+        t = _u8(text)
+        nrep = C.c_uint64(0)
+        self._check(self._lib.tc_repeats(self._h, _ptr(t) if len(t) else None, len(t), int(bool(supermaximal)), min_len, min_occ,
+                                         None, None, None, None, None, C.byref(nrep)))
+        return int(nrep.value)
+
+    def repeats(self, text, min_len=1, min_occ=2, supermaximal=False, with_sa=False):
+        """the maximal (or supermaximal) repeats of text -> (pos, len, occ, row[, sa]), uint32 arrays: repeat k is
+        text[pos[k] : pos[k] + len[k]], it occurs occ[k] times, at sa[row[k] : row[k] + occ[k]]; listed by representative
+        row (include/textcomp.h), which is not the order of row: tc_repeats"""
+        t = _u8(text)
+        kind = int(bool(supermaximal))
+        cap = max(self.repeat_count(t, min_len, min_occ, supermaximal), 1)
+        pos, ln, occ, row = (np.empty(cap, np.uint32) for _ in range(4))
+        sa = np.empty(len(t) + 1, np.uint32) if with_sa else None
+        nrep = C.c_uint64(cap)
+        self._check(self._lib.tc_repeats(self._h, _ptr(t) if len(t) else None, len(t), kind, min_len, min_occ,
+                                         _ptr(sa) if with_sa else None, _ptr(pos), _ptr(ln), _ptr(occ), _ptr(row), C.byref(nrep)))
+        k = int(nrep.value)
+        out = (pos[:k].copy(), ln[:k].copy(), occ[:k].copy(), row[:k].copy())
+        return out + (sa,) if with_sa else out
+
+    def repeats_dev(self, d_text, min_len=1, min_occ=2, supermaximal=False, with_sa=False, cap=None):
+        """text resident in HBM -> (pos, len, occ, row[, sa]), int32 tensors on the device: tc_repeats_dev.  cap: the
+        repeat slots to try first (None: the sizes-only form runs first)"""
+        import torch
+        n = d_text.numel()
+        kind = int(bool(supermaximal))
+        pt = C.c_void_p(d_text.data_ptr()) if n else None
+        d_sa = torch.empty(n + 1, dtype=torch.int32, device=d_text.device) if with_sa else None
+        psa = C.c_void_p(d_sa.data_ptr()) if with_sa else None
+        torch.cuda.synchronize()
+        if cap is None:
+            nrep = C.c_uint64(0)
+            self._check(self._lib.tc_repeats_dev(self._h, pt, n, kind, min_len, min_occ, None, None, None, None, None, C.byref(nrep)))
+            cap = int(nrep.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            out = [torch.empty(cap, dtype=torch.int32, device=d_text.device) for _ in range(4)]
+            torch.cuda.synchronize()
+            nrep = C.c_uint64(cap)
+            rc = self._lib.tc_repeats_dev(self._h, pt, n, kind, min_len, min_occ, psa, *(C.c_void_p(o.data_ptr()) for o in out),
+                                          C.byref(nrep))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nrep.value), 1)
+        self._check(rc)
+        res = tuple(o[:int(nrep.value)] for o in out)
+        return res + (d_sa,) if with_sa else res
+
     def bwt_decode(self, L, primary):
         L = _u8(L)
         N = len(L)

@@ -17,6 +17,7 @@ TC_CODING_PACKED, TC_CODING_HUFFMAN = 0, 1
 TC_FM_MAX_SA_RATE = 4096
 TC_FM_MAX_MISMATCH = 3
 TC_MAX_N = 0x7ffffff0
+TC_REPEAT_MAXIMAL, TC_REPEAT_SUPERMAXIMAL = 0, 1
 TC_LCP_SHORT_CAP = 256   # csrc/tc_lcp.hpp: comparisons of the LCP array longer than this leave the one-lane kernel
 
 ERR_NAMES = {-1: "TC_ERR_ARG", -2: "TC_ERR_CAPACITY", -3: "TC_ERR_MALFORMED", -4: "TC_ERR_HIP",
@@ -81,6 +82,8 @@ SYMBOLS = [
     ("tc_lz_parse_dev", _INT, [_P, _P, _U64, _P, _P, _PU64]),
     ("tc_lz_unparse", _INT, [_P, _P, _P, _U64, _P, _PU64]),
     ("tc_lz_unparse_dev", _INT, [_P, _P, _P, _U64, _P, _PU64]),
+    ("tc_repeats", _INT, [_P, _P, _U64, _INT, _U32, _U32, _P, _P, _P, _P, _P, _PU64]),
+    ("tc_repeats_dev", _INT, [_P, _P, _U64, _INT, _U32, _U32, _P, _P, _P, _P, _P, _PU64]),
     ("tc_bwt_decode", _INT, [_P, _P, _U64, _U64, _P]),
     ("tc_bwt_decode_sym", _INT, [_P, _P, _U64, _P, _PU64]),
     ("tc_mtf_encode", _INT, [_P, _P, _U64, _I64, _P, _P, _PU32]),
