@@ -236,6 +236,54 @@ int tc_repeats(tc_ctx *ctx, const uint8_t *text, uint64_t n, int kind, uint32_t 
                uint32_t *sa, uint32_t *rep_pos, uint32_t *rep_len, uint32_t *rep_occ, uint32_t *rep_row, uint64_t *nrep);
 int tc_repeats_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, int kind, uint32_t min_len, uint32_t min_occ,
                    uint32_t *d_sa, uint32_t *d_rep_pos, uint32_t *d_rep_len, uint32_t *d_rep_occ, uint32_t *d_rep_row, uint64_t *nrep);
+/* ---- the k-mers of a text: list, abundance spectrum and all-k profile (not part of the reference's surface) ----
+ * N = n + 1 rows; sa and lcp as tc_lcp_array defines them (row 0 is the empty suffix, the end of the text matches
+ * nothing); lcp[0] counts as 0 whatever the array holds, and lcp[N] as 0.  For k >= 1 row q is a BOUNDARY iff lcp[q] < k;
+ * row N is a boundary too.  A K-MER is the row interval [p, q) between two consecutive boundaries whose first row is long
+ * enough, sa[p] + k <= n (the rows p+1 .. q-1 have lcp >= k, so they are long enough as well; a suffix shorter than k is
+ * always a boundary and never a member).  kmer_occ = q - p, kmer_pos = sa[p] (0-based: the occurrence whose suffix sorts
+ * first), kmer_row = p; all occurrences are sa[row .. row + occ).  ORDER: increasing row, the lexicographic order of the
+ * k-mers; every k-mer appears once.  FILTERS: min_occ <= occ, and occ <= max_occ unless max_occ = 0 (no upper bound):
+ * (1, 0) lists all k-mers, (1, 1) the unique ones, (2, 0) the repeated ones.  Over all k-mers the occ sum to
+ * max(0, n - k + 1); k > n: no k-mers.  k = 0, min_occ = 0, or max_occ non-zero and below min_occ: TC_ERR_ARG.
+ *   "mississippi", k = 2: sa = 11 10 7 4 1 0 9 8 6 3 5 2, lcp = 0 0 1 1 4 0 0 1 0 2 1 3, and (row, pos, occ) =
+ *       (2,7,1) (3,4,2) (5,0,1) (6,9,1) (7,8,1) (8,6,2) (10,5,2): ip, is x2, mi, pi, pp, si x2, ss x2
+ *   "aaabaab": sa = 7 0 4 1 5 2 6 3, lcp = 0 0 2 3 1 2 0 1; k = 2: (1,0,3) (4,5,2) (7,3,1); k = 1: (1,0,5) (6,6,2)
+ *   "aaaaaa", k = 2: (2,4,5)
+ * *nk: in = capacity of the three arrays, out = the count.  Too small: TC_ERR_CAPACITY, *nk = the needed count, nothing
+ * written to the three arrays.  kmer_pos = kmer_occ = NULL with capacity 0 is the sizes-only form: TC_OK, the count
+ * written.  Capacity n is always enough.  sa (n + 1 entries) and kmer_row may each be NULL.
+ * THE SPECTRUM, for bins in 1 .. 65536 (anything else: TC_ERR_ARG): hist[i] for i < bins - 1 = the number of distinct
+ * k-mers with occ = i + 1, hist[bins - 1] = the number with occ >= bins; *distinct = the sum of hist,
+ * *total = max(0, n - k + 1).  No filters.  d_hist (bins words, in HBM) is zeroed by the call.
+ * THE PROFILE, for kmax in 1 .. 4096 (anything else: TC_ERR_ARG) and every k = 1 .. kmax: distinct[k-1] = the number of
+ * distinct k-mers = max(0, n-k+1) - #{r : lcp[r] >= k}, unique[k-1] = the number of k-mers with occ = 1 =
+ * #{r in 1 .. n : max(lcp[r], lcp[r+1]) < k} - min(k-1, n).  unique may be NULL.  Both are HOST arrays in every form, as
+ * *nk, *distinct and *total are host words.
+ * ERRORS AND EDGES.  Null buffers, n > TC_MAX_N, N = 0 or N - 1 > TC_MAX_N: TC_ERR_ARG.  n = 0: TC_OK, 0 k-mers, all-zero
+ * hist and profile; sa, when given, receives its one entry 0.
+ * The text forms build the enhanced suffix array in the calling ctx's workspace (8 bytes per text byte behind the sort:
+ * sa 4, lcp 4; the sort's own need where that is larger; tc_kmers_dev sorts straight into a d_sa the caller gives) and then
+ * do what the _esa_dev forms do.  THE _esa_dev FORMS take arrays the caller kept from tc_suffix_array_dev and
+ * tc_lcp_array_dev -- the sort is paid once for any number of k.  They stay in bounds on ANY contents: boundaries come from
+ * the d_lcp values alone, d_sa values are copied and compared (in 64 bits) and never used as an index; arrays that are not
+ * an enhanced suffix array give values without meaning, and no error.  The profile never reads sa.
+ * Scratch behind the arrays, from the calling ctx's workspace: 8 bytes per tile of 4096 rows (the tiles' last boundaries
+ * and carries), 16 per tile and the scan's sums for the list, 2 (kmax + 1) words for the profile.  Nothing per row.
+ * Cost: the list is two passes over lcp (count, fill) behind one for the tiles' boundaries, one read of sa per group and
+ * the stores; the spectrum two passes over lcp and one read of sa per group; the profile one pass over lcp. */
+int tc_kmers(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t k, uint32_t min_occ, uint32_t max_occ, uint32_t *sa,
+             uint32_t *kmer_pos, uint32_t *kmer_occ, uint32_t *kmer_row, uint64_t *nk);
+int tc_kmers_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t k, uint32_t min_occ, uint32_t max_occ, uint32_t *d_sa,
+                 uint32_t *d_kmer_pos, uint32_t *d_kmer_occ, uint32_t *d_kmer_row, uint64_t *nk);
+int tc_kmers_esa_dev(tc_ctx *ctx, const uint32_t *d_sa, const uint32_t *d_lcp, uint64_t N, uint32_t k, uint32_t min_occ,
+                     uint32_t max_occ, uint32_t *d_kmer_pos, uint32_t *d_kmer_occ, uint32_t *d_kmer_row, uint64_t *nk);
+int tc_kmer_spectrum(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t k, uint32_t bins, uint64_t *hist, uint64_t *distinct,
+                     uint64_t *total);
+int tc_kmer_spectrum_esa_dev(tc_ctx *ctx, const uint32_t *d_sa, const uint32_t *d_lcp, uint64_t N, uint32_t k, uint32_t bins,
+                             uint64_t *d_hist, uint64_t *distinct, uint64_t *total);
+int tc_kmer_profile(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t kmax, uint64_t *distinct, uint64_t *unique);
+int tc_kmer_profile_esa_dev(tc_ctx *ctx, const uint32_t *d_lcp, uint64_t N, uint32_t kmax, uint64_t *distinct, uint64_t *unique);
 
 /* bytestringFromWord8BWT (BWT.hs:108-110) = fromBWT (:93-104) + sortTB
  * (BWT/Internal.hs:144-149) + magicInverseBWT (:163-200), for a well-formed BWT

@@ -9,6 +9,7 @@
 #include "tc_lcp_host.hpp"
 #include "tc_lz_host.hpp"
 #include "tc_rep_host.hpp"
+#include "tc_kmer_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -224,6 +225,54 @@ int tc_repeats_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, int kind, uin
                    uint32_t *d_rep_pos, uint32_t *d_rep_len, uint32_t *d_rep_occ, uint32_t *d_rep_row, uint64_t *nrep) {
     TC_API_BEGIN(ctx)
     repeats_entry(ctx, d_text, n, kind, min_len, min_occ, d_sa, d_rep_pos, d_rep_len, d_rep_occ, d_rep_row, nrep, true);
+    TC_API_END(ctx)
+}
+
+// the k-mers of a text, their abundance spectrum and the all-k profile (no counterpart in the reference): tc_kmer_host.hpp
+int tc_kmers(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t k, uint32_t min_occ, uint32_t max_occ, uint32_t *sa,
+             uint32_t *kmer_pos, uint32_t *kmer_occ, uint32_t *kmer_row, uint64_t *nk) {
+    TC_API_BEGIN(ctx)
+    kmers_entry(ctx, text, n, k, min_occ, max_occ, sa, kmer_pos, kmer_occ, kmer_row, nk, false);
+    TC_API_END(ctx)
+}
+
+int tc_kmers_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t k, uint32_t min_occ, uint32_t max_occ, uint32_t *d_sa,
+                 uint32_t *d_kmer_pos, uint32_t *d_kmer_occ, uint32_t *d_kmer_row, uint64_t *nk) {
+    TC_API_BEGIN(ctx)
+    kmers_entry(ctx, d_text, n, k, min_occ, max_occ, d_sa, d_kmer_pos, d_kmer_occ, d_kmer_row, nk, true);
+    TC_API_END(ctx)
+}
+
+int tc_kmers_esa_dev(tc_ctx *ctx, const uint32_t *d_sa, const uint32_t *d_lcp, uint64_t N, uint32_t k, uint32_t min_occ,
+                     uint32_t max_occ, uint32_t *d_kmer_pos, uint32_t *d_kmer_occ, uint32_t *d_kmer_row, uint64_t *nk) {
+    TC_API_BEGIN(ctx)
+    kmers_esa_entry(ctx, d_sa, d_lcp, N, k, min_occ, max_occ, d_kmer_pos, d_kmer_occ, d_kmer_row, nk);
+    TC_API_END(ctx)
+}
+
+int tc_kmer_spectrum(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t k, uint32_t bins, uint64_t *hist, uint64_t *distinct,
+                     uint64_t *total) {
+    TC_API_BEGIN(ctx)
+    kmer_spectrum_entry(ctx, text, n, k, bins, hist, distinct, total);
+    TC_API_END(ctx)
+}
+
+int tc_kmer_spectrum_esa_dev(tc_ctx *ctx, const uint32_t *d_sa, const uint32_t *d_lcp, uint64_t N, uint32_t k, uint32_t bins,
+                             uint64_t *d_hist, uint64_t *distinct, uint64_t *total) {
+    TC_API_BEGIN(ctx)
+    kmer_spectrum_esa_entry(ctx, d_sa, d_lcp, N, k, bins, d_hist, distinct, total);
+    TC_API_END(ctx)
+}
+
+int tc_kmer_profile(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t kmax, uint64_t *distinct, uint64_t *unique) {
+    TC_API_BEGIN(ctx)
+    kmer_profile_entry(ctx, text, n, kmax, distinct, unique);
+    TC_API_END(ctx)
+}
+
+int tc_kmer_profile_esa_dev(tc_ctx *ctx, const uint32_t *d_lcp, uint64_t N, uint32_t kmax, uint64_t *distinct, uint64_t *unique) {
+    TC_API_BEGIN(ctx)
+    kmer_profile_esa_entry(ctx, d_lcp, N, kmax, distinct, unique);
     TC_API_END(ctx)
 }
 

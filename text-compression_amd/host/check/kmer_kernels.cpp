@@ -1,0 +1,214 @@
+// Stand-alone host check of the k-mer kernels' per-lane bodies (csrc/tc_kmer.hpp), meant to be built with a host sanitizer:
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I text-compression_amd/csrc
+//       text-compression_amd/host/check/kmer_kernels.cpp -o kmer_kernels && ./kmer_kernels
+// TC_KM_HOST_CHECK compiles km_mask16, km_last1, km_close, km_lane_close, km_spectrum_bin and km_profile_bins as plain C++.
+// This program plays the kernels around them one lane after another: a lane's 16 lcp words are read from a heap block of
+// exactly N entries (never past it, as km_load16 guards), the workgroup's exclusive max scan and the tiles' carries are
+// running maxima over the lanes and tiles in order, and every group a lane closes reads sa[p] from a heap block of exactly
+// N entries -- so a read one element outside either array stops the run.  The list (several filters), the spectrum bins
+// and the profile's two histograms are compared with one naive scan over the rows.  Texts: unary, period 2, 3 and 7,
+// Fibonacci, random over 1, 2, 4 and 256 letters, lengths 1 .. 2200 (with KM_TILE = 4096 that is one tile; the carries are
+// also exercised by a smaller play tile, since nothing in the lane bodies depends on the tile size).  Then arrays no text
+// has: random lcp and sa words, values above n among them, lcp[0] != 0.
+// NOT covered here, checked on the device only: km_load16's vector loads, km_block_excl_max and block_excl_sum (the
+// workgroup scans), km_tile_kernel's and km_carry_kernel's reductions, tc_scan64, the LDS and global atomics of the
+// spectrum and the profile, the ballot of the saturated bin.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <random>
+#include <string>
+#include <vector>
+
+#define TC_KM_HOST_CHECK
+#include "tc_kmer.hpp"
+
+#define EXPECT(cond)                                                              \
+    do {                                                                          \
+        if (!(cond)) {                                                            \
+            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
+            std::exit(1);                                                         \
+        }                                                                         \
+    } while (0)
+
+template <class T>
+static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
+typedef std::vector<u8> Bytes;
+struct Kmer {
+    u32 row, pos, occ;
+    bool operator==(const Kmer &o) const { return row == o.row && pos == o.pos && occ == o.occ; }
+};
+
+// ---- the naive scan: the definition, row by row ---------------------------------------------------------------------------
+static std::vector<Kmer> naive_list(const u32 *sa, const u32 *lcp, u64 N, u32 k, u32 min_occ, u32 max_occ) {
+    const u64 n = N - 1;
+    std::vector<Kmer> out;
+    u64 p = 0;
+    for (u64 q = 1; q <= N; q++) {
+        if (q < N && lcp[q] >= k) continue;
+        const u64 occ = q - p;
+        if ((u64)sa[p] + k <= n && occ >= min_occ && (max_occ == 0 || occ <= max_occ)) out.push_back(Kmer{(u32)p, sa[p], (u32)occ});
+        p = q;
+    }
+    return out;
+}
+
+// ---- the kernels' structure, one lane after another; `lanes` lanes of 16 rows make a play tile ----------------------------
+static void lane_words(const u32 *lcp, u64 base, u64 N, u32 *w) {
+    for (u32 i = 0; i < KM_ROWS; i++) w[i] = base + i < N ? lcp[base + i] : 0u;
+}
+static std::vector<Kmer> played_list(const u32 *sa, const u32 *lcp, u64 N, u32 k, u32 min_occ, u32 max_occ, u32 lanes) {
+    const u64 tile = (u64)lanes * KM_ROWS, ntiles = N / tile + 1;
+    std::vector<u32> last(ntiles, 0), carry(ntiles, 0);
+    u32 w[KM_ROWS];
+    for (u64 t = 0; t < ntiles; t++)                    // km_tile_kernel
+        for (u32 l = 0; l < lanes; l++) {
+            const u64 base = t * tile + (u64)l * KM_ROWS;
+            lane_words(lcp, base, N, w);
+            last[t] = std::max(last[t], km_last1(km_mask16(w, base, N, k), base));
+        }
+    u32 run = 0;
+    for (u64 t = 0; t < ntiles; t++) {                  // km_carry_kernel
+        carry[t] = run;
+        run = std::max(run, last[t]);
+    }
+    std::vector<Kmer> out;
+    for (u64 t = 0; t < ntiles; t++) {                  // km_pass_kernel
+        u32 before = 0;                                 // the exclusive max scan over the tile's lanes
+        for (u32 l = 0; l < lanes; l++) {
+            const u64 base = t * tile + (u64)l * KM_ROWS;
+            lane_words(lcp, base, N, w);
+            const u32 mask = km_mask16(w, base, N, k);
+            const u32 prev1 = std::max(before, carry[t]);
+            const size_t at = out.size();
+            const u32 c = km_lane_close(mask, base, prev1, sa, N - 1, k, min_occ, max_occ, [&](u32 j, u32 row, u32 pos, u32 occ) {
+                EXPECT(out.size() == at + j);
+                out.push_back(Kmer{row, pos, occ});
+            });
+            EXPECT(out.size() == at + c);
+            before = std::max(before, km_last1(mask, base));
+        }
+    }
+    return out;
+}
+
+static u64 checked_lists = 0, checked_profiles = 0;
+static void check_arrays(const u32 *sa, const u32 *lcp, u64 N, const std::vector<u32> &ks) {
+    static const u32 filters[][2] = {{1, 0}, {1, 1}, {2, 0}, {3, 5}, {7, 7}};
+    for (u32 k : ks) {
+        for (auto &f : filters) {
+            const std::vector<Kmer> want = naive_list(sa, lcp, N, k, f[0], f[1]);
+            for (u32 lanes : {1u, 3u, (u32)KM_NT}) EXPECT(played_list(sa, lcp, N, k, f[0], f[1], lanes) == want);
+            checked_lists++;
+        }
+        // the spectrum's bins: min(occ, bins) - 1, below bins
+        for (const Kmer &m : naive_list(sa, lcp, N, k, 1, 0))
+            for (u32 bins : {1u, 2u, 256u, 65536u}) {
+                const u32 b = km_spectrum_bin(m.occ, bins);
+                EXPECT(b < bins && (m.occ >= bins ? b == bins - 1 : b == m.occ - 1));
+            }
+    }
+    // the profile's two bins against the formulas' two counts
+    for (u32 kmax : {1u, 7u, 64u, 4096u}) {
+        std::vector<u64> ha(kmax + 1, 0), hb(kmax + 1, 0);
+        for (u64 r = 0; r < N; r++) {
+            u32 a, b;
+            const bool hasb = km_profile_bins(r, N, lcp[r], r + 1 < N ? lcp[r + 1] : 0xdeadbeefu, kmax, &a, &b);
+            EXPECT(a <= kmax && b <= kmax);
+            ha[a]++;
+            if (hasb) hb[b]++;
+        }
+        for (u32 k = 1; k <= kmax; k += (kmax > 64 ? 97 : 1)) {
+            u64 ge = 0, lt = 0, ge_want = 0, lt_want = 0;
+            for (u32 i = k; i <= kmax; i++) ge += ha[i];
+            for (u32 i = 0; i < k; i++) lt += hb[i];
+            for (u64 r = 1; r < N; r++) {
+                const u32 l = lcp[r], ln = r + 1 < N ? lcp[r + 1] : 0u;
+                ge_want += l >= k;
+                lt_want += std::max(l, ln) < k;
+            }
+            EXPECT(ge == ge_want && lt == lt_want);
+        }
+        checked_profiles++;
+    }
+}
+
+// ---- the enhanced suffix array of a text, naively, in heap blocks of exactly N entries ------------------------------------
+static void check_text(const Bytes &text) {
+    const u32 n = (u32)text.size(), N = n + 1;
+    std::vector<u32> order(N);
+    for (u32 i = 0; i < N; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](u32 x, u32 y) {     // the empty suffix first: a proper prefix sorts first
+        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
+        return c ? c < 0 : x > y;
+    });
+    auto sa = block<u32>(N), lcp = block<u32>(N);
+    u32 maxl = 0;
+    for (u32 j = 0; j < N; j++) {
+        u32 l = 0;
+        if (j) {
+            const u32 a = order[j - 1], b = order[j];
+            while (a + l < n && b + l < n && text[a + l] == text[b + l]) l++;
+        }
+        sa[j] = order[j];
+        lcp[j] = l;
+        maxl = std::max(maxl, l);
+    }
+    std::vector<u32> ks = {1, 2, 3, 5, 12, n, n + 1, 0xffffffffu};
+    if (maxl) { ks.push_back(maxl); ks.push_back(maxl + 1); }
+    ks.erase(std::remove(ks.begin(), ks.end(), 0u), ks.end());
+    check_arrays(sa.get(), lcp.get(), N, ks);
+    // on a text the occurrence counts of all k-mers sum to max(0, n - k + 1)
+    for (u32 k : ks) {
+        u64 sum = 0;
+        for (const Kmer &m : naive_list(sa.get(), lcp.get(), N, k, 1, 0)) sum += m.occ;
+        EXPECT(sum == (n >= k ? (u64)n - k + 1 : 0));
+    }
+}
+
+static Bytes periodic(u32 n, u32 p) {
+    Bytes t(n);
+    for (u32 i = 0; i < n; i++) t[i] = (u8)('a' + i % p);
+    return t;
+}
+static Bytes fibonacci(u32 n) {
+    std::string x = "b", y = "a";
+    while (y.size() < n) { std::string z = y + x; x = y; y = z; }
+    return Bytes(y.begin(), y.begin() + n);
+}
+
+int main() {
+    std::mt19937_64 rng(0x6b6d6572);
+    const u32 lens[] = {1, 2, 3, 15, 16, 17, 31, 32, 33, 47, 48, 49, 255, 256, 257, 1000, 2199, 2200};
+    u64 texts = 0;
+    for (u32 n : lens) {
+        check_text(periodic(n, 1));
+        for (u32 p : {2u, 3u, 7u}) check_text(periodic(n, p));
+        check_text(fibonacci(n));
+        for (u32 sigma : {1u, 2u, 4u, 256u}) {
+            Bytes t(n);
+            for (u32 i = 0; i < n; i++) t[i] = (u8)(sigma == 256 ? rng() & 255 : 'a' + rng() % sigma);
+            check_text(t);
+        }
+        texts += 9;
+    }
+    // arrays no text has
+    u64 arrays = 0;
+    for (u32 N : {1u, 2u, 16u, 17u, 49u, 300u, 2201u}) {
+        for (u32 kind = 0; kind < 4; kind++) {
+            auto sa = block<u32>(N), lcp = block<u32>(N);
+            for (u32 j = 0; j < N; j++) {
+                sa[j] = kind == 0 ? (u32)(rng() % N) : kind == 1 ? (u32)rng() : kind == 2 ? 0xffffffffu : (u32)(rng() % (2 * N));
+                lcp[j] = kind == 0 ? (u32)(rng() % 4) : kind == 1 ? (u32)rng() : kind == 2 ? (u32)(rng() % 3) : 0xffffffffu;
+            }
+            if (kind != 0) lcp[0] = 5;                  // counts as 0
+            check_arrays(sa.get(), lcp.get(), N, {1, 2, 3, N, 0x80000000u, 0xffffffffu});
+            arrays++;
+        }
+    }
+    std::printf("ok: the k-mers of %llu texts and %llu arrays no text has (%llu lists, %llu profiles)\n", (unsigned long long)texts,
+                (unsigned long long)arrays, (unsigned long long)checked_lists, (unsigned long long)checked_profiles);
+    return 0;
+}

@@ -372,6 +372,118 @@ class Context:
         res = tuple(o[:int(nrep.value)] for o in out)
         return res + (d_sa,) if with_sa else res
 
+    # ------------------------------------- the k-mers of a text: list, abundance spectrum, all-k profile
+    def kmer_count(self, text, k, min_occ=1, max_occ=0):
+        """how many distinct k-mers of text occur at least min_occ and (max_occ > 0) at most max_occ times: the
+        sizes-only form of tc_kmers"""
+        t = _u8(text)
+        nk = C.c_uint64(0)
+        self._check(self._lib.tc_kmers(self._h, _ptr(t) if len(t) else None, len(t), k, min_occ, max_occ, None, None, None, None,
+                                       C.byref(nk)))
+        return int(nk.value)
+
+    def kmers(self, text, k, min_occ=1, max_occ=0, with_sa=False):
+        """the k-mers of text -> (pos, occ, row[, sa]), uint32 arrays in lexicographic order: k-mer i is
+        text[pos[i] : pos[i] + k], it occurs occ[i] times, at sa[row[i] : row[i] + occ[i]]: tc_kmers"""
+        t = _u8(text)
+        cap = max(self.kmer_count(t, k, min_occ, max_occ), 1)
+        pos, occ, row = (np.empty(cap, np.uint32) for _ in range(3))
+        sa = np.empty(len(t) + 1, np.uint32) if with_sa else None
+        nk = C.c_uint64(cap)
+        self._check(self._lib.tc_kmers(self._h, _ptr(t) if len(t) else None, len(t), k, min_occ, max_occ,
+                                       _ptr(sa) if with_sa else None, _ptr(pos), _ptr(occ), _ptr(row), C.byref(nk)))
+        m = int(nk.value)
+        out = (pos[:m].copy(), occ[:m].copy(), row[:m].copy())
+        return out + (sa,) if with_sa else out
+
+    def _kmers_retry(self, call, device, cap):
+        """the capacity protocol of the two device lists: call(pos, occ, row, nk) -> rc; cap None: sizes first"""
+        import torch
+        torch.cuda.synchronize()
+        if cap is None:
+            nk = C.c_uint64(0)
+            self._check(call(None, None, None, C.byref(nk)))
+            cap = int(nk.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            out = [torch.empty(cap, dtype=torch.int32, device=device) for _ in range(3)]
+            torch.cuda.synchronize()
+            nk = C.c_uint64(cap)
+            rc = call(*(C.c_void_p(o.data_ptr()) for o in out), C.byref(nk))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nk.value), 1)
+        self._check(rc)
+        return tuple(o[:int(nk.value)] for o in out)
+
+    def kmers_dev(self, d_text, k, min_occ=1, max_occ=0, with_sa=False, cap=None):
+        """text resident in HBM -> (pos, occ, row[, sa]), int32 tensors on the device: tc_kmers_dev.  cap: the k-mer
+        slots to try first (None: the sizes-only form runs first)"""
+        import torch
+        n = d_text.numel()
+        pt = C.c_void_p(d_text.data_ptr()) if n else None
+        d_sa = torch.empty(n + 1, dtype=torch.int32, device=d_text.device) if with_sa else None
+        psa = C.c_void_p(d_sa.data_ptr()) if with_sa else None
+        res = self._kmers_retry(lambda p, o, r, nk: self._lib.tc_kmers_dev(self._h, pt, n, k, min_occ, max_occ, psa, p, o, r, nk),
+                                d_text.device, cap)
+        return res + (d_sa,) if with_sa else res
+
+    def kmers_esa_dev(self, d_sa, d_lcp, k, min_occ=1, max_occ=0, cap=None):
+        """a suffix array and its LCP array resident in HBM (suffix_array_dev, lcp_array_dev: the sort is paid once for
+        any number of k) -> (pos, occ, row), int32 tensors on the device: tc_kmers_esa_dev"""
+        N = d_lcp.numel()
+        if d_sa.numel() != N or d_sa.element_size() != 4 or d_lcp.element_size() != 4:
+            raise ValueError("d_sa and d_lcp must hold the same number of 32-bit entries")
+        psa, pl = C.c_void_p(d_sa.data_ptr()), C.c_void_p(d_lcp.data_ptr())
+        return self._kmers_retry(lambda p, o, r, nk: self._lib.tc_kmers_esa_dev(self._h, psa, pl, N, k, min_occ, max_occ, p, o, r, nk),
+                                 d_lcp.device, cap)
+
+    def kmer_spectrum(self, text, k, bins=256):
+        """-> (hist uint64[bins], distinct, total): hist[i] = the distinct k-mers that occur i + 1 times, the last bin
+        those that occur at least `bins` times; total = max(0, n - k + 1): tc_kmer_spectrum"""
+        t = _u8(text)
+        hist = np.empty(max(bins, 1), np.uint64)
+        distinct, total = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.tc_kmer_spectrum(self._h, _ptr(t) if len(t) else None, len(t), k, bins, _ptr(hist),
+                                               C.byref(distinct), C.byref(total)))
+        return hist, int(distinct.value), int(total.value)
+
+    def kmer_spectrum_esa_dev(self, d_sa, d_lcp, k, bins=256):
+        """the same from an enhanced suffix array resident in HBM -> (hist, an int64 tensor of `bins` entries on the
+        device, distinct, total): tc_kmer_spectrum_esa_dev"""
+        import torch
+        N = d_lcp.numel()
+        if d_sa.numel() != N or d_sa.element_size() != 4 or d_lcp.element_size() != 4:
+            raise ValueError("d_sa and d_lcp must hold the same number of 32-bit entries")
+        d_hist = torch.empty(max(bins, 1), dtype=torch.int64, device=d_lcp.device)
+        distinct, total = C.c_uint64(), C.c_uint64()
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_kmer_spectrum_esa_dev(self._h, C.c_void_p(d_sa.data_ptr()), C.c_void_p(d_lcp.data_ptr()), N, k,
+                                                       bins, C.c_void_p(d_hist.data_ptr()), C.byref(distinct), C.byref(total)))
+        return d_hist, int(distinct.value), int(total.value)
+
+    def kmer_profile(self, text, kmax, unique=True):
+        """-> (distinct, unique), uint64 arrays of kmax entries: the number of distinct k-mers and of k-mers that occur
+        once, for every k = 1 .. kmax (unique=False: the second is None): tc_kmer_profile"""
+        t = _u8(text)
+        d = np.empty(max(kmax, 1), np.uint64)
+        u = np.empty(max(kmax, 1), np.uint64) if unique else None
+        self._check(self._lib.tc_kmer_profile(self._h, _ptr(t) if len(t) else None, len(t), kmax, _ptr(d), _ptr(u) if unique else None))
+        return d[:kmax], (u[:kmax] if unique else None)
+
+    def kmer_profile_esa_dev(self, d_lcp, kmax, unique=True):
+        """the same from an LCP array resident in HBM (the suffix array is not read): tc_kmer_profile_esa_dev; the two
+        results are host arrays"""
+        import torch
+        if d_lcp.element_size() != 4:
+            raise ValueError("d_lcp must hold 32-bit entries")
+        d = np.empty(max(kmax, 1), np.uint64)
+        u = np.empty(max(kmax, 1), np.uint64) if unique else None
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_kmer_profile_esa_dev(self._h, C.c_void_p(d_lcp.data_ptr()), d_lcp.numel(), kmax, _ptr(d),
+                                                      _ptr(u) if unique else None))
+        return d[:kmax], (u[:kmax] if unique else None)
+
     def bwt_decode(self, L, primary):
         L = _u8(L)
         N = len(L)

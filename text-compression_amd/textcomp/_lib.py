@@ -84,6 +84,13 @@ SYMBOLS = [
     ("tc_lz_unparse_dev", _INT, [_P, _P, _P, _U64, _P, _PU64]),
     ("tc_repeats", _INT, [_P, _P, _U64, _INT, _U32, _U32, _P, _P, _P, _P, _P, _PU64]),
     ("tc_repeats_dev", _INT, [_P, _P, _U64, _INT, _U32, _U32, _P, _P, _P, _P, _P, _PU64]),
+    ("tc_kmers", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
+    ("tc_kmers_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
+    ("tc_kmers_esa_dev", _INT, [_P, _P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _PU64]),
+    ("tc_kmer_spectrum", _INT, [_P, _P, _U64, _U32, _U32, _P, _PU64, _PU64]),
+    ("tc_kmer_spectrum_esa_dev", _INT, [_P, _P, _P, _U64, _U32, _U32, _P, _PU64, _PU64]),
+    ("tc_kmer_profile", _INT, [_P, _P, _U64, _U32, _P, _P]),
+    ("tc_kmer_profile_esa_dev", _INT, [_P, _P, _U64, _U32, _P, _P]),
     ("tc_bwt_decode", _INT, [_P, _P, _U64, _U64, _P]),
     ("tc_bwt_decode_sym", _INT, [_P, _P, _U64, _P, _PU64]),
     ("tc_mtf_encode", _INT, [_P, _P, _U64, _I64, _P, _P, _PU32]),
