@@ -702,7 +702,16 @@ int tc_fm_info(const tc_fm *fm, uint64_t *N, uint32_t *sigma, int16_t *c_sym, ui
  * without the locate part answers tc_fm_count only (tc_fm_locate: TC_ERR_ARG).  Buffers 16-byte
  * aligned.  *bytes: in = capacity, out = bytes used (TC_ERR_CAPACITY: bytes needed).  The byte string is BUILD-SPECIFIC
  * (it carries a format version: "TCFMI02" since round 3; an export of another version is refused with a message that
- * says so): it travels between the ranks of one job, it is not an archive format. */
+ * says so): it travels between the ranks of one job, it is not an archive format.
+ * WHAT AN IMPORTED INDEX MAY HOLD.  The import checks what is listed above and nothing else: the rank vectors, the last
+ * column, the samples' values and the suffix array are taken as they come, and the queries meet them as caller data.  The
+ * rule for every query entry (count, locate, extract, the _mm forms, factorize, host and _dev alike): a malformed body is
+ * answered by TC_ERR_MALFORMED, at the import or at the query, or by TC_OK with the answer the contents define -- the one
+ * the written rules of the kernels give on those bytes: a search interval is stepped from, counted or reported only when
+ * 1 <= s <= e <= N, anything else counts as no occurrence; a locate on a full index answers the suffix array's word + 1,
+ * whatever it is; a walk that runs into one of its bounds is TC_ERR_MALFORMED -- and every kernel stays inside the
+ * index's parts: no content makes one read or write outside them, or spin.  tests/fm_wire_ref.py is that definition in
+ * numpy; tests/test_gpu_fm_import_foreign.py holds the entries to it. */
 uint64_t tc_fm_export_bound(const tc_fm *fm, int with_locate);
 int tc_fm_export_dev(tc_ctx *ctx, const tc_fm *fm, int with_locate, uint8_t *d_out, uint64_t *bytes);
 int tc_fm_import_dev(tc_ctx *ctx, const uint8_t *d_in, uint64_t bytes, tc_fm **out);

@@ -2,8 +2,8 @@
 reference of tests/factor_ref.py: fac_offs, fac_pos and fac_len are compared exactly, on the smallest shapes at which the
 kernel can go wrong (rank-line boundaries, every alphabet class, bytes the text does not hold, the length edges, a
 divergent batch of more than one workgroup), through the host and the device entry points, on a full and on sampled
-indexes.  Nothing here hands the device a malformed index: what the parse does on one is argued from the loop's bounds in
-DESIGN.md 5e."""
+indexes.  What the parse does on an imported index that no build wrote is argued from the loop's bounds in DESIGN.md 5e
+and tested in tests/test_gpu_fm_import_foreign.py against the model of tests/fm_wire_ref.py."""
 import ctypes as C
 
 import numpy as np

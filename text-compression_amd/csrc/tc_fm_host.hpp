@@ -161,59 +161,7 @@ __global__ __launch_bounds__(256) void fm_bits2_kernel(const u8 *__restrict__ L,
     }
 }
 
-// Occ(c, k): occurrences of code c in L[0 .. k)
-__device__ __forceinline__ u64 fm_occ(const u64 *__restrict__ bits, u64 lines, u32 c, u64 k) {
-    u64 line = k / FM_LINE_BITS;
-    u32 off = (u32)(k - line * FM_LINE_BITS);
-    const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(bits + ((u64)c * lines + line) * 8);
-    ulonglong2 a = p[0], b = p[1], cc = p[2], d = p[3];
-    u64 w[7] = {a.y, b.x, b.y, cc.x, cc.y, d.x, d.y};
-    u64 r = a.x;
-    u32 full = off >> 6, rem = off & 63;
-#pragma unroll
-    for (int i = 0; i < 7; i++) {
-        u64 m = ((u32)i < full) ? ~0ull : (((u32)i == full) ? ((1ull << rem) - 1ull) : 0ull);
-        r += (u64)__popcll(w[i] & m);
-    }
-    return r;
-}
-
-// Occ(c, k1) and Occ(c, k2), k1 <= k2, of one backward-search step.  Once the range [s, e] has
-// narrowed (after ~13 steps on a 2^28 DNA text it is a single row) both positions lie in the same
-// 64-byte line: it is fetched once.  Lanes whose positions straddle two lines fetch the second one.
-__device__ __forceinline__ void fm_occ2(const u64 *__restrict__ bits, u64 lines, u32 c, u64 k1, u64 k2,
-                                        u64 *r1, u64 *r2) {
-    const u64 line1 = k1 / FM_LINE_BITS, line2 = k2 / FM_LINE_BITS;
-    const u32 off1 = (u32)(k1 - line1 * FM_LINE_BITS), off2 = (u32)(k2 - line2 * FM_LINE_BITS);
-    const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(bits + ((u64)c * lines + line1) * 8);
-    ulonglong2 a = p[0], b = p[1], cc = p[2], d = p[3];
-    {
-        const u64 w[7] = {a.y, b.x, b.y, cc.x, cc.y, d.x, d.y};
-        u64 r = a.x;
-        const u32 full = off1 >> 6, rem = off1 & 63;
-#pragma unroll
-        for (int i = 0; i < 7; i++) {
-            const u64 m = ((u32)i < full) ? ~0ull : (((u32)i == full) ? ((1ull << rem) - 1ull) : 0ull);
-            r += (u64)__popcll(w[i] & m);
-        }
-        *r1 = r;
-    }
-    if (line2 != line1) {
-        const ulonglong2 *q = reinterpret_cast<const ulonglong2 *>(bits + ((u64)c * lines + line2) * 8);
-        a = q[0]; b = q[1]; cc = q[2]; d = q[3];
-    }
-    {
-        const u64 w[7] = {a.y, b.x, b.y, cc.x, cc.y, d.x, d.y};
-        u64 r = a.x;
-        const u32 full = off2 >> 6, rem = off2 & 63;
-#pragma unroll
-        for (int i = 0; i < 7; i++) {
-            const u64 m = ((u32)i < full) ? ~0ull : (((u32)i == full) ? ((1ull << rem) - 1ull) : 0ull);
-            r += (u64)__popcll(w[i] & m);
-        }
-        *r2 = r;
-    }
-}
+#include "tc_fm_count.hpp"   // fm_occ, fm_occ2: the rank lookups; fm_count_lane: the backward search of one pattern
 
 // C2[a * sigma + b] = C[a] + Occ(a, C[b]): the 0-based start of the interval of suffixes that begin with "ab"
 __global__ void fm_c2_kernel(const u64 *__restrict__ bits, u64 lines, const u32 *__restrict__ tab, u32 sigma,
@@ -224,12 +172,19 @@ __global__ void fm_c2_kernel(const u64 *__restrict__ bits, u64 lines, const u32 
     tab2[t] = tab[256 + a] + (u32)fm_occ(bits, lines, a, (u64)tab[256 + b]);
 }
 
-// countFMIndex (FMIndex/Internal.hs:347-438), one pattern per lane.
-// ranges (optional): [2p] = s, [2p+1] = e (1-based inclusive) for non-empty results.
+// countFMIndex (FMIndex/Internal.hs:347-438), one pattern per lane (the loop: fm_count_lane, tc_fm_count.hpp).
+// ranges (optional): [2p] = s, [2p+1] = e (1-based inclusive) for non-empty results, 0 0 otherwise.
+// The index may be an imported byte string, i.e. caller data.  The rule for every query on such an index: a malformed body
+// is answered by TC_ERR_MALFORMED, at import or at the query, or by TC_OK with the answer the contents define, and every
+// kernel stays inside the index's parts.  Here: an interval is only stepped from, counted or written as a range when
+// 1 <= s <= e <= N (N = the rows of the index), so no rank count, however wrong, moves a read outside the vectors, and
+// the ranges that fm_locate_fill_kernel, fm_locate_rows_kernel and fm_offsets_of_counts take from this kernel hold rows
+// below N and at most N of them per pattern.  tests/fm_wire_ref.py states the answers, tests/test_gpu_fm_import_foreign.py
+// and host/check/fm_count_kernels.cpp (the same loop under a host sanitizer) hold the kernel to them.
 template <bool PAIRS>
 __global__ __launch_bounds__(256) void fm_count_kernel(const u64 *__restrict__ bits, const u64 *__restrict__ bits2,
                                                        u64 lines, const u32 *__restrict__ tab,
-                                                       const u32 *__restrict__ tab2, u32 sigma,
+                                                       const u32 *__restrict__ tab2, u32 sigma, u64 N,
                                                        const u8 *__restrict__ pats,
                                                        const u64 *__restrict__ offs, u64 npat,
                                                        i64 *__restrict__ out,
@@ -241,62 +196,12 @@ __global__ __launch_bounds__(256) void fm_count_kernel(const u64 *__restrict__ b
     __syncthreads();
     u64 p = (u64)blockIdx.x * 256 + threadIdx.x;
     if (p >= npat) return;
-    const u64 beg = offs[p], end = offs[p + 1];
-    i64 s = -1, e = -1;
-    bool first = true, flag = false;
-    // the pattern is read right to left through an aligned 8-byte window: one load per 8 steps instead of
-    // one uncoalesced byte load per step (64 lanes = 64 different lines every time).  The aligned word
-    // that holds a valid byte lies in that byte's page, so reading it whole is always safe.
-    uintptr_t wbase = ~(uintptr_t)0;
-    u64 word = 0;
-    auto byte_at = [&](u64 q) -> u32 {   // pats[q]
-        const uintptr_t ad = (uintptr_t)(pats + q);
-        if ((ad & ~(uintptr_t)7) != wbase) {
-            wbase = ad & ~(uintptr_t)7;
-            word = *reinterpret_cast<const u64 *>(wbase);
-        }
-        return (u32)(word >> (8 * (ad & 7))) & 255u;
-    };
-    u64 q = end;
-    while (q > beg) {                   // right to left (:375)
-        if (s > e) {                    // :387-389
-            flag = true;
-            break;
-        }
-        const u32 c = s_tab[byte_at(q - 1)];
-        if (c == 0xFFFFFFFFu) break;    // findIndexL = Nothing: the loop just stops (:393,:421)
-        const i64 C = (i64)s_tab[256 + c];
-        if (first) {                    // :391-418
-            s = C + 1;
-            e = C + (i64)s_tab[512 + c];
-            first = false;
-            q--;
-            continue;
-        }
-        if (PAIRS && q - 1 > beg) {     // two symbols by one lookup, when the one to the left occurs in the text too
-            const u32 a = s_tab[byte_at(q - 2)];
-            if (a != 0xFFFFFFFFu) {
-                const u32 pr = a * sigma + c;
-                u64 o1, o2;
-                fm_occ2(bits2, lines, pr, (u64)(s - 1), (u64)e, &o1, &o2);
-                const i64 C2 = (i64)s_tab2[pr];
-                s = C2 + (i64)o1 + 1;
-                e = C2 + (i64)o2;
-                q -= 2;
-                continue;
-            }
-        }
-        u64 o1, o2;                     // :424-432 (s <= e here: s - 1 < e)
-        fm_occ2(bits, lines, c, (u64)(s - 1), (u64)e, &o1, &o2);
-        s = C + (i64)o1 + 1;
-        e = C + (i64)o2;
-        q--;
-    }
-    i64 cnt = (first || (e - s + 1) == 0 || flag) ? 0 : (e - s + 1);  // :366-371
+    u64 s = 0, e = 0;
+    const i64 cnt = fm_count_lane<PAIRS>(bits, bits2, lines, s_tab, s_tab2, sigma, N, pats, offs[p], offs[p + 1], &s, &e);
     out[p] = cnt;
     if (ranges) {
-        ranges[2 * p] = cnt ? (u64)s : 0;
-        ranges[2 * p + 1] = cnt ? (u64)e : 0;
+        ranges[2 * p] = s;
+        ranges[2 * p + 1] = e;
     }
 }
 
@@ -806,12 +711,12 @@ static void fm_count_device(tc_ctx *ctx, const tc_fm *fm, const u8 *d_pats, cons
                             u64 npat, i64 *d_out, u64 *d_ranges) {
     if (fm->d_bits2)
         fm_count_kernel<true><<<tc_cdiv(npat, 256), 256, 0, ctx->stream>>>(fm->d_bits, fm->d_bits2, fm->lines, fm->d_tab,
-                                                                           fm->d_tab2, fm->sigma_bytes, d_pats, d_offs,
-                                                                           npat, d_out, d_ranges);
+                                                                           fm->d_tab2, fm->sigma_bytes, fm->N, d_pats,
+                                                                           d_offs, npat, d_out, d_ranges);
     else
         fm_count_kernel<false><<<tc_cdiv(npat, 256), 256, 0, ctx->stream>>>(fm->d_bits, nullptr, fm->lines, fm->d_tab,
-                                                                            nullptr, fm->sigma_bytes, d_pats, d_offs,
-                                                                            npat, d_out, d_ranges);
+                                                                            nullptr, fm->sigma_bytes, fm->N, d_pats,
+                                                                            d_offs, npat, d_out, d_ranges);
     TC_LAUNCH_CHECK(ctx);
 }
 

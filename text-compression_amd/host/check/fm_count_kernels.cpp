@@ -1,0 +1,351 @@
+// Stand-alone host check of the FM-index backward search (csrc/tc_fm_count.hpp), meant to be built with a host sanitizer:
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I text-compression_amd/csrc
+//       text-compression_amd/host/check/fm_count_kernels.cpp -o fm_count_kernels && ./fm_count_kernels
+// TC_FM_COUNT_HOST_CHECK compiles fm_occ, fm_occ2 and fm_count_lane -- the loop of fm_count_kernel -- as plain C++.  Every
+// index is built naively here (suffixes sorted directly, the rank lines written in the 448-bit line format bit by bit, the
+// pair table as fm_c2_kernel makes it) with the vectors in heap blocks of exactly sigma * lines * 64 bytes, so a read one
+// word outside either of them stops the run.  Patterns lie in an 8-byte aligned block padded to 8: the loop reads aligned
+// 8-byte words.  What it walks:
+//   - well-formed indexes against brute force (substring search): n = 446, 447, 448, 1342, 1343, 1344 -- both sides of a
+//     line; n = 447 and 1343 make N a multiple of 448, so the last line is empty -- over ACGTN (pair vectors), six letters
+//     (no pairs) and 256 byte values;
+//   - indexes no build writes: a line's ones-before word set to 0, N, 2^32 - 1, 2^63, one less than its predecessor's, or
+//     a value that makes s > e behind it (V2); a line all ones, all zeros, a bit at the primary row, bits behind row N in
+//     the last line (V3); the same on the pair vectors and on the byte-vector lines the pair table is made from, the table
+//     made again from the damaged lines (V4).
+// On those the answer is the one the contents define: a naive loop here with the same rule -- an interval is stepped from
+// or reported only when 1 <= s <= e <= N -- whose every line read is checked against the vector's size.  The program
+// asserts that the damages were reached: some changed an answer, some were cut to 0 by the rule.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <random>
+#include <string>
+#include <vector>
+
+#define TC_FM_COUNT_HOST_CHECK
+#include "tc_fm_count.hpp"
+
+#define EXPECT(cond)                                                              \
+    do {                                                                          \
+        if (!(cond)) {                                                            \
+            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
+            std::exit(1);                                                         \
+        }                                                                         \
+    } while (0)
+
+typedef std::vector<u8> Bytes;
+static const u32 PAIR_SIGMA = 5;   // FM_PAIR_SIGMA of tc_fm_host.hpp
+
+struct Index {
+    Bytes text;
+    u64 n = 0, N = 0, lines = 0, primary = 0;
+    u32 sigma = 0;
+    bool pairs = false;
+    std::vector<u32> sa;
+    std::unique_ptr<u64[]> bits, bits2;     // exactly sigma * lines * 8 and sigma^2 * lines * 8 words
+    u32 tab[768], tab2[PAIR_SIGMA * PAIR_SIGMA];
+    u64 words(bool pair) const { return (u64)(pair ? sigma * sigma : sigma) * lines * 8; }
+    u64 *vec(bool pair) const { return pair ? bits2.get() : bits.get(); }
+};
+
+static void make_tab2(Index &ix) {      // fm_c2_kernel
+    memset(ix.tab2, 0, sizeof ix.tab2);
+    for (u32 t = 0; t < ix.sigma * ix.sigma; t++) {
+        const u32 a = t / ix.sigma, b = t % ix.sigma;
+        ix.tab2[t] = ix.tab[256 + a] + (u32)fm_occ(ix.bits.get(), ix.lines, a, (u64)ix.tab[256 + b]);
+    }
+}
+
+static void set_bit(u64 *vec, u64 lines, u32 v, u64 row) {
+    vec[((u64)v * lines + row / FM_LINE_BITS) * 8 + 1 + (row % FM_LINE_BITS) / 64] |= 1ull << (row % 64);
+}
+static void scan_lines(u64 *vec, u64 lines, u32 nvec) {     // word 0 = ones before the line
+    for (u32 v = 0; v < nvec; v++) {
+        u64 run = 0;
+        for (u64 l = 0; l < lines; l++) {
+            u64 *w = vec + ((u64)v * lines + l) * 8;
+            w[0] = run;
+            for (int i = 1; i < 8; i++) run += (u64)__builtin_popcountll(w[i]);
+        }
+    }
+}
+
+static void build_index(Index &ix, const Bytes &text) {
+    ix.text = text;
+    const u64 n = ix.n = text.size(), N = ix.N = n + 1;
+    ix.sa.resize(N);
+    for (u32 i = 0; i < N; i++) ix.sa[i] = i;
+    std::sort(ix.sa.begin(), ix.sa.end(), [&](u32 x, u32 y) {   // the empty suffix first: a proper prefix sorts first
+        const size_t lx = n - x, ly = n - y;
+        const int c = memcmp(text.data() + x, text.data() + y, std::min(lx, ly));
+        return c ? c < 0 : lx < ly;
+    });
+    u32 counts[256] = {};
+    for (u8 b : text) counts[b]++;
+    u32 sig = 0, acc = 1;                                       // fm_make_tab
+    for (int b = 0; b < 256; b++) {
+        ix.tab[b] = 0xFFFFFFFFu;
+        if (counts[b]) {
+            ix.tab[b] = sig;
+            ix.tab[256 + sig] = acc;
+            ix.tab[512 + sig] = counts[b];
+            acc += counts[b];
+            sig++;
+        }
+    }
+    for (u32 c = sig; c < 256; c++) ix.tab[256 + c] = ix.tab[512 + c] = 0;
+    ix.sigma = sig;
+    ix.lines = N / FM_LINE_BITS + 1;
+    ix.bits.reset(new u64[ix.words(false)]());
+    ix.pairs = sig <= PAIR_SIGMA && n >= 2;
+    if (ix.pairs) ix.bits2.reset(new u64[ix.words(true)]());
+    for (u64 j = 0; j < N; j++) {
+        const u32 p = ix.sa[j];
+        if (p == 0) {
+            ix.primary = j;                                     // no bit in any symbol vector
+            continue;
+        }
+        set_bit(ix.bits.get(), ix.lines, ix.tab[text[p - 1]], j);
+        if (ix.pairs && p >= 2) set_bit(ix.bits2.get(), ix.lines, ix.tab[text[p - 2]] * sig + ix.tab[text[p - 1]], j);
+    }
+    scan_lines(ix.bits.get(), ix.lines, sig);
+    if (ix.pairs) {
+        scan_lines(ix.bits2.get(), ix.lines, sig * sig);
+        make_tab2(ix);
+    }
+}
+
+// ---- the answer the contents define: the same rule, a plain loop, every read checked -----------------------------------------
+struct Answer {
+    i64 cnt = 0;
+    u64 s = 0, e = 0;
+    bool cut = false;       // an interval of another shape than s = e + 1 ended the search: the rule, not an empty result
+};
+static u64 occ_checked(const Index &ix, bool pair, u32 v, u64 k) {
+    const u64 line = k / FM_LINE_BITS, off = k % FM_LINE_BITS;
+    const u64 at = ((u64)v * ix.lines + line) * 8;
+    EXPECT(v < (pair ? ix.sigma * ix.sigma : ix.sigma) && line < ix.lines && at + 8 <= ix.words(pair));
+    const u64 *w = ix.vec(pair) + at;
+    u64 r = w[0];
+    for (u64 j = 0; j < off; j++) r += (w[1 + j / 64] >> (j % 64)) & 1;
+    return r;
+}
+static Answer model_count(const Index &ix, const u8 *pat, u64 m) {
+    Answer A;
+    u64 s = 1, e = ix.N, q = m;
+    bool first = true;
+    auto ok = [&](u64 a, u64 b) { return a >= 1 && a <= b && b <= ix.N; };
+    while (q > 0) {
+        if (!ok(s, e)) {
+            A.cut = s != e + 1;
+            return A;
+        }
+        const u32 c = ix.tab[pat[q - 1]];
+        if (c == 0xFFFFFFFFu) break;
+        const u64 C = ix.tab[256 + c];
+        if (first) {
+            s = C + 1;
+            e = C + ix.tab[512 + c];
+            first = false;
+            q--;
+            continue;
+        }
+        if (ix.pairs && q >= 2 && ix.tab[pat[q - 2]] != 0xFFFFFFFFu) {
+            const u32 pr = ix.tab[pat[q - 2]] * ix.sigma + c;
+            const u64 o1 = occ_checked(ix, true, pr, s - 1), o2 = occ_checked(ix, true, pr, e);
+            s = ix.tab2[pr] + o1 + 1;
+            e = ix.tab2[pr] + o2;
+            q -= 2;
+            continue;
+        }
+        const u64 o1 = occ_checked(ix, false, c, s - 1), o2 = occ_checked(ix, false, c, e);
+        s = C + o1 + 1;
+        e = C + o2;
+        q--;
+    }
+    if (first) return A;
+    if (!ok(s, e)) {
+        A.cut = s != e + 1;
+        return A;
+    }
+    A.cnt = (i64)(e - s + 1);
+    A.s = s;
+    A.e = e;
+    return A;
+}
+
+// ---- patterns: one 8-byte aligned block padded to 8, offsets as the kernel takes them ---------------------------------------
+struct Patterns {
+    std::vector<Bytes> list;
+    std::unique_ptr<u64[]> blk;
+    std::vector<u64> offs;
+    void pack() {
+        u64 total = 0;
+        offs.assign(1, 0);
+        for (const Bytes &p : list) offs.push_back(total += p.size());
+        blk.reset(new u64[total / 8 + 1]());
+        u8 *d = reinterpret_cast<u8 *>(blk.get());
+        for (size_t i = 0; i < list.size(); i++)
+            if (!list[i].empty()) memcpy(d + offs[i], list[i].data(), list[i].size());
+    }
+    const u8 *data() const { return reinterpret_cast<const u8 *>(blk.get()); }
+};
+static void make_patterns(Patterns &P, const Bytes &text, std::mt19937 &rng) {
+    const u64 n = text.size();
+    P.list.clear();
+    for (int b = 0; b < 256; b++) P.list.push_back(Bytes(1, (u8)b));             // every single byte, present or not
+    P.list.push_back(Bytes());                                                  // the empty pattern
+    u8 foreign = 0;
+    while (std::find(text.begin(), text.end(), foreign) != text.end() && foreign != 255) foreign++;
+    const bool have_foreign = std::find(text.begin(), text.end(), foreign) == text.end();
+    for (int k = 0; k < 48; k++) {
+        const u64 len = k < 20 ? 2 + rng() % 4 : k < 40 ? 2 + rng() % 12 : 20 + rng() % 200;
+        const u64 at = rng() % (n - std::min(len, n - 1));
+        Bytes p(text.begin() + at, text.begin() + std::min(n, at + len));
+        P.list.push_back(p);
+        Bytes c = p;                                                            // one changed byte
+        c[rng() % c.size()] = text[rng() % n];
+        P.list.push_back(c);
+        if (have_foreign && k % 8 == 0) {                                       // a byte the text lacks: the loop stops there
+            Bytes f = p;
+            f[rng() % f.size()] = foreign;
+            P.list.push_back(f);
+        }
+    }
+    P.list.push_back(text);                                                     // through every line
+    Bytes twice = text;
+    twice.insert(twice.end(), text.begin(), text.end());
+    P.list.push_back(twice);
+    P.pack();
+}
+
+static Answer run_lane(const Index &ix, const Patterns &P, size_t i) {
+    Answer A;
+    A.cnt = ix.pairs ? fm_count_lane<true>(ix.bits.get(), ix.bits2.get(), ix.lines, ix.tab, ix.tab2, ix.sigma, ix.N, P.data(),
+                                           P.offs[i], P.offs[i + 1], &A.s, &A.e)
+                     : fm_count_lane<false>(ix.bits.get(), nullptr, ix.lines, ix.tab, nullptr, ix.sigma, ix.N, P.data(),
+                                            P.offs[i], P.offs[i + 1], &A.s, &A.e);
+    return A;
+}
+
+struct Tally {
+    u64 cases = 0, changed = 0, cut = 0;
+};
+// every pattern through the loop and through the model; `base` (the undamaged index's answers) only to count what changed
+static void compare_all(const Index &ix, const Patterns &P, const std::vector<Answer> *base, Tally *T) {
+    bool changed = false, cut = false;
+    for (size_t i = 0; i < P.list.size(); i++) {
+        const Answer want = model_count(ix, P.list[i].data(), P.list[i].size());
+        const Answer got = run_lane(ix, P, i);
+        EXPECT(got.cnt == want.cnt && got.s == want.s && got.e == want.e);
+        EXPECT(got.cnt == 0 ? (got.s == 0 && got.e == 0) : (got.s >= 1 && got.e <= ix.N && got.cnt == (i64)(got.e - got.s + 1)));
+        if (base && (*base)[i].cnt != got.cnt) changed = true;
+        cut = cut || want.cut;
+    }
+    if (T) {
+        T->cases++;
+        T->changed += changed;
+        T->cut += cut;
+    }
+}
+
+static u64 brute_count(const Bytes &text, const Bytes &p) {
+    if (p.empty() || p.size() > text.size()) return 0;
+    u64 c = 0;
+    for (size_t i = 0; i + p.size() <= text.size(); i++) c += memcmp(text.data() + i, p.data(), p.size()) == 0;
+    return c;
+}
+
+// ---- the damages -----------------------------------------------------------------------------------------------------------
+// damage one line of one vector, run, restore.  On a byte vector of an index with pairs the pair table is made again from
+// the damaged lines, as the import does.
+template <class F>
+static void with_line(Index &ix, bool pair, u32 v, u64 line, const Patterns &P, const std::vector<Answer> &base, Tally *T, F &&damage) {
+    u64 *w = ix.vec(pair) + ((u64)v * ix.lines + line) * 8;
+    u64 keep[8];
+    memcpy(keep, w, sizeof keep);
+    damage(w);
+    if (memcmp(keep, w, sizeof keep) != 0) {
+        if (!pair && ix.pairs) make_tab2(ix);
+        compare_all(ix, P, &base, T);
+        memcpy(w, keep, sizeof keep);
+        if (!pair && ix.pairs) make_tab2(ix);
+    }
+}
+
+static void damages(Index &ix, const Patterns &P, std::mt19937 &rng, Tally *V2, Tally *V3, Tally *V4) {
+    std::vector<Answer> base;
+    for (size_t i = 0; i < P.list.size(); i++) base.push_back(run_lane(ix, P, i));
+    for (int pair = 0; pair <= (ix.pairs ? 1 : 0); pair++) {
+        const u32 nvec = pair ? ix.sigma * ix.sigma : ix.sigma;
+        std::vector<std::pair<u32, u64>> where;
+        for (u32 v = 0; v < nvec; v++)
+            for (u64 l = 0; l < ix.lines; l++) where.push_back({v, l});
+        std::shuffle(where.begin(), where.end(), rng);
+        if (where.size() > 10) where.resize(10);    // (a sample: every line is alike to the loop)
+        // (the pair vectors, and the byte vectors the pair table is made from, are family V4)
+        Tally *H = (pair || ix.pairs) ? V4 : V2, *B = (pair || ix.pairs) ? V4 : V3;
+        for (const auto &vl : where) {
+            const u32 v = vl.first;
+            const u64 l = vl.second;
+            const u64 prev = l ? ix.vec(pair)[((u64)v * ix.lines + l - 1) * 8] : 0;
+            const u64 own = ix.vec(pair)[((u64)v * ix.lines + l) * 8];
+            const u64 heads[] = {0, ix.N, 0xFFFFFFFFull, 1ull << 63, prev - 1, own + 1000, own + 1};
+            for (u64 h : heads) with_line(ix, pair, v, l, P, base, H, [&](u64 *w) { w[0] = h; });
+            with_line(ix, pair, v, l, P, base, B, [&](u64 *w) { for (int i = 1; i < 8; i++) w[i] = ~0ull; });
+            with_line(ix, pair, v, l, P, base, B, [&](u64 *w) { for (int i = 1; i < 8; i++) w[i] = 0; });
+            if (l == ix.primary / FM_LINE_BITS)
+                with_line(ix, pair, v, l, P, base, B, [&](u64 *w) { w[1 + (ix.primary % FM_LINE_BITS) / 64] |= 1ull << (ix.primary % 64); });
+            if (l == ix.lines - 1)
+                with_line(ix, pair, v, l, P, base, B, [&](u64 *w) {
+                    for (u64 r = ix.N % FM_LINE_BITS; r < FM_LINE_BITS; r++) w[1 + r / 64] |= 1ull << (r % 64);
+                });
+        }
+    }
+}
+
+static Bytes random_text(std::mt19937 &rng, u64 n, const std::string &alphabet) {
+    Bytes t(n);
+    for (u8 &b : t) b = alphabet.empty() ? (u8)(rng() & 255) : (u8)alphabet[rng() % alphabet.size()];
+    return t;
+}
+
+int main() {
+    std::mt19937 rng(20250214);
+    Tally V2, V3, V4;
+    u64 indexes = 0, patterns = 0;
+    for (u64 n : {446u, 447u, 448u, 1342u, 1343u, 1344u})
+        for (const char *alphabet : {"ACGTN", "ACGTNU", ""}) {
+            Index ix;
+            build_index(ix, random_text(rng, n, alphabet));
+            EXPECT(ix.lines == ix.N / FM_LINE_BITS + 1 && ix.pairs == (strlen(alphabet) == 5));
+            Patterns P;
+            make_patterns(P, ix.text, rng);
+            for (size_t i = 0; i < P.list.size(); i++) {        // well-formed: brute force over the text
+                const Answer got = run_lane(ix, P, i);
+                const Bytes &p = P.list[i];
+                // (a byte the text lacks stops the loop: what is counted is the pattern's part behind the last such byte)
+                size_t from = p.size();
+                while (from > 0 && ix.tab[p[from - 1]] != 0xFFFFFFFFu) from--;
+                EXPECT((u64)got.cnt == brute_count(ix.text, Bytes(p.begin() + from, p.end())));
+                for (u64 r = got.s; got.cnt && r <= got.e; r++)
+                    EXPECT(memcmp(ix.text.data() + ix.sa[r - 1], p.data() + from, p.size() - from) == 0);
+            }
+            compare_all(ix, P, nullptr, nullptr);
+            damages(ix, P, rng, &V2, &V3, &V4);
+            indexes++;
+            patterns += P.list.size();
+        }
+    for (const Tally *T : {&V2, &V3, &V4}) EXPECT(T->cases > 0 && T->changed > 0);
+    EXPECT(V2.cut > 0 && V4.cut > 0);
+    std::printf("ok: backward search of %llu patterns on %llu indexes; damaged lines: V2 %llu (changed %llu, cut %llu), V3 %llu (changed %llu), "
+                "V4 %llu (changed %llu, cut %llu)\n",
+                (unsigned long long)patterns, (unsigned long long)indexes, (unsigned long long)V2.cases,
+                (unsigned long long)V2.changed, (unsigned long long)V2.cut, (unsigned long long)V3.cases,
+                (unsigned long long)V3.changed, (unsigned long long)V4.cases, (unsigned long long)V4.changed,
+                (unsigned long long)V4.cut);
+    return 0;
+}
