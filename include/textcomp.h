@@ -284,6 +284,52 @@ int tc_kmer_spectrum_esa_dev(tc_ctx *ctx, const uint32_t *d_sa, const uint32_t *
                              uint64_t *d_hist, uint64_t *distinct, uint64_t *total);
 int tc_kmer_profile(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t kmax, uint64_t *distinct, uint64_t *unique);
 int tc_kmer_profile_esa_dev(tc_ctx *ctx, const uint32_t *d_lcp, uint64_t N, uint32_t kmax, uint64_t *distinct, uint64_t *unique);
+/* ---- one text against another: matching statistics, maximal exact matches, longest common substring (not part of the
+ * reference's surface) ----
+ * Q is the query (a bytes), T the target (b bytes), a + b <= TC_MAX_N; all positions 0-based.  For every 0 <= i < a:
+ *   ms_len[i] = the largest l such that Q[i .. i+l) occurs in T.  The match lies inside both texts and never runs over an
+ *               end; l = 0: the byte Q[i] does not occur in T.
+ *   ms_pos[i] = the start in T of the lexicographically smallest suffix of T that has that string as a prefix (the end of
+ *               the text sorts first, as everywhere here); 0 where l = 0.
+ *   ms_occ[i] = the number of occurrences of that string in T, overlapping ones included; 0 where l = 0.
+ * (ms_len, ms_pos + 1, ms_occ) is what tc_fm_match_stats answers for the single pattern Q on an index of T built by
+ * tc_fm_build_lcp.  ms_pos and ms_occ may each be NULL; ms_len may not.
+ * THE MEMS for min_len >= 1 are the triples (mem_start, mem_pos, mem_len) = (i, ms_pos[i], ms_len[i]) with
+ * ms_len[i] >= min_len and (i = 0 or ms_len[i-1] <= ms_len[i]), in increasing i: the rule of tc_fm_mems.  *nmem (a host
+ * word): in = capacity of the three arrays, out = the count.  Too small: TC_ERR_CAPACITY, *nmem = the needed count, nothing
+ * written to the arrays.  mem_start = mem_pos = mem_len = NULL with capacity 0 is the sizes-only form: TC_OK, the count
+ * written.  Capacity a is always enough.  tc_mems_from_stats_dev is the filter alone over two arrays of a entries in HBM,
+ * so that one tc_text_match_stats_dev serves any number of min_len; it compares and copies the array values and never
+ * uses one as an index, so it stays in bounds on any contents (d_ms_pos may be NULL in its sizes-only form).
+ * THE LCS: *len = the largest ms_len, *qpos = the smallest i that attains it, *tpos = ms_pos[qpos] -- Q[qpos .. qpos+len)
+ * = T[tpos .. tpos+len) is a longest common substring -- and (0, 0, 0) when no byte is common; *sum = the sum of ms_len
+ * (sum / a, the mean matching-statistics length, is the usual similarity estimate).  The four are host words in both forms.
+ *     Q         T         ms_len        ms_pos        ms_occ        MEMs at min_len 1         LCS (len, qpos, tpos), sum
+ *     "banana"  "ananas"  0 5 4 3 2 1   0 0 1 0 1 0   0 1 1 2 2 3   (1,0,5)                   (5, 1, 0), 15
+ *     "ab"      "abab"    2 1           2 3           2 2           (0,2,2)                   (2, 0, 2), 3
+ *     "aaaaa"   "aaa"     3 3 3 2 1     0 0 0 1 2     1 1 1 2 3     (0,0,3) (1,0,3) (2,0,3)   (3, 0, 0), 12
+ * ERRORS AND EDGES.  A NULL required buffer, a + b > TC_MAX_N or min_len = 0: TC_ERR_ARG, nothing written.  a = 0: TC_OK,
+ * nothing read or written, 0 MEMs, an LCS of all zeros.  b = 0: zeros to every given array, 0 MEMs, no sort.  Q and T may
+ * be the same buffer or overlap (both are only read): for Q = T, ms_len[i] = a - i.
+ * The calls take the two texts only.  They are copied into one text Q T whose enhanced suffix array answers everything;
+ * that text, the arrays and all scratch (25 bytes per byte of the two texts behind the sort: the text 1, sa 4, lcp 4, the
+ * T-row flags and then the two row lists 8, the T-row counts 8; up to 12 bytes per query byte for results the caller did
+ * not give in HBM; the sort's own need where that is larger) live in the calling ctx's workspace.  The _dev forms take the
+ * two texts as separate HBM pointers and every array in HBM. */
+int tc_text_match_stats(tc_ctx *ctx, const uint8_t *query, uint64_t a, const uint8_t *target, uint64_t b, uint32_t *ms_len,
+                        uint32_t *ms_pos, uint32_t *ms_occ);
+int tc_text_match_stats_dev(tc_ctx *ctx, const uint8_t *d_query, uint64_t a, const uint8_t *d_target, uint64_t b,
+                            uint32_t *d_ms_len, uint32_t *d_ms_pos, uint32_t *d_ms_occ);
+int tc_text_mems(tc_ctx *ctx, const uint8_t *query, uint64_t a, const uint8_t *target, uint64_t b, uint32_t min_len,
+                 uint32_t *mem_start, uint32_t *mem_pos, uint32_t *mem_len, uint64_t *nmem);
+int tc_text_mems_dev(tc_ctx *ctx, const uint8_t *d_query, uint64_t a, const uint8_t *d_target, uint64_t b, uint32_t min_len,
+                     uint32_t *d_mem_start, uint32_t *d_mem_pos, uint32_t *d_mem_len, uint64_t *nmem);
+int tc_text_lcs(tc_ctx *ctx, const uint8_t *query, uint64_t a, const uint8_t *target, uint64_t b, uint32_t *len, uint64_t *qpos,
+                uint64_t *tpos, uint64_t *sum);
+int tc_text_lcs_dev(tc_ctx *ctx, const uint8_t *d_query, uint64_t a, const uint8_t *d_target, uint64_t b, uint32_t *len,
+                    uint64_t *qpos, uint64_t *tpos, uint64_t *sum);
+int tc_mems_from_stats_dev(tc_ctx *ctx, const uint32_t *d_ms_len, const uint32_t *d_ms_pos, uint64_t a, uint32_t min_len,
+                           uint32_t *d_mem_start, uint32_t *d_mem_pos, uint32_t *d_mem_len, uint64_t *nmem);
 
 /* bytestringFromWord8BWT (BWT.hs:108-110) = fromBWT (:93-104) + sortTB
  * (BWT/Internal.hs:144-149) + magicInverseBWT (:163-200), for a well-formed BWT

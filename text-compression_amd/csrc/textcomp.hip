@@ -10,6 +10,7 @@
 #include "tc_lz_host.hpp"
 #include "tc_rep_host.hpp"
 #include "tc_kmer_host.hpp"
+#include "tc_tm_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -273,6 +274,57 @@ int tc_kmer_profile(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t kmax,
 int tc_kmer_profile_esa_dev(tc_ctx *ctx, const uint32_t *d_lcp, uint64_t N, uint32_t kmax, uint64_t *distinct, uint64_t *unique) {
     TC_API_BEGIN(ctx)
     kmer_profile_esa_entry(ctx, d_lcp, N, kmax, distinct, unique);
+    TC_API_END(ctx)
+}
+
+// one text against another: matching statistics, maximal exact matches, longest common substring (no counterpart in the
+// reference): tc_tm_host.hpp
+int tc_text_match_stats(tc_ctx *ctx, const uint8_t *query, uint64_t a, const uint8_t *target, uint64_t b, uint32_t *ms_len,
+                        uint32_t *ms_pos, uint32_t *ms_occ) {
+    TC_API_BEGIN(ctx)
+    text_match_stats_entry(ctx, query, a, target, b, ms_len, ms_pos, ms_occ, false);
+    TC_API_END(ctx)
+}
+
+int tc_text_match_stats_dev(tc_ctx *ctx, const uint8_t *d_query, uint64_t a, const uint8_t *d_target, uint64_t b, uint32_t *d_ms_len,
+                            uint32_t *d_ms_pos, uint32_t *d_ms_occ) {
+    TC_API_BEGIN(ctx)
+    text_match_stats_entry(ctx, d_query, a, d_target, b, d_ms_len, d_ms_pos, d_ms_occ, true);
+    TC_API_END(ctx)
+}
+
+int tc_text_mems(tc_ctx *ctx, const uint8_t *query, uint64_t a, const uint8_t *target, uint64_t b, uint32_t min_len,
+                 uint32_t *mem_start, uint32_t *mem_pos, uint32_t *mem_len, uint64_t *nmem) {
+    TC_API_BEGIN(ctx)
+    text_mems_entry(ctx, query, a, target, b, min_len, mem_start, mem_pos, mem_len, nmem, false);
+    TC_API_END(ctx)
+}
+
+int tc_text_mems_dev(tc_ctx *ctx, const uint8_t *d_query, uint64_t a, const uint8_t *d_target, uint64_t b, uint32_t min_len,
+                     uint32_t *d_mem_start, uint32_t *d_mem_pos, uint32_t *d_mem_len, uint64_t *nmem) {
+    TC_API_BEGIN(ctx)
+    text_mems_entry(ctx, d_query, a, d_target, b, min_len, d_mem_start, d_mem_pos, d_mem_len, nmem, true);
+    TC_API_END(ctx)
+}
+
+int tc_text_lcs(tc_ctx *ctx, const uint8_t *query, uint64_t a, const uint8_t *target, uint64_t b, uint32_t *len, uint64_t *qpos,
+                uint64_t *tpos, uint64_t *sum) {
+    TC_API_BEGIN(ctx)
+    text_lcs_entry(ctx, query, a, target, b, len, qpos, tpos, sum, false);
+    TC_API_END(ctx)
+}
+
+int tc_text_lcs_dev(tc_ctx *ctx, const uint8_t *d_query, uint64_t a, const uint8_t *d_target, uint64_t b, uint32_t *len,
+                    uint64_t *qpos, uint64_t *tpos, uint64_t *sum) {
+    TC_API_BEGIN(ctx)
+    text_lcs_entry(ctx, d_query, a, d_target, b, len, qpos, tpos, sum, true);
+    TC_API_END(ctx)
+}
+
+int tc_mems_from_stats_dev(tc_ctx *ctx, const uint32_t *d_ms_len, const uint32_t *d_ms_pos, uint64_t a, uint32_t min_len,
+                           uint32_t *d_mem_start, uint32_t *d_mem_pos, uint32_t *d_mem_len, uint64_t *nmem) {
+    TC_API_BEGIN(ctx)
+    mems_from_stats_entry(ctx, d_ms_len, d_ms_pos, a, min_len, d_mem_start, d_mem_pos, d_mem_len, nmem);
     TC_API_END(ctx)
 }
 

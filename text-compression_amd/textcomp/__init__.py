@@ -484,6 +484,117 @@ class Context:
                                                       _ptr(u) if unique else None))
         return d[:kmax], (u[:kmax] if unique else None)
 
+    # ------------------------------------- one text against another: matching statistics, MEMs, LCS
+    def text_match_stats(self, query, target, pos=True, occ=True):
+        """-> (ms_len, ms_pos, ms_occ), uint32 arrays of len(query) entries, 0-based: ms_len[i] = the longest prefix of
+        query[i:] that occurs in target, ms_pos[i] = where the smallest suffix of target with that prefix starts,
+        ms_occ[i] = its occurrences in target (pos / occ False: None in their place): tc_text_match_stats"""
+        q, t = _u8(query), _u8(target)
+        a = len(q)
+        ms_len = np.empty(a, np.uint32)
+        ms_pos = np.empty(a, np.uint32) if pos else None
+        ms_occ = np.empty(a, np.uint32) if occ else None
+        if a == 0:
+            return ms_len, ms_pos, ms_occ
+        self._check(self._lib.tc_text_match_stats(self._h, _ptr(q) if a else None, a, _ptr(t) if len(t) else None, len(t),
+                                                  _ptr(ms_len), _ptr(ms_pos), _ptr(ms_occ)))
+        return ms_len, ms_pos, ms_occ
+
+    def text_mem_count(self, query, target, min_len=1):
+        """the number of maximal exact matches of query in target that are at least min_len long (the sizes-only form of
+        tc_text_mems)"""
+        q, t = _u8(query), _u8(target)
+        nmem = C.c_uint64(0)
+        self._check(self._lib.tc_text_mems(self._h, _ptr(q) if len(q) else None, len(q), _ptr(t) if len(t) else None, len(t),
+                                           min_len, None, None, None, C.byref(nmem)))
+        return int(nmem.value)
+
+    def text_mems(self, query, target, min_len=1):
+        """the maximal exact matches of query in target -> (start, pos, len), uint32 arrays in increasing start:
+        query[start : start + len] == target[pos : pos + len]: tc_text_mems"""
+        q, t = _u8(query), _u8(target)
+        cap = max(self.text_mem_count(q, t, min_len), 1)
+        start, pos, ln = (np.empty(cap, np.uint32) for _ in range(3))
+        nmem = C.c_uint64(cap)
+        self._check(self._lib.tc_text_mems(self._h, _ptr(q) if len(q) else None, len(q), _ptr(t) if len(t) else None, len(t),
+                                           min_len, _ptr(start), _ptr(pos), _ptr(ln), C.byref(nmem)))
+        k = int(nmem.value)
+        return start[:k].copy(), pos[:k].copy(), ln[:k].copy()
+
+    def text_lcs(self, query, target):
+        """-> (len, qpos, tpos, sum): query[qpos : qpos + len] == target[tpos : tpos + len] is a longest common substring
+        (the first in query; (0, 0, 0) when no byte is common), sum = the sum of ms_len: tc_text_lcs"""
+        q, t = _u8(query), _u8(target)
+        ln, qpos, tpos, tot = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self._lib.tc_text_lcs(self._h, _ptr(q) if len(q) else None, len(q), _ptr(t) if len(t) else None, len(t),
+                                          C.byref(ln), C.byref(qpos), C.byref(tpos), C.byref(tot)))
+        return int(ln.value), int(qpos.value), int(tpos.value), int(tot.value)
+
+    @staticmethod
+    def _dev_ptr(d):
+        return C.c_void_p(d.data_ptr()) if d.numel() else None
+
+    def text_match_stats_dev(self, d_query, d_target, pos=True, occ=True):
+        """the two texts resident in HBM (torch uint8 tensors on this context's device; they may be one tensor) ->
+        (ms_len, ms_pos, ms_occ), int32 tensors of a entries on the device (None where not asked for):
+        tc_text_match_stats_dev"""
+        import torch
+        a = d_query.numel()
+        out = [torch.empty(a, dtype=torch.int32, device=d_query.device) if want else None for want in (True, pos, occ)]
+        if a == 0:
+            return tuple(out)
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_text_match_stats_dev(self._h, self._dev_ptr(d_query), a, self._dev_ptr(d_target),
+                                                      d_target.numel(), *(C.c_void_p(o.data_ptr()) if o is not None else None for o in out)))
+        return tuple(out)
+
+    def _mems_retry(self, call, device, cap):
+        """the capacity protocol of the two device MEM lists: call(start, pos, len, nmem) -> rc; cap None: sizes first"""
+        import torch
+        torch.cuda.synchronize()
+        if cap is None:
+            nmem = C.c_uint64(0)
+            self._check(call(None, None, None, C.byref(nmem)))
+            cap = int(nmem.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            out = [torch.empty(cap, dtype=torch.int32, device=device) for _ in range(3)]
+            torch.cuda.synchronize()
+            nmem = C.c_uint64(cap)
+            rc = call(*(C.c_void_p(o.data_ptr()) for o in out), C.byref(nmem))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nmem.value), 1)
+        self._check(rc)
+        return tuple(o[:int(nmem.value)] for o in out)
+
+    def text_mems_dev(self, d_query, d_target, min_len=1, cap=None):
+        """the two texts resident in HBM -> (start, pos, len), int32 tensors on the device: tc_text_mems_dev.  cap: the
+        MEM slots to try first (None: the sizes-only form runs first)"""
+        pq, pt = self._dev_ptr(d_query), self._dev_ptr(d_target)
+        a, b = d_query.numel(), d_target.numel()
+        return self._mems_retry(lambda s, p, l, nm: self._lib.tc_text_mems_dev(self._h, pq, a, pt, b, min_len, s, p, l, nm),
+                                d_query.device, cap)
+
+    def mems_from_stats_dev(self, d_ms_len, d_ms_pos, min_len=1, cap=None):
+        """matching statistics resident in HBM (two 32-bit tensors of one length: text_match_stats_dev's, kept for any
+        number of min_len) -> (start, pos, len), int32 tensors on the device: tc_mems_from_stats_dev"""
+        a = d_ms_len.numel()
+        if d_ms_pos.numel() != a or d_ms_len.element_size() != 4 or d_ms_pos.element_size() != 4:
+            raise ValueError("d_ms_len and d_ms_pos must hold the same number of 32-bit entries")
+        pl, pp = self._dev_ptr(d_ms_len), self._dev_ptr(d_ms_pos)
+        return self._mems_retry(lambda s, p, l, nm: self._lib.tc_mems_from_stats_dev(self._h, pl, pp, a, min_len, s, p, l, nm),
+                                d_ms_len.device, cap)
+
+    def text_lcs_dev(self, d_query, d_target):
+        """the two texts resident in HBM -> (len, qpos, tpos, sum), host integers: tc_text_lcs_dev"""
+        import torch
+        ln, qpos, tpos, tot = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_text_lcs_dev(self._h, self._dev_ptr(d_query), d_query.numel(), self._dev_ptr(d_target),
+                                              d_target.numel(), C.byref(ln), C.byref(qpos), C.byref(tpos), C.byref(tot)))
+        return int(ln.value), int(qpos.value), int(tpos.value), int(tot.value)
+
     def bwt_decode(self, L, primary):
         L = _u8(L)
         N = len(L)

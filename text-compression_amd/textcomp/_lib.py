@@ -91,6 +91,13 @@ SYMBOLS = [
     ("tc_kmer_spectrum_esa_dev", _INT, [_P, _P, _P, _U64, _U32, _U32, _P, _PU64, _PU64]),
     ("tc_kmer_profile", _INT, [_P, _P, _U64, _U32, _P, _P]),
     ("tc_kmer_profile_esa_dev", _INT, [_P, _P, _U64, _U32, _P, _P]),
+    ("tc_text_match_stats", _INT, [_P, _P, _U64, _P, _U64, _P, _P, _P]),
+    ("tc_text_match_stats_dev", _INT, [_P, _P, _U64, _P, _U64, _P, _P, _P]),
+    ("tc_text_mems", _INT, [_P, _P, _U64, _P, _U64, _U32, _P, _P, _P, _PU64]),
+    ("tc_text_mems_dev", _INT, [_P, _P, _U64, _P, _U64, _U32, _P, _P, _P, _PU64]),
+    ("tc_text_lcs", _INT, [_P, _P, _U64, _P, _U64, _PU32, _PU64, _PU64, _PU64]),
+    ("tc_text_lcs_dev", _INT, [_P, _P, _U64, _P, _U64, _PU32, _PU64, _PU64, _PU64]),
+    ("tc_mems_from_stats_dev", _INT, [_P, _P, _P, _U64, _U32, _P, _P, _P, _PU64]),
     ("tc_bwt_decode", _INT, [_P, _P, _U64, _U64, _P]),
     ("tc_bwt_decode_sym", _INT, [_P, _P, _U64, _P, _PU64]),
     ("tc_mtf_encode", _INT, [_P, _P, _U64, _I64, _P, _P, _PU32]),
