@@ -52,6 +52,12 @@ int tc_dbg_msd_split_used(tc_ctx *ctx, uint32_t *used);
  * LSD way, TC_SA_MSD_JOINT=0, TC_MSD_DIR=0.  out[1] = the fills of that directory, summed over the workgroups (one per
  * round of slots a workgroup looked at; 0 where out[0] is 0). */
 int tc_dbg_msd_dir(tc_ctx *ctx, uint32_t out[2]);
+/* The pass over the text that finds the tied suffixes of key-only MSD levels again (csrc/tc_sa.hpp; TC_TIED_PROBE), of this
+ * context's last suffix sort.  out[0] = 0 if none ran (the LSD way, levels that move suffix starts, no tied suffix, more
+ * than the table is made for), 1 = tied_probe_kernel (codes through a byte image in LDS), 2 = tied_probe_w_kernel (raw text
+ * in LDS, codes from the key generator's register table).  out[1] = the entries it found (0 where out[0] is 0).  When the
+ * levels ran a second time with suffix starts, the figures are those of the key-only attempt before it. */
+int tc_dbg_tied_probe(tc_ctx *ctx, uint32_t out[2]);
 /* What the splitter walks of this context's last inverse BWT (a decode runs one; csrc/tc_ibwt.hpp, ibwt_walk_rank_copy in
  * csrc/tc_decode_host.hpp) did.  out[0] = the attempts run: 1, or 2 when the walks of the first wanted more extra splitter
  * slots than there are and were repeated the old way; 0 if no walk ran (a column without a Nothing).  Of the last attempt:

@@ -49,6 +49,8 @@ struct tc_ctx {
     u32 lz_tile = 0;       // positions per tile of the LZ77 parse, set by tc_dbg_lz_set_tile (0: LZ_TILE, tc_lz.hpp)
     int msd_dir_used = 0;    // the last suffix sort's aligned MSD level ran with the directory of live parents (tc_dbg_msd_dir)
     int msd_split_used = 0;  // the last suffix sort's MSD levels 1 and 2 used the split key layout (tc_dbg_msd_split_used)
+    int tied_probe_used = 0;   // the pass over the text of the last suffix sort's key-only levels (tc_dbg_tied_probe): 0 none, 1 tied_probe_kernel, 2 tied_probe_w_kernel
+    u32 tied_probe_found = 0;  // ... and the entries it found
     // the last inverse BWT's walks (ibwt_walk_rank_copy; tc_dbg_ibwt_walk): attempts run, and of the last of them the
     // records that overflowed and the extra splitter slots taken
     u32 ibwt_attempts = 0, ibwt_overflowed = 0, ibwt_extra_taken = 0;

@@ -1303,6 +1303,192 @@ __global__ __launch_bounds__(TPK_NT) void tied_probe_kernel(const u8 *__restrict
     }
 }
 
+// The same pass for alphabets whose codes come from the key generator's register table (RadixKeyGen::hash_ok, at most 8
+// bytes): the text goes to LDS RAW, one 16-byte store per unit a thread fetched, and the codes are made in registers,
+// four per v_perm_b32 -- no byte image, no table read per byte.  A thread's 64 bytes start TPW_STRIDE = 80 bytes
+// apart: the 16 lanes one cycle of a 16-byte LDS read serves ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same
+// + 32) then start at dwords 20 * lane, which are the 16 multiples of 4 mod 64 once each -- no bank is asked twice.
+// Codes at or beyond n are 0 (the key layout's "beyond the end"): raw bytes there are stored as 0 and, in the turn(s)
+// that reach n, the window's codes are masked by byte from n - base; units that are not whole, or not 16-byte aligned
+// in memory, are put together from byte loads and stored the same way.  The rolling hash over CODES, the filter, the
+// exact value and the table are tied_probe_kernel's (so are tied_table_kernel and the filter's contents).
+// Two things differ behind the window, both because the launch is bound by latency, not by LDS or VALU throughput
+// (measured: with only the staging changed it took 1.02 ms against tied_probe_kernel's 0.79 -- profiles/r15_tied_probe.txt):
+//  - every wave is on its own.  A wave stages the 4096 + 64 bytes of ITS 64 lanes in its own part of s_raw and goes
+//    through the text in turns of 4096 positions; no workgroup barrier after the filter is in LDS, so the waves of
+//    a CU drift apart and one's LDS reads lie beside another's VALU work.  (The 64 bytes behind a wave's positions
+//    are loaded by it and by the next wave.)  The grid is tied_probe_kernel's: 3 x CUs workgroups of TPK_NT.
+//  - the positions that pass the filter are dealt out over the lanes of the wave before their exact value is made
+//    (below, at the list).
+#define TPW_STRIDE 80u
+#define TPW_LIST 512u
+#define TPW_TURN (64u * TPK_PER)       // positions a wave goes through per turn: 64 per lane
+#define TPW_CHUNKS 65u                 // ... and their bytes in LDS: a stretch of 64 per lane and the 64 behind them
+// four codes at bytes q .. q + 3 of a stretch with `left` bytes in front of the end of the text: all ones where the byte is inside
+__device__ __forceinline__ u32 tpw_left_mask(u32 left, u32 q) {
+    return left >= q + 4 ? 0xffffffffu : left > q ? (1u << (8 * (left - q))) - 1u : 0u;
+}
+// LDS written by lanes of a wave is read by other lanes of the same wave behind this
+__device__ __forceinline__ void tpw_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <int S>
+__global__ __launch_bounds__(TPK_NT) void tied_probe_w_kernel(const u8 *__restrict__ text, u32 n, RadixKeyGen kg,
+                                                              TiedTable T, u32 *__restrict__ out_slot,
+                                                              u32 *__restrict__ out_idx, u32 *__restrict__ out_grp,
+                                                              u32 *total, u32 cap) {
+    constexpr u32 h = 7 * S;                       // symbols per key
+    constexpr int NX = (h + 15) / 16;              // 16-byte units of the next thread's bytes in the window
+    constexpr int WD = 16 + 4 * NX;                // dwords of the window
+    static_assert(h <= 56 && NX <= 4, "the window is a thread's 4 units + at most 4 of the next thread's");
+    __shared__ u32 s_bloom[(1u << TP_BLOOM_LOG2) / 32];
+    __shared__ uint4 s_raw[(TPK_NT / 64) * TPW_CHUNKS * (TPW_STRIDE / 16)];
+    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u32 B = kg.B;
+    for (u32 i = tid; i < (1u << TP_BLOOM_LOG2) / 32; i += TPK_NT) s_bloom[i] = T.bloom[i];
+    __syncthreads();   // (the only barrier of the workgroup: from here on every wave is on its own)
+    uint4 *wraw = s_raw + (tid >> 6) * TPW_CHUNKS * (TPW_STRIDE / 16);   // this wave's 64 + 1 stretches of 64 bytes
+    const u32 nturns = n / TPW_TURN + (n % TPW_TURN != 0);
+    const u32 gwave = blockIdx.x * (TPK_NT / 64) + (tid >> 6), gwaves = gridDim.x * (TPK_NT / 64);
+    // (the one-turn-ahead fetch: tied_probe_kernel's, per wave -- a lane's units are 1 KiB apart, a load is 1 KiB)
+    constexpr int NU = (TPW_TURN + 64 + 64 * 16 - 1) / (64 * 16);
+    uint4 raw[NU];
+    auto unit_ok = [&](u32 base, int i) -> bool {
+        const u32 p = ((u32)i * 64 + lane) * 16;
+        const u64 g = (u64)base + p;
+        return p < TPW_TURN + 64 && g + 16 <= n && ((((uintptr_t)text) + g) & 15) == 0;
+    };
+    auto fetch = [&](u32 base) {
+#pragma unroll
+        for (int i = 0; i < NU; i++) {
+            raw[i] = make_uint4(0, 0, 0, 0);
+            if (unit_ok(base, i)) raw[i] = *reinterpret_cast<const uint4 *>(text + (u64)base + ((u32)i * 64 + lane) * 16);
+        }
+    };
+    if (gwave < nturns) fetch(gwave * TPW_TURN);
+    for (u32 turn = gwave; turn < nturns; turn += gwaves) {
+        const u32 base = turn * TPW_TURN;
+        tpw_wave_sync();   // (the previous turn's bytes have been read)
+#pragma unroll
+        for (int i = 0; i < NU; i++) {
+            const u32 u = (u32)i * 64 + lane;   // unit of the turn: bytes 16 u ..
+            if (u >= (TPW_TURN + 64) / 16) continue;
+            uint4 x = raw[i];
+            if (!unit_ok(base, i)) {
+                const u64 g = (u64)base + u * 16;
+                u32 d[4] = {0, 0, 0, 0};
+                for (int j = 0; j < 16; j++)
+                    if (g + j < n) d[j >> 2] |= (u32)text[g + j] << (8 * (j & 3));
+                x = make_uint4(d[0], d[1], d[2], d[3]);
+            }
+            wraw[(u >> 2) * (TPW_STRIDE / 16) + (u & 3u)] = x;
+        }
+        if (turn + gwaves < nturns) fetch((turn + gwaves) * TPW_TURN);
+        tpw_wave_sync();
+        const u32 p0 = lane * TPK_PER;
+        u64 hits = 0;
+        if (p0 < n - base) {
+            u32 W[WD];
+#pragma unroll
+            for (int i = 0; i < 4 + NX; i++) {
+                const uint4 x = wraw[(lane + (i >> 2)) * (TPW_STRIDE / 16) + (i & 3)];
+                W[4 * i + 0] = x.x; W[4 * i + 1] = x.y; W[4 * i + 2] = x.z; W[4 * i + 3] = x.w;
+            }
+#pragma unroll
+            for (int i = 0; i < WD; i++) W[i] = __builtin_amdgcn_perm(kg.thi, kg.tlo, (W[i] >> kg.hsh) & 0x07070707u);
+            const u32 left = n - base - p0;   // > 0
+            if (n - base < TPW_TURN + 64) {   // (wave-uniform) the window may reach the end of the text
+#pragma unroll
+                for (int i = 0; i < WD; i++) W[i] &= tpw_left_mask(left, 4u * (u32)i);
+            }
+            auto code = [&](int x) -> u32 { return (W[x >> 2] >> (8 * (x & 3))) & 255u; };
+            u32 H = 0;
+#pragma unroll
+            for (int j = 0; j < (int)h; j++) H = tp_rotl(H, 1) ^ tp_sym(code(j));
+#pragma unroll
+            for (int j = 0; j < TPK_PER; j++) {
+                const u32 hb = H >> (32 - TP_BLOOM_LOG2);
+                hits |= (u64)((s_bloom[hb >> 5] >> (hb & 31)) & 1u) << j;
+                H = tp_rotl(H, 1) ^ tp_rotl(tp_sym(code(j)), h & 31u) ^ tp_sym(code(j + (int)h));
+            }
+            if (left < TPK_PER) hits &= (1ull << left) - 1ull;   // (no position at or beyond n)
+        }
+        // The exact value of the h symbols at the positions that passed the filter, and the table.  A few thousand
+        // tied keys' filter lets through about one position in a hundred: 0.6 per thread and tile, but three or four
+        // for some lane of every wave, and a wave that goes through its lanes' own positions takes that many turns,
+        // each an LDS round trip and a load from the table.  So the wave's positions go through a list and are dealt
+        // out one per lane: a turn per 64 positions of the wave.  The list is the wave's own 64 gaps of 16 bytes
+        // behind its threads' raw bytes (TPW_LIST entries of 16 bits); it is filled by rounds of one position per
+        // lane that has any left, placed by ballot and lane count, until a round might not fit -- a wave with more
+        // positions than that deals out and fills again.  Only this wave writes and reads its list, between two
+        // barriers of the workgroup.
+        {
+            u16 *lst = reinterpret_cast<u16 *>(wraw) + 32;
+            auto lst_at = [&](u32 e) -> u16 & { return lst[(e >> 3) * (TPW_STRIDE / 2) + (e & 7u)]; };
+            const u32 *rw = reinterpret_cast<const u32 *>(wraw);
+            while (__ballot(hits != 0)) {   // (wave-uniform)
+                u32 cnt = 0;
+                while (cnt + 64 <= TPW_LIST) {
+                    const u64 b = __ballot(hits != 0);
+                    if (!b) break;
+                    if (hits) {
+                        const u32 e = cnt + __builtin_amdgcn_mbcnt_hi((u32)(b >> 32), __builtin_amdgcn_mbcnt_lo((u32)b, 0u));
+                        lst_at(e) = (u16)(p0 + (u32)__builtin_ctzll(hits));
+                        hits &= hits - 1;
+                    }
+                    cnt += (u32)__popcll(b);
+                }
+                tpw_wave_sync();
+                for (u32 k = lane; k < cnt; k += 64) {
+                    const u32 q = lst_at(k);        // position in the turn
+                    const u32 pos = base + q;       // < n
+                    // its h bytes from LDS as whole dwords (one round trip), shifted into place, then codes
+                    constexpr int ND = (h + 3) / 4;
+                    u32 w[ND + 1];
+#pragma unroll
+                    for (int i = 0; i <= ND; i++) {
+                        const u32 lq = (q & ~3u) + 4u * (u32)i;
+                        w[i] = rw[(lq + (lq >> 6) * (TPW_STRIDE - 64u)) >> 2];
+                    }
+                    u64 v = 0;   // (four symbols at a time: B^4 fits 32 bits, and the 64-bit multiply is the slow one)
+#pragma unroll
+                    for (int i = 0; i < ND; i++) {
+                        u32 d = __builtin_amdgcn_alignbit(w[i + 1], w[i], 8u * (q & 3u));
+                        d = __builtin_amdgcn_perm(kg.thi, kg.tlo, (d >> kg.hsh) & 0x07070707u) & tpw_left_mask(n - pos, 4u * (u32)i);
+                        u32 D = 0, mult = 1;
+#pragma unroll
+                        for (int x = 4 * i; x < 4 * i + 4 && x < (int)h; x++) {
+                            D = D * B + ((d >> (8 * (x & 3))) & 255u);
+                            mult *= B;
+                        }
+                        v = v * mult + D;
+                    }
+                    u32 slot = (u32)(tp_mix(v) >> (64 - TP_SLOT_BITS));
+                    for (u32 probe = 0; probe < (1u << TP_SLOT_BITS); probe++) {
+                        const u64 kk = T.key[slot];
+                        if (kk == v) {
+                            const u32 jj = atomicAdd(&T.cnt[slot], 1u);
+                            const u32 o = atomicAdd(total, 1u);
+                            if (o < cap) {
+                                const u32 g0 = T.grp[slot];
+                                out_slot[o] = g0 + jj;
+                                out_idx[o] = pos;
+                                out_grp[o] = g0;
+                            }
+                            break;
+                        }
+                        if (kk == 0ull) break;
+                        slot = (slot + 1) & ((1u << TP_SLOT_BITS) - 1u);
+                    }
+                }
+                tpw_wave_sync();
+            }
+        }
+    }
+}
+
 // active set arrives unordered from finish_kernel; refine needs it in SA order:
 // key = slot << 32 | grp, value = idx, sorted by the slot bits
 __global__ __launch_bounds__(256) void pack_active_kernel(const u32 *__restrict__ slot,

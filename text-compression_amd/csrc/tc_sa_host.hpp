@@ -818,7 +818,7 @@ static Round0Out sa_round0_msd(SaRun &R, const Round0Plan &pl, bool keyonly) {
 }
 
 // Key-only levels: the fm tied members in act[0] are known by slot, group and key; finds their suffix starts again by one
-// pass over the text (tied_table_kernel, tied_probe_kernel: tc_sa.hpp) and leaves them in act[0][1].  False: more ties
+// pass over the text (tied_table_kernel, tied_probe_kernel or tied_probe_w_kernel: tc_sa.hpp) and leaves them in act[0][1].  False: more ties
 // than the table is made for, whole buckets, or a pass that did not find exactly fm positions.
 static bool sa_keyonly_recover(SaRun &R, u32 fm, u32 flags) {
     tc_ctx *ctx = R.ctx;
@@ -836,11 +836,17 @@ static bool sa_keyonly_recover(SaRun &R, u32 fm, u32 flags) {
         tc_memset_async(ctx, d_total, 0, sizeof(u64));
         tied_table_kernel<<<tc_cdiv(fm, 256), 256, 0, s>>>(b.act[0][1], b.act[0][3], b.act[0][2], fm, cfg.B, cfg.s, cfg.P, b.tp);
         TC_LAUNCH_CHECK(ctx);
-        const RadixKeyGen kgp = sa_keygen(R);
+        RadixKeyGen kgp = sa_keygen(R);
+        radix_keygen_hash(kgp);
+        // codes from the register table where the alphabet has one (tied_probe_w_kernel), else through the byte image
+        const bool wide = kgp.hash_ok != 0 && R.K.keygen_hash != 0 && cfg.B <= 8 && R.K.tied_probe != 0;
         u32 pgrid = (u32)ctx->num_cus * 3;
         if (pgrid > tc_cdiv(n, TPK_TILE)) pgrid = tc_cdiv(n, TPK_TILE);
         switch (cfg.s) {   // (symbols per field: B^s <= 256)
-#define TC_PROBE(S) case S: tied_probe_kernel<S><<<pgrid, TPK_NT, 0, s>>>(R.text, n, kgp, b.tp, b.act[0][0], b.act[0][1], b.act[0][2], d_total, fm); break;
+#define TC_PROBE(S) case S: \
+            if (wide) tied_probe_w_kernel<S><<<pgrid, TPK_NT, 0, s>>>(R.text, n, kgp, b.tp, b.act[0][0], b.act[0][1], b.act[0][2], d_total, fm); \
+            else tied_probe_kernel<S><<<pgrid, TPK_NT, 0, s>>>(R.text, n, kgp, b.tp, b.act[0][0], b.act[0][1], b.act[0][2], d_total, fm); \
+            break;
             TC_PROBE(1) TC_PROBE(2) TC_PROBE(3) TC_PROBE(4) TC_PROBE(5) TC_PROBE(6) TC_PROBE(7) TC_PROBE(8)
 #undef TC_PROBE
             default: TC_FAIL(ctx, TC_ERR_INTERNAL, "key-only levels: %u symbols per field", cfg.s);
@@ -848,7 +854,9 @@ static bool sa_keyonly_recover(SaRun &R, u32 fm, u32 flags) {
         TC_LAUNCH_CHECK(ctx);
         tc_d2h(ctx, &ctx->h_scalars[SA_SLOT_PROBE], ctx->d_scalars + SA_SLOT_PROBE, sizeof(u64));
         TC_HIP(ctx, hipStreamSynchronize(s));
-        ok = sa_slot_lo(ctx, SA_SLOT_PROBE) == fm;
+        ctx->tied_probe_used = wide ? 2 : 1;
+        ctx->tied_probe_found = sa_slot_lo(ctx, SA_SLOT_PROBE);
+        ok = ctx->tied_probe_found == fm;
     }
     if (R.K.trace)
         fprintf(stderr, "textcomp: key-only levels: %u tied suffixes %s (the pass over the text met %u)\n", fm,
@@ -1335,6 +1343,8 @@ static void sa_run(tc_ctx *ctx, SaBuffers &b, const u8 *d_text, u64 n, u32 *d_sa
     sa_trace_buffers(R);
     ctx->msd_split_used = 0;
     ctx->msd_dir_used = 0;
+    ctx->tied_probe_used = 0;
+    ctx->tied_probe_found = 0;
     if (sa_alphabet(R, counts256_out, primary)) return;
 
     const u32 P_full = R.cfg.P;   // fields chosen for the full path (every field is a pass there)

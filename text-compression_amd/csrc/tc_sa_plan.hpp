@@ -31,6 +31,7 @@ struct SaKnobs {
     int msd_joint = env_int("TC_SA_MSD_JOINT", 1);   // 0 = level 3 counts its own digits instead of taking them from level 2
     int msd_split = env_int("TC_MSD_SPLIT", 1);   // 0 = level 1 of the key-only levels writes 64-bit keys instead of two arrays of halves (and the joint count reads all 8 bytes)
     int msd_dir = env_int("TC_MSD_DIR", 1);   // 0 = the aligned level walks the parent tables at every boundary instead of keeping a directory of its live parents in LDS
+    int tied_probe = env_int("TC_TIED_PROBE", 1);   // 0 = the tied suffixes of the key-only levels are always found again through the byte image of codes (tied_probe_kernel), never by codes from the register table (tied_probe_w_kernel)
     int msd_finish_lut = env_int("TC_MSD_FINISH_LUT", 1);   // 0 = the finish bins by key bits instead of equal-mass intervals
     int msd_finish_ko = env_int("TC_MSD_FINISH_KO", 1);   // 0 = the generic finish instance for the key-only levels
     int tier2 = env_int("TC_SA_TIER2", 1);   // 0 = no fix pass for over-long buckets of the LSD finish (the full path then)

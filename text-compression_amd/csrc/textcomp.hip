@@ -857,6 +857,13 @@ int tc_dbg_msd_dir(tc_ctx *ctx, uint32_t out[2]) {
     TC_API_END(ctx)
 }
 
+int tc_dbg_tied_probe(tc_ctx *ctx, uint32_t out[2]) {
+    if (!ctx || !out) return TC_ERR_ARG;
+    out[0] = (uint32_t)ctx->tied_probe_used;
+    out[1] = ctx->tied_probe_found;
+    return TC_OK;
+}
+
 int tc_dbg_ibwt_walk(tc_ctx *ctx, uint32_t out[3]) {
     if (!ctx || !out) return TC_ERR_ARG;
     out[0] = ctx->ibwt_attempts;
