@@ -236,6 +236,34 @@ int tc_repeats(tc_ctx *ctx, const uint8_t *text, uint64_t n, int kind, uint32_t 
                uint32_t *sa, uint32_t *rep_pos, uint32_t *rep_len, uint32_t *rep_occ, uint32_t *rep_row, uint64_t *nrep);
 int tc_repeats_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, int kind, uint32_t min_len, uint32_t min_occ,
                    uint32_t *d_sa, uint32_t *d_rep_pos, uint32_t *d_rep_len, uint32_t *d_rep_occ, uint32_t *d_rep_row, uint64_t *nrep);
+/* ---- tandem repeats: the runs (maximal repetitions) of a text (not part of the reference's surface) ----
+ * A RUN of text[0..n) is a triple (start s, end e, period p), with p >= 1 and 0 <= s <= e < n, such that all of these hold:
+ *   - text[k] = text[k+p] for every s <= k <= e - p;
+ *   - e - s + 1 >= 2p;
+ *   - p is the smallest period of text[s..e];
+ *   - the run extends neither way: s = 0 or text[s-1] != text[s+p-1], and e = n - 1 or text[e+1] != text[e+1-p].
+ * The ends of the text match nothing.  "mississippi" has the runs (1,7,3), (2,3,1), (5,6,1), (8,9,1); "aabaabaab" has
+ * (0,1,1), (0,8,3), (3,4,1), (6,7,1); a unary text of n >= 2 bytes has the single run (0, n-1, 1).  A text of n bytes has
+ * fewer than n runs (the runs theorem), so capacity n is always enough.
+ * OUTPUT: three arrays run_start = s, run_len = e - s + 1 and run_period = p, in increasing start and, for equal starts,
+ * increasing period.  The order depends on the text only, not on the method, and is the same on every call.
+ * FILTERS: a run is reported if it passes all four: run_period >= min_period (>= 1); run_period <= max_period, where 0
+ * means no limit and any other value must be >= min_period; run_len / run_period, rounded down, >= min_copies (>= 2);
+ * run_len >= min_len (>= 1).  Anything else: TC_ERR_ARG.
+ * *nrun: in = capacity of the three arrays, out = the count.  Too small: TC_ERR_CAPACITY, *nrun = the needed count, nothing
+ * written to the three arrays.  run_start = run_len = run_period = NULL with capacity 0 is the sizes-only form: TC_OK, the
+ * count written.
+ * ERRORS AND EDGES.  Null buffers or n > TC_MAX_N: TC_ERR_ARG.  n = 0: TC_OK, 0 runs, nothing read.  The calls take the
+ * text only: the enhanced suffix arrays of the text and of its reverse and all scratch (66 bytes per text byte behind the
+ * two sorts: the two texts 2, one suffix array 4, two inverse suffix arrays, one complement and two LCP arrays 20, the
+ * candidate words 24, the per-start counts and segment starts 16; the sort's own need behind the first 26 where that is
+ * larger) live in the calling ctx's workspace.  The _dev form takes every array in HBM; nrun stays a host word. */
+int tc_tandem_repeats(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_period, uint32_t max_period,
+                      uint32_t min_copies, uint32_t min_len, uint32_t *run_start, uint32_t *run_len, uint32_t *run_period,
+                      uint64_t *nrun);
+int tc_tandem_repeats_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_period, uint32_t max_period,
+                          uint32_t min_copies, uint32_t min_len, uint32_t *d_run_start, uint32_t *d_run_len,
+                          uint32_t *d_run_period, uint64_t *nrun);
 /* ---- the k-mers of a text: list, abundance spectrum and all-k profile (not part of the reference's surface) ----
  * N = n + 1 rows; sa and lcp as tc_lcp_array defines them (row 0 is the empty suffix, the end of the text matches
  * nothing); lcp[0] counts as 0 whatever the array holds, and lcp[N] as 0.  For k >= 1 row q is a BOUNDARY iff lcp[q] < k;

@@ -11,6 +11,7 @@
 #include "tc_rep_host.hpp"
 #include "tc_kmer_host.hpp"
 #include "tc_tm_host.hpp"
+#include "tc_tr_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -226,6 +227,22 @@ int tc_repeats_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, int kind, uin
                    uint32_t *d_rep_pos, uint32_t *d_rep_len, uint32_t *d_rep_occ, uint32_t *d_rep_row, uint64_t *nrep) {
     TC_API_BEGIN(ctx)
     repeats_entry(ctx, d_text, n, kind, min_len, min_occ, d_sa, d_rep_pos, d_rep_len, d_rep_occ, d_rep_row, nrep, true);
+    TC_API_END(ctx)
+}
+
+// the runs (tandem repeats) of a text (no counterpart in the reference): tc_tr_host.hpp
+int tc_tandem_repeats(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_period, uint32_t max_period, uint32_t min_copies,
+                      uint32_t min_len, uint32_t *run_start, uint32_t *run_len, uint32_t *run_period, uint64_t *nrun) {
+    TC_API_BEGIN(ctx)
+    tandem_repeats_entry(ctx, text, n, min_period, max_period, min_copies, min_len, run_start, run_len, run_period, nrun, false);
+    TC_API_END(ctx)
+}
+
+int tc_tandem_repeats_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_period, uint32_t max_period,
+                          uint32_t min_copies, uint32_t min_len, uint32_t *d_run_start, uint32_t *d_run_len, uint32_t *d_run_period,
+                          uint64_t *nrun) {
+    TC_API_BEGIN(ctx)
+    tandem_repeats_entry(ctx, d_text, n, min_period, max_period, min_copies, min_len, d_run_start, d_run_len, d_run_period, nrun, true);
     TC_API_END(ctx)
 }
 

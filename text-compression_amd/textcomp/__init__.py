@@ -372,6 +372,53 @@ class Context:
         res = tuple(o[:int(nrep.value)] for o in out)
         return res + (d_sa,) if with_sa else res
 
+    # ------------------------------------- tandem repeats: the runs (maximal repetitions) of a text
+    def tandem_repeat_count(self, text, min_period=1, max_period=0, min_copies=2, min_len=1):
+        """the number of runs of text that pass the four filters (the sizes-only form of tc_tandem_repeats)"""
+        t = _u8(text)
+        nrun = C.c_uint64(0)
+        self._check(self._lib.tc_tandem_repeats(self._h, _ptr(t) if len(t) else None, len(t), min_period, max_period, min_copies,
+                                                min_len, None, None, None, C.byref(nrun)))
+        return int(nrun.value)
+
+    def tandem_repeats(self, text, min_period=1, max_period=0, min_copies=2, min_len=1):
+        """the runs of text -> (start, len, period), uint32 arrays: run k is text[start[k] : start[k] + len[k]], whose
+        smallest period is period[k] and which extends neither way; by increasing start, then period.  max_period = 0: no
+        limit; a run passes with len // period >= min_copies: tc_tandem_repeats"""
+        t = _u8(text)
+        cap = max(self.tandem_repeat_count(t, min_period, max_period, min_copies, min_len), 1)
+        start, ln, period = (np.empty(cap, np.uint32) for _ in range(3))
+        nrun = C.c_uint64(cap)
+        self._check(self._lib.tc_tandem_repeats(self._h, _ptr(t) if len(t) else None, len(t), min_period, max_period, min_copies,
+                                                min_len, _ptr(start), _ptr(ln), _ptr(period), C.byref(nrun)))
+        k = int(nrun.value)
+        return start[:k].copy(), ln[:k].copy(), period[:k].copy()
+
+    def tandem_repeats_dev(self, d_text, min_period=1, max_period=0, min_copies=2, min_len=1, cap=None):
+        """text resident in HBM -> (start, len, period), int32 tensors on the device: tc_tandem_repeats_dev.  cap: the run
+        slots to try first (None: the sizes-only form runs first)"""
+        import torch
+        n = d_text.numel()
+        pt = C.c_void_p(d_text.data_ptr()) if n else None
+        torch.cuda.synchronize()
+        if cap is None:
+            nrun = C.c_uint64(0)
+            self._check(self._lib.tc_tandem_repeats_dev(self._h, pt, n, min_period, max_period, min_copies, min_len, None, None, None,
+                                                        C.byref(nrun)))
+            cap = int(nrun.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            out = [torch.empty(cap, dtype=torch.int32, device=d_text.device) for _ in range(3)]
+            torch.cuda.synchronize()
+            nrun = C.c_uint64(cap)
+            rc = self._lib.tc_tandem_repeats_dev(self._h, pt, n, min_period, max_period, min_copies, min_len,
+                                                 *(C.c_void_p(o.data_ptr()) for o in out), C.byref(nrun))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nrun.value), 1)
+        self._check(rc)
+        return tuple(o[:int(nrun.value)] for o in out)
+
     # ------------------------------------- the k-mers of a text: list, abundance spectrum, all-k profile
     def kmer_count(self, text, k, min_occ=1, max_occ=0):
         """how many distinct k-mers of text occur at least min_occ and (max_occ > 0) at most max_occ times: the

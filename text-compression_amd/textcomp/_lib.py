@@ -84,6 +84,8 @@ SYMBOLS = [
     ("tc_lz_unparse_dev", _INT, [_P, _P, _P, _U64, _P, _PU64]),
     ("tc_repeats", _INT, [_P, _P, _U64, _INT, _U32, _U32, _P, _P, _P, _P, _P, _PU64]),
     ("tc_repeats_dev", _INT, [_P, _P, _U64, _INT, _U32, _U32, _P, _P, _P, _P, _P, _PU64]),
+    ("tc_tandem_repeats", _INT, [_P, _P, _U64, _U32, _U32, _U32, _U32, _P, _P, _P, _PU64]),
+    ("tc_tandem_repeats_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _U32, _P, _P, _P, _PU64]),
     ("tc_kmers", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_esa_dev", _INT, [_P, _P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _PU64]),
