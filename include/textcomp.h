@@ -264,6 +264,46 @@ int tc_tandem_repeats(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min
 int tc_tandem_repeats_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_period, uint32_t max_period,
                           uint32_t min_copies, uint32_t min_len, uint32_t *d_run_start, uint32_t *d_run_len,
                           uint32_t *d_run_period, uint64_t *nrun);
+/* ---- palindromes and inverted repeats of a text, with mismatches (not part of the reference's surface) ----
+ * sigma is a byte map that is an involution: sigma(sigma(x)) = x for all 256 bytes.  comp is a HOST pointer to its 256
+ * bytes, or NULL for the identity; it is a host pointer in the _dev forms too, like the scalar filters.  Under the identity
+ * the calls find the palindromes of the text, under the DNA complement (A<->T, C<->G) its inverted repeats: the stretches
+ * that equal their own reverse complement.
+ * text[s .. s+len) is a SIGMA-PALINDROME with mm mismatches when mm = |{k : 0 <= k < ceil(len/2), text[s+k] !=
+ * sigma(text[s+len-1-k])}|.  The middle byte of an odd length counts as a pair with itself: under the DNA complement it
+ * is always a mismatch, under the identity it never is.  Its CENTRE is c = 2s + len - 1, which lies in 0 .. 2n-2.
+ * For a budget max_mismatch = m the calls report, for every centre, the LONGEST palindrome there that meets all three:
+ * mm <= m; its outermost pair matches (a palindrome never ends on a mismatch); len >= min_len.  That is at most one
+ * palindrome per centre, so fewer than 2n in all: capacity 2n - 1 is always enough.
+ * "mississippi" under the identity with m = 0 and min_len = 3: (1,4,0) issi, (1,7,0) ississi, (4,4,0) issi, (7,4,0) ippi
+ * -- sis and ssiss share the centre of ississi and are not reported; with min_len = 1 the ten single bytes that are no
+ * longer palindrome's centre join them.  "ACGT" under the DNA complement: (0,4,0) alone -- CG shares its centre.  "ACAGT"
+ * under the DNA complement: nothing at m = 0; (0,5,1) and (2,3,1) at m = 1 -- AGT, like every odd length, spends one
+ * mismatch on its middle byte.
+ * OUTPUT: three arrays pal_start = s, pal_len = len and pal_mm = mm, in increasing centre.  pal_mm alone may be NULL in any
+ * call; it is then not written.
+ * *npal: in = capacity of the arrays, out = the count.  Too small: TC_ERR_CAPACITY, *npal = the needed count, nothing
+ * written to the arrays.  pal_start = pal_len = pal_mm = NULL with capacity 0 is the sizes-only form: TC_OK, the count
+ * written.
+ * tc_longest_palindrome: the longest palindrome under the same rule (min_len = 1), of equal lengths the one with the
+ * smallest centre, into three host words in both forms.  len = 0 when there is none: n = 0, or a sigma without a fixed
+ * point and a text without a matching pair.
+ * ERRORS AND EDGES.  TC_ERR_ARG, before a buffer is touched, for: a null npal; a null required buffer; min_len = 0;
+ * max_mismatch > TC_PAL_MAX_MISMATCH; 2n > TC_MAX_N; a comp with comp[comp[x]] != x for some x.  n = 0: TC_OK, nothing
+ * read, 0 palindromes.  The calls take the text only: the joint text S = text . sigma(reverse(text)) of 2n bytes, its
+ * enhanced suffix array and all scratch (42 bytes per text byte behind the sort: S 2, its suffix array, inverse suffix
+ * array and LCP array 24, the packed centre words 16; the sort's own need behind the first 26 where that is larger) live
+ * in the calling ctx's workspace.  The _dev forms take the text and the arrays in HBM; comp, npal and the three words of
+ * tc_longest_palindrome stay in host memory. */
+#define TC_PAL_MAX_MISMATCH 16
+int tc_palindromes(tc_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_t *comp, uint32_t max_mismatch, uint32_t min_len,
+                   uint32_t *pal_start, uint32_t *pal_len, uint32_t *pal_mm, uint64_t *npal);
+int tc_palindromes_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uint8_t *comp, uint32_t max_mismatch,
+                       uint32_t min_len, uint32_t *d_pal_start, uint32_t *d_pal_len, uint32_t *d_pal_mm, uint64_t *npal);
+int tc_longest_palindrome(tc_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_t *comp, uint32_t max_mismatch,
+                          uint32_t *start, uint32_t *len, uint32_t *mm);
+int tc_longest_palindrome_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uint8_t *comp, uint32_t max_mismatch,
+                              uint32_t *start, uint32_t *len, uint32_t *mm);
 /* ---- the k-mers of a text: list, abundance spectrum and all-k profile (not part of the reference's surface) ----
  * N = n + 1 rows; sa and lcp as tc_lcp_array defines them (row 0 is the empty suffix, the end of the text matches
  * nothing); lcp[0] counts as 0 whatever the array holds, and lcp[N] as 0.  For k >= 1 row q is a BOUNDARY iff lcp[q] < k;

@@ -12,6 +12,7 @@
 #include "tc_kmer_host.hpp"
 #include "tc_tm_host.hpp"
 #include "tc_tr_host.hpp"
+#include "tc_pal_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -243,6 +244,35 @@ int tc_tandem_repeats_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32
                           uint64_t *nrun) {
     TC_API_BEGIN(ctx)
     tandem_repeats_entry(ctx, d_text, n, min_period, max_period, min_copies, min_len, d_run_start, d_run_len, d_run_period, nrun, true);
+    TC_API_END(ctx)
+}
+
+// the palindromes and inverted repeats of a text, with mismatches (no counterpart in the reference): tc_pal_host.hpp
+int tc_palindromes(tc_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_t *comp, uint32_t max_mismatch, uint32_t min_len,
+                   uint32_t *pal_start, uint32_t *pal_len, uint32_t *pal_mm, uint64_t *npal) {
+    TC_API_BEGIN(ctx)
+    palindromes_entry(ctx, text, n, comp, max_mismatch, min_len, pal_start, pal_len, pal_mm, npal, false);
+    TC_API_END(ctx)
+}
+
+int tc_palindromes_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uint8_t *comp, uint32_t max_mismatch, uint32_t min_len,
+                       uint32_t *d_pal_start, uint32_t *d_pal_len, uint32_t *d_pal_mm, uint64_t *npal) {
+    TC_API_BEGIN(ctx)
+    palindromes_entry(ctx, d_text, n, comp, max_mismatch, min_len, d_pal_start, d_pal_len, d_pal_mm, npal, true);
+    TC_API_END(ctx)
+}
+
+int tc_longest_palindrome(tc_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_t *comp, uint32_t max_mismatch, uint32_t *start,
+                          uint32_t *len, uint32_t *mm) {
+    TC_API_BEGIN(ctx)
+    longest_palindrome_entry(ctx, text, n, comp, max_mismatch, start, len, mm, false);
+    TC_API_END(ctx)
+}
+
+int tc_longest_palindrome_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uint8_t *comp, uint32_t max_mismatch,
+                              uint32_t *start, uint32_t *len, uint32_t *mm) {
+    TC_API_BEGIN(ctx)
+    longest_palindrome_entry(ctx, d_text, n, comp, max_mismatch, start, len, mm, true);
     TC_API_END(ctx)
 }
 

@@ -39,6 +39,28 @@ def _u8(b):
     return np.frombuffer(bytes(b), dtype=np.uint8)
 
 
+def _dna_complement():
+    t = np.arange(256, dtype=np.uint8)
+    for a, b in (b"AT", b"CG", b"at", b"cg"):
+        t[a], t[b] = b, a
+    t.setflags(write=False)
+    return t
+
+
+# the comp of the palindrome calls under which they find inverted repeats: A<->T, C<->G, a<->t, c<->g, everything else fixed
+DNA_COMPLEMENT = _dna_complement()
+
+
+def _comp(comp):
+    """a byte involution as the 256-byte host table the palindrome calls take (None: the identity, a null pointer)"""
+    if comp is None:
+        return None
+    t = _u8(comp)
+    if len(t) != 256:
+        raise ValueError("comp holds 256 bytes, not %d" % len(t))
+    return t
+
+
 class Context:
     """One device + stream + workspace (`tc_ctx`)."""
 
@@ -418,6 +440,73 @@ class Context:
             cap = max(int(nrun.value), 1)
         self._check(rc)
         return tuple(o[:int(nrun.value)] for o in out)
+
+    # ------------------------------------- palindromes and inverted repeats of a text, with mismatches
+    def palindrome_count(self, text, comp=None, max_mismatch=0, min_len=1):
+        """the number of palindromes of text under comp that tc_palindromes reports (its sizes-only form)"""
+        t, c = _u8(text), _comp(comp)
+        npal = C.c_uint64(0)
+        self._check(self._lib.tc_palindromes(self._h, _ptr(t) if len(t) else None, len(t), _ptr(c), max_mismatch, min_len, None, None,
+                                             None, C.byref(npal)))
+        return int(npal.value)
+
+    def palindromes(self, text, comp=None, max_mismatch=0, min_len=1):
+        """for every centre the longest palindrome of text under the byte involution comp (None: the identity;
+        DNA_COMPLEMENT: inverted repeats) with at most max_mismatch mismatching pairs, a matching outermost pair and at least
+        min_len bytes -> (start, len, mm), uint32 arrays by increasing centre 2 start + len - 1: tc_palindromes"""
+        t, c = _u8(text), _comp(comp)
+        cap = max(self.palindrome_count(t, c, max_mismatch, min_len), 1)
+        start, ln, mm = (np.empty(cap, np.uint32) for _ in range(3))
+        npal = C.c_uint64(cap)
+        self._check(self._lib.tc_palindromes(self._h, _ptr(t) if len(t) else None, len(t), _ptr(c), max_mismatch, min_len, _ptr(start),
+                                             _ptr(ln), _ptr(mm), C.byref(npal)))
+        k = int(npal.value)
+        return start[:k].copy(), ln[:k].copy(), mm[:k].copy()
+
+    def palindromes_dev(self, d_text, comp=None, max_mismatch=0, min_len=1, cap=None):
+        """text resident in HBM -> (start, len, mm), int32 tensors on the device: tc_palindromes_dev.  comp stays a host
+        table; cap: the slots to try first (None: the sizes-only form runs first)"""
+        import torch
+        n = d_text.numel()
+        c = _comp(comp)
+        pt = C.c_void_p(d_text.data_ptr()) if n else None
+        torch.cuda.synchronize()
+        if cap is None:
+            npal = C.c_uint64(0)
+            self._check(self._lib.tc_palindromes_dev(self._h, pt, n, _ptr(c), max_mismatch, min_len, None, None, None, C.byref(npal)))
+            cap = int(npal.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            out = [torch.empty(cap, dtype=torch.int32, device=d_text.device) for _ in range(3)]
+            torch.cuda.synchronize()
+            npal = C.c_uint64(cap)
+            rc = self._lib.tc_palindromes_dev(self._h, pt, n, _ptr(c), max_mismatch, min_len, *(C.c_void_p(o.data_ptr()) for o in out),
+                                              C.byref(npal))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(npal.value), 1)
+        self._check(rc)
+        return tuple(o[:int(npal.value)] for o in out)
+
+    def longest_palindrome(self, text, comp=None, max_mismatch=0):
+        """(start, len, mm) of the longest palindrome of text under comp, of equal lengths the one with the smallest centre;
+        len = 0 when there is none: tc_longest_palindrome"""
+        t, c = _u8(text), _comp(comp)
+        start, ln, mm = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.tc_longest_palindrome(self._h, _ptr(t) if len(t) else None, len(t), _ptr(c), max_mismatch,
+                                                    C.byref(start), C.byref(ln), C.byref(mm)))
+        return int(start.value), int(ln.value), int(mm.value)
+
+    def longest_palindrome_dev(self, d_text, comp=None, max_mismatch=0):
+        """text resident in HBM -> (start, len, mm), host integers: tc_longest_palindrome_dev"""
+        import torch
+        n = d_text.numel()
+        c = _comp(comp)
+        torch.cuda.synchronize()
+        start, ln, mm = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.tc_longest_palindrome_dev(self._h, C.c_void_p(d_text.data_ptr()) if n else None, n, _ptr(c), max_mismatch,
+                                                        C.byref(start), C.byref(ln), C.byref(mm)))
+        return int(start.value), int(ln.value), int(mm.value)
 
     # ------------------------------------- the k-mers of a text: list, abundance spectrum, all-k profile
     def kmer_count(self, text, k, min_occ=1, max_occ=0):

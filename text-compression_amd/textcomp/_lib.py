@@ -18,6 +18,7 @@ TC_FM_MAX_SA_RATE = 4096
 TC_FM_MAX_MISMATCH = 3
 TC_MAX_N = 0x7ffffff0
 TC_REPEAT_MAXIMAL, TC_REPEAT_SUPERMAXIMAL = 0, 1
+TC_PAL_MAX_MISMATCH = 16
 TC_LCP_SHORT_CAP = 256   # csrc/tc_lcp.hpp: comparisons of the LCP array longer than this leave the one-lane kernel
 
 ERR_NAMES = {-1: "TC_ERR_ARG", -2: "TC_ERR_CAPACITY", -3: "TC_ERR_MALFORMED", -4: "TC_ERR_HIP",
@@ -86,6 +87,10 @@ SYMBOLS = [
     ("tc_repeats_dev", _INT, [_P, _P, _U64, _INT, _U32, _U32, _P, _P, _P, _P, _P, _PU64]),
     ("tc_tandem_repeats", _INT, [_P, _P, _U64, _U32, _U32, _U32, _U32, _P, _P, _P, _PU64]),
     ("tc_tandem_repeats_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _U32, _P, _P, _P, _PU64]),
+    ("tc_palindromes", _INT, [_P, _P, _U64, _P, _U32, _U32, _P, _P, _P, _PU64]),
+    ("tc_palindromes_dev", _INT, [_P, _P, _U64, _P, _U32, _U32, _P, _P, _P, _PU64]),
+    ("tc_longest_palindrome", _INT, [_P, _P, _U64, _P, _U32, _PU32, _PU32, _PU32]),
+    ("tc_longest_palindrome_dev", _INT, [_P, _P, _U64, _P, _U32, _PU32, _PU32, _PU32]),
     ("tc_kmers", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_esa_dev", _INT, [_P, _P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _PU64]),
