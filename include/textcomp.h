@@ -304,6 +304,50 @@ int tc_longest_palindrome(tc_ctx *ctx, const uint8_t *text, uint64_t n, const ui
                           uint32_t *start, uint32_t *len, uint32_t *mm);
 int tc_longest_palindrome_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uint8_t *comp, uint32_t max_mismatch,
                               uint32_t *start, uint32_t *len, uint32_t *mm);
+/* ---- the minimal absent words of a text (not part of the reference's surface) ----
+ * A word x of length >= 2 over bytes is a MINIMAL ABSENT WORD (MAW) of text[0..n) if x does not occur in the text, x
+ * without its first byte occurs, and x without its last byte occurs.  Absent single bytes are not reported.  Write
+ * x = a . w . b, where w may be empty.
+ * N = n + 1 rows, with sa, lcp and left(r) exactly as tc_repeats defines them: row 0 is the empty suffix, left is Nothing
+ * for the one row with sa = 0, and left(0) = text[n-1].  IN ROWS: a NODE is the root [0, N-1] with l = 0, or an LCP interval
+ * [lb, rb] of depth l as in tc_repeats: lb < rb, l = min lcp[lb+1 .. rb], lcp[lb] < l, rb = N - 1 or lcp[rb+1] < l.  The
+ * BOUNDARIES of a node are the rows k in (lb, rb] with lcp[k] = l; its CHILDREN are the maximal row ranges between
+ * boundaries.  The child that starts at lb is dropped when sa[lb] + l = n: that suffix is w itself at the end of the text, so
+ * it has no next byte.  For a child [cl, cr] whose next byte is b = text[sa[cl] + l], let Lw = the set of bytes left(r) over
+ * lb <= r <= rb, without Nothing, and Lc the same over cl <= r <= cr.  The MAWs hanging off this child are a . w . b for
+ * every a in Lw \ Lc; their length is l + 2.  A MAW a . w . b exists only where w is empty or a maximal repeat.
+ * OUTPUT, one entry per MAW: maw_left = a, maw_pos = sa[cl] (0-based), maw_len = l + 2.  The word is the byte maw_left
+ * followed by text[maw_pos .. maw_pos + maw_len - 1).
+ * ORDER: every row k >= 1 is a boundary of exactly one node, the one with l = lcp[k].  Row k reports the child [k, q-1]
+ * that starts at it, and -- when k is the node's first boundary -- the first child [lb, k-1] before that, unless it is
+ * dropped.  The list is in increasing k; within a child, increasing a.  That is deterministic, like the representative-row
+ * order of tc_repeats; it is NOT sorted by word.
+ *   text          (a, pos, len)                                  words
+ *   abaab         (a,2,3) (b,3,3) (a,0,4) (b,4,2)                aaa bab aaba bb
+ *   aaabaab       (a,0,4) (b,0,4) (b,1,5) (b,5,3) (b,6,2)        aaaa baaa baaba bab bb
+ *   mississippi   18 words: ii mip pip pis missip sissis im mm pm sm mp sp ipi ppp ms ps isi sss
+ * A text that holds each of the 256 byte values once has the 65 281 words ab that are not adjacent pairs and nothing
+ * longer.  A unary text a^n has the one word a^(n+1): a^n occurs and a^(n+1) does not; so n = 1 has one word, of length 2.
+ * FILTERS: only words with min_len <= len, and len <= max_len unless max_len = 0 (no limit), are reported.  min_len < 2, or
+ * a max_len that is neither 0 nor >= min_len: TC_ERR_ARG.
+ * *nmaw: in = capacity of the three arrays, out = the count.  Too small: TC_ERR_CAPACITY, *nmaw = the needed count, nothing
+ * written to the three arrays.  maw_left = maw_pos = maw_len = NULL with capacity 0 is the sizes-only form: TC_OK, the
+ * count written.  No simple capacity is always enough -- the count is O(sigma n), at most 512 per row -- so size first.
+ * tc_absent_word_profile: hist[len] = the number of MAWs of length len for len <= kmax (kmax + 1 entries, hist[0] =
+ * hist[1] = 0), 2 <= kmax <= 4096; *total (may be NULL) = the MAWs of every length.  hist equals the histogram of maw_len of
+ * the list call with the window (2, 0).
+ * ERRORS AND EDGES.  Null buffers or n > TC_MAX_N: TC_ERR_ARG.  n = 0: TC_OK, 0 words (an all-zero hist), nothing read.
+ * The calls take the text only: the suffix array, the LCP array, the last column and all scratch (25 bytes per text byte
+ * behind the sort: sa 4, lcp 4, last column 1, the rows' counts 8, the left-context change counts 8, and 36 / (f - 1) for the
+ * two trees of fan-out f = 64; the sort's own need where that is larger; the host form of the list adds 9 bytes per slot of
+ * capacity) live in the calling ctx's workspace.  The _dev forms take the text and every array (hist included) in HBM; nmaw
+ * and total stay host words. */
+int tc_absent_words(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_len, uint32_t max_len, uint8_t *maw_left,
+                    uint32_t *maw_pos, uint32_t *maw_len, uint64_t *nmaw);
+int tc_absent_words_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint32_t max_len, uint8_t *d_maw_left,
+                        uint32_t *d_maw_pos, uint32_t *d_maw_len, uint64_t *nmaw);
+int tc_absent_word_profile(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t kmax, uint64_t *hist, uint64_t *total);
+int tc_absent_word_profile_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t kmax, uint64_t *d_hist, uint64_t *total);
 /* ---- the k-mers of a text: list, abundance spectrum and all-k profile (not part of the reference's surface) ----
  * N = n + 1 rows; sa and lcp as tc_lcp_array defines them (row 0 is the empty suffix, the end of the text matches
  * nothing); lcp[0] counts as 0 whatever the array holds, and lcp[N] as 0.  For k >= 1 row q is a BOUNDARY iff lcp[q] < k;

@@ -13,6 +13,7 @@
 #include "tc_tm_host.hpp"
 #include "tc_tr_host.hpp"
 #include "tc_pal_host.hpp"
+#include "tc_maw_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -259,6 +260,33 @@ int tc_palindromes_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uin
                        uint32_t *d_pal_start, uint32_t *d_pal_len, uint32_t *d_pal_mm, uint64_t *npal) {
     TC_API_BEGIN(ctx)
     palindromes_entry(ctx, d_text, n, comp, max_mismatch, min_len, d_pal_start, d_pal_len, d_pal_mm, npal, true);
+    TC_API_END(ctx)
+}
+
+// the minimal absent words of a text (no counterpart in the reference): tc_maw_host.hpp
+int tc_absent_words(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_len, uint32_t max_len, uint8_t *maw_left,
+                    uint32_t *maw_pos, uint32_t *maw_len, uint64_t *nmaw) {
+    TC_API_BEGIN(ctx)
+    absent_words_entry(ctx, text, n, min_len, max_len, maw_left, maw_pos, maw_len, nmaw, false);
+    TC_API_END(ctx)
+}
+
+int tc_absent_words_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint32_t max_len, uint8_t *d_maw_left,
+                        uint32_t *d_maw_pos, uint32_t *d_maw_len, uint64_t *nmaw) {
+    TC_API_BEGIN(ctx)
+    absent_words_entry(ctx, d_text, n, min_len, max_len, d_maw_left, d_maw_pos, d_maw_len, nmaw, true);
+    TC_API_END(ctx)
+}
+
+int tc_absent_word_profile(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t kmax, uint64_t *hist, uint64_t *total) {
+    TC_API_BEGIN(ctx)
+    absent_word_profile_entry(ctx, text, n, kmax, hist, total, false);
+    TC_API_END(ctx)
+}
+
+int tc_absent_word_profile_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t kmax, uint64_t *d_hist, uint64_t *total) {
+    TC_API_BEGIN(ctx)
+    absent_word_profile_entry(ctx, d_text, n, kmax, d_hist, total, true);
     TC_API_END(ctx)
 }
 

@@ -508,6 +508,73 @@ class Context:
                                                         C.byref(start), C.byref(ln), C.byref(mm)))
         return int(start.value), int(ln.value), int(mm.value)
 
+    # ------------------------------------- the minimal absent words of a text
+    def absent_word_count(self, text, min_len=2, max_len=0):
+        """the number of minimal absent words of text with min_len <= len (<= max_len unless that is 0): the sizes-only form
+        of tc_absent_words"""
+        t = _u8(text)
+        nmaw = C.c_uint64(0)
+        self._check(self._lib.tc_absent_words(self._h, _ptr(t) if len(t) else None, len(t), min_len, max_len, None, None, None,
+                                              C.byref(nmaw)))
+        return int(nmaw.value)
+
+    def absent_words(self, text, min_len=2, max_len=0):
+        """the minimal absent words of text -> (left uint8, pos uint32, len uint32): word k is the byte left[k] followed by
+        text[pos[k] : pos[k] + len[k] - 1]; it does not occur in text, while it does without its first and without its last
+        byte.  In the row order of include/textcomp.h, not sorted by word; max_len = 0: no limit: tc_absent_words"""
+        t = _u8(text)
+        cap = max(self.absent_word_count(t, min_len, max_len), 1)
+        left, pos, ln = np.empty(cap, np.uint8), np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+        nmaw = C.c_uint64(cap)
+        self._check(self._lib.tc_absent_words(self._h, _ptr(t) if len(t) else None, len(t), min_len, max_len, _ptr(left), _ptr(pos),
+                                              _ptr(ln), C.byref(nmaw)))
+        k = int(nmaw.value)
+        return left[:k].copy(), pos[:k].copy(), ln[:k].copy()
+
+    def absent_words_dev(self, d_text, min_len=2, max_len=0, cap=None):
+        """text resident in HBM -> (left uint8, pos int32, len int32), tensors on the device: tc_absent_words_dev.  cap: the
+        word slots to try first (None: the sizes-only form runs first)"""
+        import torch
+        n = d_text.numel()
+        pt = C.c_void_p(d_text.data_ptr()) if n else None
+        torch.cuda.synchronize()
+        if cap is None:
+            nmaw = C.c_uint64(0)
+            self._check(self._lib.tc_absent_words_dev(self._h, pt, n, min_len, max_len, None, None, None, C.byref(nmaw)))
+            cap = int(nmaw.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            out = [torch.empty(cap, dtype=dt, device=d_text.device) for dt in (torch.uint8, torch.int32, torch.int32)]
+            torch.cuda.synchronize()
+            nmaw = C.c_uint64(cap)
+            rc = self._lib.tc_absent_words_dev(self._h, pt, n, min_len, max_len, *(C.c_void_p(o.data_ptr()) for o in out),
+                                               C.byref(nmaw))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nmaw.value), 1)
+        self._check(rc)
+        return tuple(o[:int(nmaw.value)] for o in out)
+
+    def absent_word_profile(self, text, kmax):
+        """-> (hist, total): hist[l] = the number of minimal absent words of length l <= kmax (a uint64 array of kmax + 1
+        entries), total = those of every length: tc_absent_word_profile"""
+        t = _u8(text)
+        hist = np.zeros(max(int(kmax), 0) + 1, np.uint64)
+        total = C.c_uint64(0)
+        self._check(self._lib.tc_absent_word_profile(self._h, _ptr(t) if len(t) else None, len(t), kmax, _ptr(hist), C.byref(total)))
+        return hist, int(total.value)
+
+    def absent_word_profile_dev(self, d_text, kmax):
+        """text resident in HBM -> (hist, an int64 tensor of kmax + 1 entries on the device, total): tc_absent_word_profile_dev"""
+        import torch
+        n = d_text.numel()
+        hist = torch.zeros(max(int(kmax), 0) + 1, dtype=torch.int64, device=d_text.device)
+        torch.cuda.synchronize()
+        total = C.c_uint64(0)
+        self._check(self._lib.tc_absent_word_profile_dev(self._h, C.c_void_p(d_text.data_ptr()) if n else None, n, kmax,
+                                                         C.c_void_p(hist.data_ptr()), C.byref(total)))
+        return hist, int(total.value)
+
     # ------------------------------------- the k-mers of a text: list, abundance spectrum, all-k profile
     def kmer_count(self, text, k, min_occ=1, max_occ=0):
         """how many distinct k-mers of text occur at least min_occ and (max_occ > 0) at most max_occ times: the
@@ -1424,6 +1491,13 @@ class FMIndexHandle:
 
 
 _DEFAULT = None
+
+
+def absent_word_bytes(text, left, pos, ln):
+    """the words of Context.absent_words as a list of bytes, in list order: left[k] followed by
+    text[pos[k] : pos[k] + len[k] - 1].  For small results: the words of a long text need O(sigma n) bytes each."""
+    t = _u8(text).tobytes()
+    return [bytes([int(a)]) + t[int(p):int(p) + int(l) - 1] for a, p, l in zip(np.asarray(left), np.asarray(pos), np.asarray(ln))]
 
 
 def container_coding(blob):

@@ -91,6 +91,10 @@ SYMBOLS = [
     ("tc_palindromes_dev", _INT, [_P, _P, _U64, _P, _U32, _U32, _P, _P, _P, _PU64]),
     ("tc_longest_palindrome", _INT, [_P, _P, _U64, _P, _U32, _PU32, _PU32, _PU32]),
     ("tc_longest_palindrome_dev", _INT, [_P, _P, _U64, _P, _U32, _PU32, _PU32, _PU32]),
+    ("tc_absent_words", _INT, [_P, _P, _U64, _U32, _U32, _P, _P, _P, _PU64]),
+    ("tc_absent_words_dev", _INT, [_P, _P, _U64, _U32, _U32, _P, _P, _P, _PU64]),
+    ("tc_absent_word_profile", _INT, [_P, _P, _U64, _U32, _P, _PU64]),
+    ("tc_absent_word_profile_dev", _INT, [_P, _P, _U64, _U32, _P, _PU64]),
     ("tc_kmers", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_esa_dev", _INT, [_P, _P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _PU64]),
