@@ -348,6 +348,55 @@ int tc_absent_words_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t
                         uint32_t *d_maw_pos, uint32_t *d_maw_len, uint64_t *nmaw);
 int tc_absent_word_profile(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t kmax, uint64_t *hist, uint64_t *total);
 int tc_absent_word_profile_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t kmax, uint64_t *d_hist, uint64_t *total);
+/* ---- what is unique in a text: shortest unique prefixes, minimal unique substrings, the shortest unique substring at
+ * every position (not part of the reference's surface) ----
+ * A substring is UNIQUE when it occurs exactly once in text[0..n).  Occurrences may overlap; the empty string is never
+ * unique.  All positions are 0-based, and the end of the text matches nothing.
+ * SHORTEST UNIQUE PREFIX: up[i], for 0 <= i < n, is the length of the shortest unique substring that starts at i, and 0
+ * where none does -- exactly when the whole suffix at i occurs again as a prefix of another suffix.  IN ROWS, with
+ * N = n + 1, sa and lcp as tc_lcp_array defines them and lcp[N] counted as 0: for the row r with sa[r] = i let
+ * m = max(lcp[r], lcp[r+1]); then up[i] = m + 1 if i + m < n, else 0.
+ * MINIMAL UNIQUE SUBSTRING (MUS): text[s .. s+len) is a MUS when it is unique while it occurs at least twice without its
+ * first byte and at least twice without its last byte.  The empty string counts as occurring twice, so a byte that occurs
+ * once is a MUS of length 1.  Equivalently, s starts a MUS of length up[s] iff up[s] != 0 and (s = n - 1, or up[s+1] = 0,
+ * or up[s+1] >= up[s]).  No MUS contains another, so starts and ends both increase strictly along the list; there are at
+ * most n of them, so capacity n is always enough; a non-empty text has at least one.
+ * SHORTEST UNIQUE SUBSTRING AT A POSITION (point SUS): for every position p, the shortest unique substring
+ * text[s .. s+len) with s <= p < s + len; of equal lengths, the one with the smallest s.  Every unique substring contains a
+ * MUS, so with the MUS list (s_k, e_k = s_k + len_k - 1) the answer at p is the best of up to three candidates: the shortest
+ * MUS with s_k <= p <= e_k, leftmost on ties, as (s_k, len_k); the MUS with the largest e_k < p, extended right, as
+ * (s_k, p - s_k + 1); the MUS with the smallest s_k > p, extended left, as (p, e_k - p + 1).
+ *   text          up                      MUS (start, len)                   point SUS (start, len) for p = 0 .. n-1
+ *   mississippi   1 5 4 3 5 4 3 2 2 2 0   (0,1) (3,3) (7,2) (8,2) (9,2)      (0,1) (0,2) (0,3) (3,3) (3,3) (3,3) (6,3) (7,2) (7,2) (8,2) (9,2)
+ *   abaab         3 2 2 0 0               (1,2) (2,2)                        (0,3) (1,2) (1,2) (2,2) (2,3)
+ *   banana        1 4 3 0 0 0             (0,1) (2,3)                        (0,1) (0,2) (0,3) (2,3) (2,3) (2,4)
+ *   abcabc        4 3 2 0 0 0             (2,2)                              (0,4) (1,3) (2,2) (2,2) (2,3) (2,4)
+ *   aaaa          4 0 0 0                 (0,4)                              (0,4) (0,4) (0,4) (0,4)
+ *   a             1                       (0,1)                              (0,1)
+ * The MUS of mississippi are m, sis, ip, pp, pi; of abaab ba, aa; of banana b, nan; of abcabc ca.
+ * tc_unique_prefixes: up, n entries.
+ * tc_unique_substrings: two arrays mus_start = s and mus_len = len, in increasing start.  FILTERS: only MUS with
+ * min_len <= len, and len <= max_len unless max_len = 0 (no limit), are reported.  min_len = 0, or a max_len that is neither
+ * 0 nor >= min_len: TC_ERR_ARG.
+ * *nmus: in = capacity of the two arrays, out = the count.  Too small: TC_ERR_CAPACITY, *nmus = the needed count, nothing
+ * written to the two arrays.  mus_start = mus_len = NULL with capacity 0 is the sizes-only form: TC_OK, the count written.
+ * tc_shortest_unique: two arrays sus_start = s and sus_len = len, n entries each.  sus_start alone may be NULL; it is then
+ * not written.  The filters of the list do not apply.
+ * ERRORS AND EDGES.  A null context, a null required buffer or n > TC_MAX_N: TC_ERR_ARG, before a buffer is touched.  n = 0:
+ * TC_OK, nothing read or written, 0 MUS.  The calls take the text only: the suffix array, the LCP array and all scratch (sa 4
+ * and lcp 4 bytes per text byte, then up 4: 12 for tc_unique_prefixes -- up is the caller's array in the _dev form -- and for
+ * the list; the point call adds the MUS lengths 4, the predecessor and successor arrays 8 and 4 / (f - 1) for the min tree of
+ * fan-out f = 64: 24; the host forms add their outputs, 8 bytes per slot of capacity or per position; the sort's own need
+ * where that is larger) live in the calling ctx's workspace.  The _dev forms take the text and every array in HBM; nmus
+ * stays a host word. */
+int tc_unique_prefixes(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *up);
+int tc_unique_prefixes_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_up);
+int tc_unique_substrings(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_len, uint32_t max_len, uint32_t *mus_start,
+                         uint32_t *mus_len, uint64_t *nmus);
+int tc_unique_substrings_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint32_t max_len,
+                             uint32_t *d_mus_start, uint32_t *d_mus_len, uint64_t *nmus);
+int tc_shortest_unique(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *sus_start, uint32_t *sus_len);
+int tc_shortest_unique_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_sus_start, uint32_t *d_sus_len);
 /* ---- the k-mers of a text: list, abundance spectrum and all-k profile (not part of the reference's surface) ----
  * N = n + 1 rows; sa and lcp as tc_lcp_array defines them (row 0 is the empty suffix, the end of the text matches
  * nothing); lcp[0] counts as 0 whatever the array holds, and lcp[N] as 0.  For k >= 1 row q is a BOUNDARY iff lcp[q] < k;

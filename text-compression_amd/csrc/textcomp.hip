@@ -14,6 +14,7 @@
 #include "tc_tr_host.hpp"
 #include "tc_pal_host.hpp"
 #include "tc_maw_host.hpp"
+#include "tc_sus_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -287,6 +288,46 @@ int tc_absent_word_profile(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_
 int tc_absent_word_profile_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t kmax, uint64_t *d_hist, uint64_t *total) {
     TC_API_BEGIN(ctx)
     absent_word_profile_entry(ctx, d_text, n, kmax, d_hist, total, true);
+    TC_API_END(ctx)
+}
+
+// what is unique in a text: shortest unique prefixes, minimal unique substrings, the shortest unique substring over every
+// position (no counterpart in the reference): tc_sus_host.hpp
+int tc_unique_prefixes(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *up) {
+    TC_API_BEGIN(ctx)
+    unique_prefixes_entry(ctx, text, n, up, false);
+    TC_API_END(ctx)
+}
+
+int tc_unique_prefixes_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_up) {
+    TC_API_BEGIN(ctx)
+    unique_prefixes_entry(ctx, d_text, n, d_up, true);
+    TC_API_END(ctx)
+}
+
+int tc_unique_substrings(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_len, uint32_t max_len, uint32_t *mus_start,
+                         uint32_t *mus_len, uint64_t *nmus) {
+    TC_API_BEGIN(ctx)
+    unique_substrings_entry(ctx, text, n, min_len, max_len, mus_start, mus_len, nmus, false);
+    TC_API_END(ctx)
+}
+
+int tc_unique_substrings_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint32_t max_len, uint32_t *d_mus_start,
+                             uint32_t *d_mus_len, uint64_t *nmus) {
+    TC_API_BEGIN(ctx)
+    unique_substrings_entry(ctx, d_text, n, min_len, max_len, d_mus_start, d_mus_len, nmus, true);
+    TC_API_END(ctx)
+}
+
+int tc_shortest_unique(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *sus_start, uint32_t *sus_len) {
+    TC_API_BEGIN(ctx)
+    shortest_unique_entry(ctx, text, n, sus_start, sus_len, false);
+    TC_API_END(ctx)
+}
+
+int tc_shortest_unique_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_sus_start, uint32_t *d_sus_len) {
+    TC_API_BEGIN(ctx)
+    shortest_unique_entry(ctx, d_text, n, d_sus_start, d_sus_len, true);
     TC_API_END(ctx)
 }
 

@@ -575,6 +575,90 @@ class Context:
                                                          C.c_void_p(hist.data_ptr()), C.byref(total)))
         return hist, int(total.value)
 
+    # ------------------------------------- what is unique in a text: prefixes, minimal unique substrings, point SUS
+    def unique_prefixes(self, text):
+        """up, a uint32 array: up[i] = the length of the shortest substring that starts at i and occurs once in text, 0 where
+        even the whole suffix occurs again: tc_unique_prefixes"""
+        t = _u8(text)
+        up = np.empty(len(t), np.uint32)
+        self._check(self._lib.tc_unique_prefixes(self._h, _ptr(t) if len(t) else None, len(t), _ptr(up) if len(t) else None))
+        return up
+
+    def unique_prefixes_dev(self, d_text):
+        """text resident in HBM -> up, an int32 tensor on the device: tc_unique_prefixes_dev"""
+        import torch
+        n = d_text.numel()
+        up = torch.empty(n, dtype=torch.int32, device=d_text.device)
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_unique_prefixes_dev(self._h, C.c_void_p(d_text.data_ptr()) if n else None, n,
+                                                     C.c_void_p(up.data_ptr()) if n else None))
+        return up
+
+    def unique_substring_count(self, text, min_len=1, max_len=0):
+        """the number of minimal unique substrings of text with min_len <= len (<= max_len unless that is 0): the sizes-only
+        form of tc_unique_substrings"""
+        t = _u8(text)
+        nmus = C.c_uint64(0)
+        self._check(self._lib.tc_unique_substrings(self._h, _ptr(t) if len(t) else None, len(t), min_len, max_len, None, None,
+                                                   C.byref(nmus)))
+        return int(nmus.value)
+
+    def unique_substrings(self, text, min_len=1, max_len=0):
+        """the minimal unique substrings of text -> (start, len), uint32 arrays: text[start[k] : start[k] + len[k]] occurs
+        once, while it occurs again without its first and without its last byte; by increasing start (and end).  max_len = 0:
+        no limit: tc_unique_substrings"""
+        t = _u8(text)
+        cap = max(self.unique_substring_count(t, min_len, max_len), 1)
+        start, ln = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+        nmus = C.c_uint64(cap)
+        self._check(self._lib.tc_unique_substrings(self._h, _ptr(t) if len(t) else None, len(t), min_len, max_len, _ptr(start),
+                                                   _ptr(ln), C.byref(nmus)))
+        k = int(nmus.value)
+        return start[:k].copy(), ln[:k].copy()
+
+    def unique_substrings_dev(self, d_text, min_len=1, max_len=0, cap=None):
+        """text resident in HBM -> (start, len), int32 tensors on the device: tc_unique_substrings_dev.  cap: the slots to try
+        first (None: the sizes-only form runs first)"""
+        import torch
+        n = d_text.numel()
+        pt = C.c_void_p(d_text.data_ptr()) if n else None
+        torch.cuda.synchronize()
+        if cap is None:
+            nmus = C.c_uint64(0)
+            self._check(self._lib.tc_unique_substrings_dev(self._h, pt, n, min_len, max_len, None, None, C.byref(nmus)))
+            cap = int(nmus.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            out = [torch.empty(cap, dtype=torch.int32, device=d_text.device) for _ in range(2)]
+            torch.cuda.synchronize()
+            nmus = C.c_uint64(cap)
+            rc = self._lib.tc_unique_substrings_dev(self._h, pt, n, min_len, max_len, *(C.c_void_p(o.data_ptr()) for o in out),
+                                                    C.byref(nmus))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nmus.value), 1)
+        self._check(rc)
+        return tuple(o[:int(nmus.value)] for o in out)
+
+    def shortest_unique(self, text):
+        """for every position p the shortest substring of text that covers p and occurs once, of equal lengths the leftmost
+        -> (start, len), uint32 arrays of len(text) entries: tc_shortest_unique"""
+        t = _u8(text)
+        start, ln = np.empty(len(t), np.uint32), np.empty(len(t), np.uint32)
+        self._check(self._lib.tc_shortest_unique(self._h, _ptr(t) if len(t) else None, len(t), _ptr(start) if len(t) else None,
+                                                 _ptr(ln) if len(t) else None))
+        return start, ln
+
+    def shortest_unique_dev(self, d_text):
+        """text resident in HBM -> (start, len), int32 tensors on the device: tc_shortest_unique_dev"""
+        import torch
+        n = d_text.numel()
+        start, ln = (torch.empty(n, dtype=torch.int32, device=d_text.device) for _ in range(2))
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_shortest_unique_dev(self._h, C.c_void_p(d_text.data_ptr()) if n else None, n,
+                                                     C.c_void_p(start.data_ptr()) if n else None, C.c_void_p(ln.data_ptr()) if n else None))
+        return start, ln
+
     # ------------------------------------- the k-mers of a text: list, abundance spectrum, all-k profile
     def kmer_count(self, text, k, min_occ=1, max_occ=0):
         """how many distinct k-mers of text occur at least min_occ and (max_occ > 0) at most max_occ times: the

@@ -95,6 +95,12 @@ SYMBOLS = [
     ("tc_absent_words_dev", _INT, [_P, _P, _U64, _U32, _U32, _P, _P, _P, _PU64]),
     ("tc_absent_word_profile", _INT, [_P, _P, _U64, _U32, _P, _PU64]),
     ("tc_absent_word_profile_dev", _INT, [_P, _P, _U64, _U32, _P, _PU64]),
+    ("tc_unique_prefixes", _INT, [_P, _P, _U64, _P]),
+    ("tc_unique_prefixes_dev", _INT, [_P, _P, _U64, _P]),
+    ("tc_unique_substrings", _INT, [_P, _P, _U64, _U32, _U32, _P, _P, _PU64]),
+    ("tc_unique_substrings_dev", _INT, [_P, _P, _U64, _U32, _U32, _P, _P, _PU64]),
+    ("tc_shortest_unique", _INT, [_P, _P, _U64, _P, _P]),
+    ("tc_shortest_unique_dev", _INT, [_P, _P, _U64, _P, _P]),
     ("tc_kmers", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_esa_dev", _INT, [_P, _P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _PU64]),
