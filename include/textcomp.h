@@ -397,6 +397,73 @@ int tc_unique_substrings_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uin
                              uint32_t *d_mus_start, uint32_t *d_mus_len, uint64_t *nmus);
 int tc_shortest_unique(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *sus_start, uint32_t *sus_len);
 int tc_shortest_unique_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_sus_start, uint32_t *d_sus_len);
+/* ---- the repeat cover of a text: which bytes are repeated content, as spans, as a mask, and the text without them (not part
+ * of the reference's surface) ----
+ * text[0..n), positions 0-based, min_len = L >= 1, min_occ = q >= 2, kind TC_COVER_ALL or TC_COVER_LATER.  Occurrences may
+ * overlap.  The end of the text matches nothing.
+ * SEED: position i with i + L <= n is a seed iff text[i..i+L) occurs at least q times in the text and, for TC_COVER_LATER, i
+ * is not its leftmost occurrence.
+ * COVER: byte p is covered iff some seed i has i <= p < i + L.  Equivalently, p is covered iff it lies in an occurrence of
+ * some substring of length >= L that occurs >= q times (for LATER: in an occurrence that is not that substring's leftmost).
+ * For LATER and q = 2 the cover is the union of [i, i + lpf[i]) over the i with lpf[i] >= L, lpf as tc_lpf_array defines it;
+ * for ALL and q = 2, i is a seed iff i + L <= n and (up[i] = 0 or up[i] > L), up as tc_unique_prefixes defines it; for any q,
+ * i is a seed of kind ALL iff the L-mer of tc_kmers that holds i has occ >= q.
+ * SPANS: the maximal runs of covered bytes as (start, len), in increasing start.  Every len >= L, two spans are at least one
+ * byte apart, and there are at most (n + 1) / (L + 1) of them: capacity n is always enough.  covered = the sum of the span
+ * lengths.
+ * MASK: with a 256-byte map, out[p] = map[text[p]] where p is covered and text[p] elsewhere; with map = NULL, out[p] = 1 / 0,
+ * the cover itself as bytes.  n bytes.
+ * DEDUP: out is the text with the covered bytes removed, in order: n - covered bytes.  With LATER every string of >= L bytes
+ * that occurred earlier is cut out and its first copy kept; with ALL only the content that occurs fewer than q times at
+ * length L remains.  The result may hold new repeats across the cuts: what stood left and right of a cut is adjacent now.
+ *   text                        L q  kind   spans (start,len)   covered  mask                       dedup
+ *   mississippi                 2 2  ALL    (1,7)               7        mISSISSIppi                mppi
+ *   mississippi                 2 2  LATER  (4,4)               4        missISSIppi                missppi
+ *   mississippi                 1 4  ALL    (1,7) (10,1)        8        mISSISSIppI                mpp
+ *   mississippi                 1 4  LATER  (3,5) (10,1)        6        misSISSIppI                mispp
+ *   abcabcabc                   3 3  ALL    (0,9)               9        ABCABCABC                  (empty)
+ *   abcabcabc                   3 2  LATER  (3,6)               6        abcABCABC                  abc
+ *   banana                      2 2  LATER  (3,3)               3        banANA                     ban
+ *   aaaa                        2 2  LATER  (1,3)               3        aAAA                       a
+ *   abcdabxcd                   2 2  ALL    (0,6) (7,2)         8        ABCDABxCD                  x
+ *   abcdabxcd                   2 2  LATER  (4,2) (7,2)         4        abcdABxCD                  abcdx
+ *   "the cat sat; the cat ran"  4 2  LATER  (13,8)              8        the cat sat; THE CAT ran   "the cat sat; ran"
+ * (masks shown with the map that turns a letter into upper case.)
+ * THE GENERAL FORM, tc_cover_*_dev, over an array len of n words in HBM: position i counts iff len[i] >= L, and covers
+ * [i, min(n, i + len[i])), the sum taken in 64 bits.  Spans, mask and dedup are defined as above.  The values are compared
+ * and added and never used as an index, so the calls stay in bounds on any contents.  With len = lpf it is the LATER cover at
+ * q = 2; with len = ms_len of tc_text_match_stats_dev it is the part of a query that is found in a target.
+ * CAPACITY.  *nspans and *nout: in = capacity (of the two arrays, of out), out = the count.  Too small: TC_ERR_CAPACITY, the
+ * needed count written, nothing written to the arrays.  NULL arrays with capacity 0 is the sizes-only form: TC_OK, the count
+ * written.  covered is written in every form where the cover was computed; it may be NULL.
+ * ERRORS AND EDGES.  TC_ERR_ARG, before a buffer is touched, for: a null context or required buffer; n > TC_MAX_N;
+ * min_len = 0; min_occ < 2; an unknown kind; out overlapping the text; a NULL d_text with a non-NULL map.  n = 0 or
+ * min_len > n (the text calls): TC_OK, 0 spans, covered 0, nothing sorted; the mask is the text (zeroes without a map), the
+ * dedup is the text.  The text calls take the text only: the suffix array, the LCP array and all scratch (sa 4 and lcp 4
+ * bytes per text byte, then len 4, and 4 / (f - 1) for each min tree of fan-out f = 64 -- none for ALL with q = 2, that of
+ * lcp for q > 2, that of sa as well for LATER: 12 bytes per text byte and a little; the host forms add their outputs; the
+ * sort's own need where that is larger) live in the calling ctx's workspace; the general form needs 36 bytes per 2048
+ * positions.  The _dev forms take the text and every array in HBM; map, the counts and covered stay in host memory. */
+#define TC_COVER_ALL 0
+#define TC_COVER_LATER 1
+int tc_repeat_spans(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind,
+                    uint32_t *span_start, uint32_t *span_len, uint64_t *nspans, uint64_t *covered);
+int tc_repeat_spans_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind,
+                        uint32_t *d_span_start, uint32_t *d_span_len, uint64_t *nspans, uint64_t *covered);
+int tc_repeat_mask(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind,
+                   const uint8_t *map, uint8_t *out, uint64_t *covered);
+int tc_repeat_mask_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind,
+                       const uint8_t *map, uint8_t *d_out, uint64_t *covered);
+int tc_repeat_dedup(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind, uint8_t *out,
+                    uint64_t *nout, uint64_t *covered);
+int tc_repeat_dedup_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind,
+                        uint8_t *d_out, uint64_t *nout, uint64_t *covered);
+int tc_cover_spans_dev(tc_ctx *ctx, const uint32_t *d_len, uint64_t n, uint32_t min_len, uint32_t *d_span_start,
+                       uint32_t *d_span_len, uint64_t *nspans, uint64_t *covered);
+int tc_cover_mask_dev(tc_ctx *ctx, const uint32_t *d_len, const uint8_t *d_text, uint64_t n, uint32_t min_len, const uint8_t *map,
+                      uint8_t *d_out, uint64_t *covered);
+int tc_cover_dedup_dev(tc_ctx *ctx, const uint32_t *d_len, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint8_t *d_out,
+                       uint64_t *nout, uint64_t *covered);
 /* ---- the k-mers of a text: list, abundance spectrum and all-k profile (not part of the reference's surface) ----
  * N = n + 1 rows; sa and lcp as tc_lcp_array defines them (row 0 is the empty suffix, the end of the text matches
  * nothing); lcp[0] counts as 0 whatever the array holds, and lcp[N] as 0.  For k >= 1 row q is a BOUNDARY iff lcp[q] < k;

@@ -15,6 +15,7 @@
 #include "tc_pal_host.hpp"
 #include "tc_maw_host.hpp"
 #include "tc_sus_host.hpp"
+#include "tc_cov_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -328,6 +329,87 @@ int tc_shortest_unique(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t *s
 int tc_shortest_unique_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t *d_sus_start, uint32_t *d_sus_len) {
     TC_API_BEGIN(ctx)
     shortest_unique_entry(ctx, d_text, n, d_sus_start, d_sus_len, true);
+    TC_API_END(ctx)
+}
+
+// the repeat cover of a text: the bytes that lie in repeated content as spans, as a mask, and the text without them; the same over
+// a caller's array of lengths (no counterpart in the reference): tc_cov_host.hpp
+static CovCall cov_spans_call(uint32_t *span_start, uint32_t *span_len, uint64_t *nspans, uint64_t *covered) {
+    CovCall c;
+    c.what = COV_SPANS; c.span_start = span_start; c.span_len = span_len; c.count = nspans; c.covered = covered;
+    return c;
+}
+static CovCall cov_mask_call(const uint8_t *map, uint8_t *out, uint64_t *covered) {
+    CovCall c;
+    c.what = COV_MASK; c.map = map; c.out = out; c.covered = covered;
+    return c;
+}
+static CovCall cov_dedup_call(uint8_t *out, uint64_t *nout, uint64_t *covered) {
+    CovCall c;
+    c.what = COV_DEDUP; c.out = out; c.count = nout; c.covered = covered;
+    return c;
+}
+
+int tc_repeat_spans(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind, uint32_t *span_start,
+                    uint32_t *span_len, uint64_t *nspans, uint64_t *covered) {
+    TC_API_BEGIN(ctx)
+    repeat_cover_entry(ctx, text, n, min_len, min_occ, kind, cov_spans_call(span_start, span_len, nspans, covered), false);
+    TC_API_END(ctx)
+}
+
+int tc_repeat_spans_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind,
+                        uint32_t *d_span_start, uint32_t *d_span_len, uint64_t *nspans, uint64_t *covered) {
+    TC_API_BEGIN(ctx)
+    repeat_cover_entry(ctx, d_text, n, min_len, min_occ, kind, cov_spans_call(d_span_start, d_span_len, nspans, covered), true);
+    TC_API_END(ctx)
+}
+
+int tc_repeat_mask(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind, const uint8_t *map,
+                   uint8_t *out, uint64_t *covered) {
+    TC_API_BEGIN(ctx)
+    repeat_cover_entry(ctx, text, n, min_len, min_occ, kind, cov_mask_call(map, out, covered), false);
+    TC_API_END(ctx)
+}
+
+int tc_repeat_mask_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind, const uint8_t *map,
+                       uint8_t *d_out, uint64_t *covered) {
+    TC_API_BEGIN(ctx)
+    repeat_cover_entry(ctx, d_text, n, min_len, min_occ, kind, cov_mask_call(map, d_out, covered), true);
+    TC_API_END(ctx)
+}
+
+int tc_repeat_dedup(tc_ctx *ctx, const uint8_t *text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind, uint8_t *out,
+                    uint64_t *nout, uint64_t *covered) {
+    TC_API_BEGIN(ctx)
+    repeat_cover_entry(ctx, text, n, min_len, min_occ, kind, cov_dedup_call(out, nout, covered), false);
+    TC_API_END(ctx)
+}
+
+int tc_repeat_dedup_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint32_t min_occ, uint32_t kind, uint8_t *d_out,
+                        uint64_t *nout, uint64_t *covered) {
+    TC_API_BEGIN(ctx)
+    repeat_cover_entry(ctx, d_text, n, min_len, min_occ, kind, cov_dedup_call(d_out, nout, covered), true);
+    TC_API_END(ctx)
+}
+
+int tc_cover_spans_dev(tc_ctx *ctx, const uint32_t *d_len, uint64_t n, uint32_t min_len, uint32_t *d_span_start, uint32_t *d_span_len,
+                       uint64_t *nspans, uint64_t *covered) {
+    TC_API_BEGIN(ctx)
+    cover_entry(ctx, d_len, nullptr, n, min_len, cov_spans_call(d_span_start, d_span_len, nspans, covered));
+    TC_API_END(ctx)
+}
+
+int tc_cover_mask_dev(tc_ctx *ctx, const uint32_t *d_len, const uint8_t *d_text, uint64_t n, uint32_t min_len, const uint8_t *map,
+                      uint8_t *d_out, uint64_t *covered) {
+    TC_API_BEGIN(ctx)
+    cover_entry(ctx, d_len, d_text, n, min_len, cov_mask_call(map, d_out, covered));
+    TC_API_END(ctx)
+}
+
+int tc_cover_dedup_dev(tc_ctx *ctx, const uint32_t *d_len, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint8_t *d_out,
+                       uint64_t *nout, uint64_t *covered) {
+    TC_API_BEGIN(ctx)
+    cover_entry(ctx, d_len, d_text, n, min_len, cov_dedup_call(d_out, nout, covered));
     TC_API_END(ctx)
 }
 

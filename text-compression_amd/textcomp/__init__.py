@@ -51,6 +51,29 @@ def _dna_complement():
 DNA_COMPLEMENT = _dna_complement()
 
 
+# the kinds of the repeat cover: every occurrence of repeated content, or every occurrence but the leftmost
+COVER_ALL, COVER_LATER = _lib.TC_COVER_ALL, _lib.TC_COVER_LATER
+
+
+def _soft_mask():
+    t = np.arange(256, dtype=np.uint8)
+    t[ord("A"):ord("Z") + 1] += 32
+    t.setflags(write=False)
+    return t
+
+
+# maps of the mask calls: SOFT_MASK lower-cases ASCII letters, hard_mask(b) turns every covered byte into b
+SOFT_MASK = _soft_mask()
+
+
+def hard_mask(byte=b"N"):
+    """the 256-byte map that turns every byte into `byte` (an integer or a one-byte string)"""
+    b = byte if isinstance(byte, int) else bytes(byte)[0] if len(bytes(byte)) == 1 else None
+    if b is None or not 0 <= b <= 255:
+        raise ValueError("hard_mask takes one byte")
+    return np.full(256, b, dtype=np.uint8)
+
+
 def _comp(comp):
     """a byte involution as the 256-byte host table the palindrome calls take (None: the identity, a null pointer)"""
     if comp is None:
@@ -658,6 +681,174 @@ class Context:
         self._check(self._lib.tc_shortest_unique_dev(self._h, C.c_void_p(d_text.data_ptr()) if n else None, n,
                                                      C.c_void_p(start.data_ptr()) if n else None, C.c_void_p(ln.data_ptr()) if n else None))
         return start, ln
+
+    # ------------------------------------- the repeat cover of a text: spans, mask, dedup; the same over an array of lengths
+    @staticmethod
+    def _cover_map(map):
+        if map is None:
+            return None
+        m = np.ascontiguousarray(np.frombuffer(bytes(map), np.uint8) if isinstance(map, (bytes, bytearray)) else map, dtype=np.uint8)
+        if m.shape != (256,):
+            raise ValueError("map must hold 256 bytes")
+        return m
+
+    def repeat_cover_count(self, text, min_len, min_occ=2, kind=COVER_ALL):
+        """(spans, covered): how many maximal runs of repeated content text has, and how many bytes they hold -- a byte is
+        covered when it lies in a stretch of min_len bytes that occurs min_occ times (COVER_LATER: and has occurred before):
+        the sizes-only form of tc_repeat_spans"""
+        t = _u8(text)
+        ns, cov = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.tc_repeat_spans(self._h, _ptr(t) if len(t) else None, len(t), min_len, min_occ, kind, None, None,
+                                              C.byref(ns), C.byref(cov)))
+        return int(ns.value), int(cov.value)
+
+    def repeat_spans(self, text, min_len, min_occ=2, kind=COVER_ALL):
+        """the maximal runs of covered bytes -> (start, len, covered): uint32 arrays in increasing start and the sum of len:
+        tc_repeat_spans"""
+        t = _u8(text)
+        cap = max(self.repeat_cover_count(t, min_len, min_occ, kind)[0], 1)
+        start, ln = np.empty(cap, np.uint32), np.empty(cap, np.uint32)
+        ns, cov = C.c_uint64(cap), C.c_uint64(0)
+        self._check(self._lib.tc_repeat_spans(self._h, _ptr(t) if len(t) else None, len(t), min_len, min_occ, kind, _ptr(start),
+                                              _ptr(ln), C.byref(ns), C.byref(cov)))
+        k = int(ns.value)
+        return start[:k].copy(), ln[:k].copy(), int(cov.value)
+
+    def repeat_mask(self, text, min_len, min_occ=2, kind=COVER_ALL, map=None):
+        """-> (out, covered): out[p] = map[text[p]] where p is covered and text[p] elsewhere (map: 256 bytes, such as SOFT_MASK
+        or hard_mask(b"N")); map None: out[p] = 1 / 0, the cover itself: tc_repeat_mask"""
+        t, m = _u8(text), self._cover_map(map)
+        out = np.empty(len(t), np.uint8)
+        cov = C.c_uint64(0)
+        self._check(self._lib.tc_repeat_mask(self._h, _ptr(t) if len(t) else None, len(t), min_len, min_occ, kind,
+                                             _ptr(m) if m is not None else None, _ptr(out) if len(t) else None, C.byref(cov)))
+        return out, int(cov.value)
+
+    def repeat_dedup(self, text, min_len, min_occ=2, kind=COVER_LATER):
+        """-> (out, covered): the text without its covered bytes, a uint8 array of len(text) - covered entries.  COVER_LATER
+        keeps the first copy of everything; the result may hold new repeats across the cuts: tc_repeat_dedup"""
+        t = _u8(text)
+        out = np.empty(max(len(t), 1), np.uint8)
+        nout, cov = C.c_uint64(len(t)), C.c_uint64(0)
+        self._check(self._lib.tc_repeat_dedup(self._h, _ptr(t) if len(t) else None, len(t), min_len, min_occ, kind, _ptr(out),
+                                              C.byref(nout), C.byref(cov)))
+        return out[:int(nout.value)].copy(), int(cov.value)
+
+    def _spans_retry(self, call, device, cap):
+        """the capacity protocol of the device span lists: call(start, len, nspans, covered) -> rc; cap None: sizes first"""
+        import torch
+        torch.cuda.synchronize()
+        cov = C.c_uint64(0)
+        if cap is None:
+            ns = C.c_uint64(0)
+            self._check(call(None, None, C.byref(ns), C.byref(cov)))
+            cap = int(ns.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            out = [torch.empty(cap, dtype=torch.int32, device=device) for _ in range(2)]
+            torch.cuda.synchronize()
+            ns = C.c_uint64(cap)
+            rc = call(*(C.c_void_p(o.data_ptr()) for o in out), C.byref(ns), C.byref(cov))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(ns.value), 1)
+        self._check(rc)
+        return out[0][:int(ns.value)], out[1][:int(ns.value)], int(cov.value)
+
+    def repeat_spans_dev(self, d_text, min_len, min_occ=2, kind=COVER_ALL, cap=None):
+        """text resident in HBM -> (start, len, covered), int32 tensors on the device and a host integer: tc_repeat_spans_dev.
+        cap: the slots to try first (None: the sizes-only form runs first)"""
+        n, pt = d_text.numel(), self._dev_ptr(d_text)
+        return self._spans_retry(lambda s, l, ns, cv: self._lib.tc_repeat_spans_dev(self._h, pt, n, min_len, min_occ, kind, s, l, ns, cv),
+                                 d_text.device, cap)
+
+    def repeat_cover_count_dev(self, d_text, min_len, min_occ=2, kind=COVER_ALL):
+        """text resident in HBM -> (spans, covered): the sizes-only form of tc_repeat_spans_dev"""
+        import torch
+        ns, cov = C.c_uint64(0), C.c_uint64(0)
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_repeat_spans_dev(self._h, self._dev_ptr(d_text), d_text.numel(), min_len, min_occ, kind, None, None,
+                                                  C.byref(ns), C.byref(cov)))
+        return int(ns.value), int(cov.value)
+
+    def repeat_mask_dev(self, d_text, min_len, min_occ=2, kind=COVER_ALL, map=None):
+        """text resident in HBM -> (out, covered), a uint8 tensor on the device and a host integer: tc_repeat_mask_dev"""
+        import torch
+        n, m = d_text.numel(), self._cover_map(map)
+        out = torch.empty(n, dtype=torch.uint8, device=d_text.device)
+        cov = C.c_uint64(0)
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_repeat_mask_dev(self._h, self._dev_ptr(d_text), n, min_len, min_occ, kind,
+                                                 _ptr(m) if m is not None else None, self._dev_ptr(out), C.byref(cov)))
+        return out, int(cov.value)
+
+    def _dedup_retry(self, call, device, cap):
+        """the capacity protocol of the device dedups: call(out, nout, covered) -> rc; cap None: sizes first"""
+        import torch
+        torch.cuda.synchronize()
+        cov = C.c_uint64(0)
+        if cap is None:
+            nout = C.c_uint64(0)
+            self._check(call(None, C.byref(nout), C.byref(cov)))
+            cap = int(nout.value)
+        cap = max(int(cap), 1)
+        for _ in range(2):
+            out = torch.empty(cap, dtype=torch.uint8, device=device)
+            torch.cuda.synchronize()
+            nout = C.c_uint64(cap)
+            rc = call(C.c_void_p(out.data_ptr()), C.byref(nout), C.byref(cov))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nout.value), 1)
+        self._check(rc)
+        return out[:int(nout.value)], int(cov.value)
+
+    def repeat_dedup_dev(self, d_text, min_len, min_occ=2, kind=COVER_LATER, cap=None):
+        """text resident in HBM -> (out, covered), a uint8 tensor on the device and a host integer: tc_repeat_dedup_dev.  cap: the
+        bytes to try first (None: the sizes-only form runs first; d_text.numel() is always enough)"""
+        n, pt = d_text.numel(), self._dev_ptr(d_text)
+        return self._dedup_retry(lambda o, no, cv: self._lib.tc_repeat_dedup_dev(self._h, pt, n, min_len, min_occ, kind, o, no, cv),
+                                 d_text.device, cap)
+
+    @staticmethod
+    def _len_words(d_len):
+        if d_len.element_size() != 4:
+            raise ValueError("d_len must hold 32-bit entries")
+        return d_len.numel()
+
+    def cover_spans_dev(self, d_len, min_len, cap=None):
+        """an array of lengths resident in HBM (a 32-bit tensor: lpf_array_dev's, text_match_stats_dev's ms_len, or any other)
+        -> (start, len, covered): position i counts iff len[i] >= min_len and covers [i, i + len[i]): tc_cover_spans_dev"""
+        n, pl = self._len_words(d_len), self._dev_ptr(d_len)
+        return self._spans_retry(lambda s, l, ns, cv: self._lib.tc_cover_spans_dev(self._h, pl, n, min_len, s, l, ns, cv), d_len.device, cap)
+
+    def cover_mask_dev(self, d_len, d_text, min_len, map=None):
+        """-> (out, covered): the mask of d_text (a uint8 tensor of d_len.numel() bytes; may be None without a map) under the
+        cover of d_len: tc_cover_mask_dev"""
+        import torch
+        n, m = self._len_words(d_len), self._cover_map(map)
+        if d_text is not None and d_text.numel() != n:
+            raise ValueError("d_text and d_len must have one length")
+        out = torch.empty(n, dtype=torch.uint8, device=d_len.device)
+        cov = C.c_uint64(0)
+        torch.cuda.synchronize()
+        self._check(self._lib.tc_cover_mask_dev(self._h, self._dev_ptr(d_len), self._dev_ptr(d_text) if d_text is not None else None, n,
+                                                min_len, _ptr(m) if m is not None else None, self._dev_ptr(out), C.byref(cov)))
+        return out, int(cov.value)
+
+    def cover_dedup_dev(self, d_len, d_text, min_len, cap=None):
+        """-> (out, covered): d_text without the bytes the cover of d_len holds: tc_cover_dedup_dev"""
+        n = self._len_words(d_len)
+        if d_text.numel() != n:
+            raise ValueError("d_text and d_len must have one length")
+        pl, pt = self._dev_ptr(d_len), self._dev_ptr(d_text)
+        return self._dedup_retry(lambda o, no, cv: self._lib.tc_cover_dedup_dev(self._h, pl, pt, n, min_len, o, no, cv), d_len.device, cap)
+
+    def text_cover_dev(self, d_query, d_target, min_len):
+        """the two texts resident in HBM -> (start, len, covered): the maximal stretches of d_query made of substrings of at
+        least min_len bytes that occur in d_target: text_match_stats_dev(pos=False, occ=False), then cover_spans_dev"""
+        ms_len = self.text_match_stats_dev(d_query, d_target, pos=False, occ=False)[0]
+        return self.cover_spans_dev(ms_len, min_len)
 
     # ------------------------------------- the k-mers of a text: list, abundance spectrum, all-k profile
     def kmer_count(self, text, k, min_occ=1, max_occ=0):

@@ -18,6 +18,7 @@ TC_FM_MAX_SA_RATE = 4096
 TC_FM_MAX_MISMATCH = 3
 TC_MAX_N = 0x7ffffff0
 TC_REPEAT_MAXIMAL, TC_REPEAT_SUPERMAXIMAL = 0, 1
+TC_COVER_ALL, TC_COVER_LATER = 0, 1
 TC_PAL_MAX_MISMATCH = 16
 TC_LCP_SHORT_CAP = 256   # csrc/tc_lcp.hpp: comparisons of the LCP array longer than this leave the one-lane kernel
 
@@ -101,6 +102,15 @@ SYMBOLS = [
     ("tc_unique_substrings_dev", _INT, [_P, _P, _U64, _U32, _U32, _P, _P, _PU64]),
     ("tc_shortest_unique", _INT, [_P, _P, _U64, _P, _P]),
     ("tc_shortest_unique_dev", _INT, [_P, _P, _U64, _P, _P]),
+    ("tc_repeat_spans", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _PU64, _PU64]),
+    ("tc_repeat_spans_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _PU64, _PU64]),
+    ("tc_repeat_mask", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _PU64]),
+    ("tc_repeat_mask_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _PU64]),
+    ("tc_repeat_dedup", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _PU64, _PU64]),
+    ("tc_repeat_dedup_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _PU64, _PU64]),
+    ("tc_cover_spans_dev", _INT, [_P, _P, _U64, _U32, _P, _P, _PU64, _PU64]),
+    ("tc_cover_mask_dev", _INT, [_P, _P, _P, _U64, _U32, _P, _P, _PU64]),
+    ("tc_cover_dedup_dev", _INT, [_P, _P, _P, _U64, _U32, _P, _PU64, _PU64]),
     ("tc_kmers", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_esa_dev", _INT, [_P, _P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _PU64]),
