@@ -464,6 +464,60 @@ int tc_cover_mask_dev(tc_ctx *ctx, const uint32_t *d_len, const uint8_t *d_text,
                       uint8_t *d_out, uint64_t *covered);
 int tc_cover_dedup_dev(tc_ctx *ctx, const uint32_t *d_len, const uint8_t *d_text, uint64_t n, uint32_t min_len, uint8_t *d_out,
                        uint64_t *nout, uint64_t *covered);
+/* ---- a kept enhanced suffix array: build once, batched substring queries (not part of the reference's surface) ----
+ * tc_esa is an opaque handle, owned like tc_fm: its own device blocks, not the workspace of the ctx that built it.  It lives
+ * until tc_esa_free and is read-only after the build.  WHAT THE HANDLE KEEPS: a copy of the text (n bytes and 16 of padding);
+ * sa, lcp and isa, N = n + 1 entries each, sa and lcp exactly as tc_suffix_array_dev and tc_lcp_array_dev define them (row 0
+ * is the empty suffix), isa[sa[r]] = r; the min tree over lcp and a min tree over sa, fan-out 64: about 13.2 bytes per text
+ * byte in all, tc_esa_device_bytes reports the real figures (part 0 all, 1 text, 2 sa, 3 isa, 4 lcp + its min tree, 5 the min
+ * tree of sa; parts 1 .. 5 sum to part 0).  The build sorts and makes the LCP array in the ctx's workspace, which holds scratch
+ * only.  n = 0 builds the one-row ESA.  A failed build releases everything and leaves *out NULL.
+ * tc_esa_arrays: the device pointers (each out-pointer may be NULL); they stay valid until tc_esa_free and may be passed to
+ * tc_kmers_esa_dev, tc_kmer_spectrum_esa_dev, tc_kmer_profile_esa_dev and tc_cover_*_dev: the sort is paid once.
+ * tc_esa_read: entries [first, first + count) of one array (what: 1 text, 2 sa, 3 isa, 4 lcp) to host memory, or to device
+ * memory with dst_on_device != 0.  A range past the array is TC_ERR_ARG.
+ * THE QUERIES, each over nq queries; in the _dev forms every array is in HBM and nq is a host word.  nq = 0: TC_OK, nothing
+ * touched.  Positions are 0-based and run 0 .. n inclusive; position n is the empty suffix.  Occurrences may overlap.  The end
+ * of the text matches nothing.
+ * LCE: len[q] is the largest L with a[q] + L <= n, b[q] + L <= n and at most max_mismatch positions k < L where
+ * text[a + k] != text[b + k]; mm[q] is the number of such positions (mm may be NULL).  max_mismatch <= TC_ESA_MAX_MISMATCH.
+ * a == b gives n - a and 0 mismatches.
+ *   mississippi: (1, 4) gives 4 at max_mismatch 0, 5 with mm = 1 at 1, 7 with mm = 2 at 2; (0, 0) gives 11; (3, 11) gives 0
+ * FIND: for the substring text[start .. start + len), first_row[q] is the smallest row whose suffix has the substring as a
+ * prefix, occ[q] is the number of such rows, first_pos[q] is the smallest text position where it occurs.  Each of the three
+ * may be NULL, but not all three.  len = 0 answers (0, n + 1, 0).
+ *   mississippi: (1, 4) "issi" gives first_row 3, occ 2, first_pos 1; (2, 1) "s" gives first_row 8, occ 4, first_pos 2
+ * COMPARE: order[q] = -1, 0, 1 as text[a_start .. a_start + a_len) sorts before, equals, sorts behind
+ * text[b_start .. b_start + b_len), bytes compared as unsigned; a proper prefix sorts first.  common[q] is the length of
+ * their common prefix (common may be NULL).
+ *   mississippi: (1, 4) against (4, 4) gives 0, common 4; (1, 4) against (4, 3) gives 1, common 3; (8, 2) against (5, 2) gives
+ *   -1, common 0
+ * ERRORS.  TC_ERR_ARG for: a null context, handle or required buffer; max_mismatch > TC_ESA_MAX_MISMATCH; n > TC_MAX_N; a
+ * handle built on another device than the ctx's; a query that leaves the text (a position above n, start + len > n) in both
+ * forms -- the kernel raises a flag, every access stays in bounds, and the outputs of the batch are unspecified.  Any number
+ * of ctxs on the handle's device may query one handle at the same time; in the calling ctx's workspace a query batch needs
+ * its flag word and, in the host form, the bytes of its arrays. */
+typedef struct tc_esa tc_esa;
+#define TC_ESA_MAX_MISMATCH 16
+int tc_esa_build(tc_ctx *ctx, const uint8_t *text, uint64_t n, tc_esa **out);
+int tc_esa_build_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, tc_esa **out);
+void tc_esa_free(tc_esa *esa);
+uint64_t tc_esa_n(const tc_esa *esa);
+uint64_t tc_esa_device_bytes(const tc_esa *esa, int part);
+int tc_esa_arrays(const tc_esa *esa, const uint8_t **d_text, const uint32_t **d_sa, const uint32_t **d_lcp, const uint32_t **d_isa);
+int tc_esa_read(tc_ctx *ctx, const tc_esa *esa, int what, uint64_t first, uint64_t count, void *dst, int dst_on_device);
+int tc_esa_lce(tc_ctx *ctx, const tc_esa *esa, const uint32_t *a, const uint32_t *b, uint64_t nq, uint32_t max_mismatch,
+               uint32_t *len, uint32_t *mm);
+int tc_esa_lce_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_a, const uint32_t *d_b, uint64_t nq, uint32_t max_mismatch,
+                   uint32_t *d_len, uint32_t *d_mm);
+int tc_esa_find(tc_ctx *ctx, const tc_esa *esa, const uint32_t *start, const uint32_t *len, uint64_t nq, uint32_t *first_row,
+                uint32_t *occ, uint32_t *first_pos);
+int tc_esa_find_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_start, const uint32_t *d_len, uint64_t nq,
+                    uint32_t *d_first_row, uint32_t *d_occ, uint32_t *d_first_pos);
+int tc_esa_compare(tc_ctx *ctx, const tc_esa *esa, const uint32_t *a_start, const uint32_t *a_len, const uint32_t *b_start,
+                   const uint32_t *b_len, uint64_t nq, int8_t *order, uint32_t *common);
+int tc_esa_compare_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_a_start, const uint32_t *d_a_len,
+                       const uint32_t *d_b_start, const uint32_t *d_b_len, uint64_t nq, int8_t *d_order, uint32_t *d_common);
 /* ---- the k-mers of a text: list, abundance spectrum and all-k profile (not part of the reference's surface) ----
  * N = n + 1 rows; sa and lcp as tc_lcp_array defines them (row 0 is the empty suffix, the end of the text matches
  * nothing); lcp[0] counts as 0 whatever the array holds, and lcp[N] as 0.  For k >= 1 row q is a BOUNDARY iff lcp[q] < k;

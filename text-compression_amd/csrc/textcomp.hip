@@ -16,6 +16,7 @@
 #include "tc_maw_host.hpp"
 #include "tc_sus_host.hpp"
 #include "tc_cov_host.hpp"
+#include "tc_esa_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -410,6 +411,82 @@ int tc_cover_dedup_dev(tc_ctx *ctx, const uint32_t *d_len, const uint8_t *d_text
                        uint64_t *nout, uint64_t *covered) {
     TC_API_BEGIN(ctx)
     cover_entry(ctx, d_len, d_text, n, min_len, cov_dedup_call(d_out, nout, covered));
+    TC_API_END(ctx)
+}
+
+// the kept enhanced suffix array and its batched substring queries (no counterpart in the reference): tc_esa_host.hpp
+int tc_esa_build(tc_ctx *ctx, const uint8_t *text, uint64_t n, tc_esa **out) {
+    if (out) *out = nullptr;
+    TC_API_BEGIN(ctx)
+    esa_build_entry(ctx, text, n, out, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_build_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, tc_esa **out) {
+    if (out) *out = nullptr;
+    TC_API_BEGIN(ctx)
+    esa_build_entry(ctx, d_text, n, out, true);
+    TC_API_END(ctx)
+}
+
+void tc_esa_free(tc_esa *esa) { esa_release(esa); }
+uint64_t tc_esa_n(const tc_esa *esa) { return esa ? esa->n : 0; }
+uint64_t tc_esa_device_bytes(const tc_esa *esa, int part) { return esa_device_bytes(esa, part); }
+
+int tc_esa_arrays(const tc_esa *esa, const uint8_t **d_text, const uint32_t **d_sa, const uint32_t **d_lcp, const uint32_t **d_isa) {
+    if (!esa) return TC_ERR_ARG;
+    if (d_text) *d_text = esa->d_text;
+    if (d_sa) *d_sa = esa->d_sa;
+    if (d_lcp) *d_lcp = esa->d_lcp;
+    if (d_isa) *d_isa = esa->d_isa;
+    return TC_OK;
+}
+
+int tc_esa_read(tc_ctx *ctx, const tc_esa *esa, int what, uint64_t first, uint64_t count, void *dst, int dst_on_device) {
+    TC_API_BEGIN(ctx)
+    esa_read_entry(ctx, esa, what, first, count, dst, dst_on_device != 0);
+    TC_API_END(ctx)
+}
+
+int tc_esa_lce(tc_ctx *ctx, const tc_esa *esa, const uint32_t *a, const uint32_t *b, uint64_t nq, uint32_t max_mismatch, uint32_t *len,
+               uint32_t *mm) {
+    TC_API_BEGIN(ctx)
+    esa_lce_entry(ctx, esa, a, b, nq, max_mismatch, len, mm, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_lce_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_a, const uint32_t *d_b, uint64_t nq, uint32_t max_mismatch,
+                   uint32_t *d_len, uint32_t *d_mm) {
+    TC_API_BEGIN(ctx)
+    esa_lce_entry(ctx, esa, d_a, d_b, nq, max_mismatch, d_len, d_mm, true);
+    TC_API_END(ctx)
+}
+
+int tc_esa_find(tc_ctx *ctx, const tc_esa *esa, const uint32_t *start, const uint32_t *len, uint64_t nq, uint32_t *first_row, uint32_t *occ,
+                uint32_t *first_pos) {
+    TC_API_BEGIN(ctx)
+    esa_find_entry(ctx, esa, start, len, nq, first_row, occ, first_pos, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_find_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_start, const uint32_t *d_len, uint64_t nq, uint32_t *d_first_row,
+                    uint32_t *d_occ, uint32_t *d_first_pos) {
+    TC_API_BEGIN(ctx)
+    esa_find_entry(ctx, esa, d_start, d_len, nq, d_first_row, d_occ, d_first_pos, true);
+    TC_API_END(ctx)
+}
+
+int tc_esa_compare(tc_ctx *ctx, const tc_esa *esa, const uint32_t *a_start, const uint32_t *a_len, const uint32_t *b_start,
+                   const uint32_t *b_len, uint64_t nq, int8_t *order, uint32_t *common) {
+    TC_API_BEGIN(ctx)
+    esa_compare_entry(ctx, esa, a_start, a_len, b_start, b_len, nq, reinterpret_cast<signed char *>(order), common, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_compare_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_a_start, const uint32_t *d_a_len, const uint32_t *d_b_start,
+                       const uint32_t *d_b_len, uint64_t nq, int8_t *d_order, uint32_t *d_common) {
+    TC_API_BEGIN(ctx)
+    esa_compare_entry(ctx, esa, d_a_start, d_a_len, d_b_start, d_b_len, nq, reinterpret_cast<signed char *>(d_order), d_common, true);
     TC_API_END(ctx)
 }
 

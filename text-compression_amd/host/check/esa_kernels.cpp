@@ -1,0 +1,376 @@
+// Stand-alone host check of the query lanes of the kept enhanced suffix array (csrc/tc_esa.hpp), meant to be built with a host
+// sanitizer:
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I text-compression_amd/csrc
+//       text-compression_amd/host/check/esa_kernels.cpp -o esa_kernels && ./esa_kernels
+// TC_FM_MS_HOST_CHECK compiles esa_lce_kernel, esa_find_kernel and esa_compare_kernel, the range minimum of csrc/tc_lz.hpp and
+// the row searches of csrc/tc_fm_ms.hpp as plain C++, as host/check/cover_kernels.cpp does for the repeat cover: the HIP keywords
+// defined away, the lanes run one after another.  Everything around them is built naively here -- suffixes sorted directly, the
+// LCP array by comparing neighbours, the inverse by a scatter, the two min trees by fm_lmin_kernel level over level at fan-outs 4
+// and 64 -- in heap blocks of exactly the bytes the library's handle allocates (the text with its 16 bytes of padding, the three
+// row arrays rounded up to 16 bytes, the trees' words), and every query and result array holds exactly nq entries, so a read or a
+// store one element outside any of them stops the run.  Every answer is compared with loops over the bytes.  Texts: unary,
+// periodic (2, 3, 7), Fibonacci, random over 2, 4 and 200 letters, a text followed by its copy, one letter and then 2600 times
+// another.  Queries: all pairs and all substrings on the texts of at most 40 bytes; on the longer ones sampled pairs and the
+// adversarial ones -- (i, i + period), (i, n), (n, n), (i, i), positions 0, n - 1 and n, len = 0 and len = n, substrings that
+// occur once -- and queries that leave the text, which must raise the flag and touch nothing outside the blocks.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <random>
+#include <string>
+#include <vector>
+
+#define TC_FM_MS_HOST_CHECK
+#include "tc_esa.hpp"
+
+#define EXPECT(cond)                                                              \
+    do {                                                                          \
+        if (!(cond)) {                                                            \
+            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
+            std::exit(1);                                                         \
+        }                                                                         \
+    } while (0)
+
+template <class F>
+static void launch(u64 grid, F &&kernel) {
+    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
+}
+// a heap block of exactly `bytes` bytes
+template <class T>
+static std::unique_ptr<T[]> block_bytes(size_t bytes) {
+    EXPECT(bytes % sizeof(T) == 0);
+    return std::unique_ptr<T[]>(new T[bytes / sizeof(T) ? bytes / sizeof(T) : 1]);
+}
+template <class T>
+static std::unique_ptr<T[]> block_of(const std::vector<T> &v) {
+    std::unique_ptr<T[]> p(new T[v.size() ? v.size() : 1]);
+    std::copy(v.begin(), v.end(), p.get());
+    return p;
+}
+
+typedef std::vector<u8> Bytes;
+
+static u64 g_texts = 0, g_lce = 0, g_find = 0, g_cmp = 0, g_refused = 0;
+static u64 g_down[FM_MS_MAXLEV + 1] = {}, g_up[FM_MS_MAXLEV + 1] = {}, g_min[FM_MS_MAXLEV + 1] = {};
+static u32 g_maxlev4 = 0;
+static bool g_pos0 = false, g_posn1 = false, g_posn = false, g_len0 = false, g_lenn = false, g_once = false;
+
+// ---- the handle, naively, in the library's block sizes (tc_esa_host.hpp) -----------------------------------------------------
+struct Esa {
+    u32 n, N, lf, nlev, words;
+    std::unique_ptr<u8[]> text;
+    std::unique_ptr<u32[]> sa, isa, lcp, lcp_min, sa_min;
+};
+static Esa esa_of(const Bytes &t, u32 lf) {
+    Esa e;
+    e.n = (u32)t.size();
+    e.N = e.n + 1;
+    e.lf = lf;
+    const u32 n = e.n, N = e.N;
+    const size_t rows = ((size_t)N * 4 + 15) & ~(size_t)15;
+    e.text = block_bytes<u8>(((size_t)n + 16 + 15) & ~(size_t)15);
+    std::memset(e.text.get(), 0, ((size_t)n + 16 + 15) & ~(size_t)15);
+    std::copy(t.begin(), t.end(), e.text.get());
+    e.sa = block_bytes<u32>(rows);
+    e.isa = block_bytes<u32>(rows);
+    e.lcp = block_bytes<u32>(rows);
+    for (size_t i = 0; i < rows / 4; i++) e.sa[i] = e.isa[i] = e.lcp[i] = 0xdeadbeefu;   // (what lies behind row N - 1 is never an answer)
+    for (u32 i = 0; i < N; i++) e.sa[i] = i;
+    std::sort(e.sa.get(), e.sa.get() + N, [&](u32 x, u32 y) {       // the empty suffix first: a proper prefix sorts first
+        const int c = std::memcmp(t.data() + x, t.data() + y, std::min(n - x, n - y));
+        return c ? c < 0 : x > y;
+    });
+    for (u32 j = 0; j < N; j++) {
+        u32 l = 0;
+        if (j) {
+            const u32 a = e.sa[j - 1], b = e.sa[j];
+            while (a + l < n && b + l < n && t[a + l] == t[b + l]) l++;
+        }
+        e.lcp[j] = l;
+        e.isa[e.sa[j]] = j;
+    }
+    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1];
+    e.nlev = fm_ms_tree_shape(N, lf, off, cnt, &e.words);
+    e.lcp_min = block_bytes<u32>((size_t)e.words * 4);
+    e.sa_min = block_bytes<u32>((size_t)e.words * 4);
+    for (int which = 0; which < 2; which++) {
+        const u32 *src = which ? e.sa.get() : e.lcp.get();
+        u32 *lmin = which ? e.sa_min.get() : e.lcp_min.get();
+        for (u32 k = 1; k <= e.nlev; k++) {
+            u32 *dst = lmin + off[k];
+            launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], lf, dst, cnt[k]); });
+            src = dst;
+        }
+    }
+    return e;
+}
+
+// ---- brute force -------------------------------------------------------------------------------------------------------------
+static void brute_lce(const Bytes &t, u32 a, u32 b, u32 m, u32 *len, u32 *mm) {
+    const u32 n = (u32)t.size();
+    u32 L = 0, k = 0;
+    while (a + L < n && b + L < n) {
+        if (t[a + L] != t[b + L]) {
+            if (k == m) break;
+            k++;
+        }
+        L++;
+    }
+    *len = L;
+    *mm = k;
+}
+static void brute_find(const Bytes &t, const Esa &e, u32 s, u32 l, u32 *row, u32 *occ, u32 *pos) {
+    const u32 n = e.n;
+    if (l == 0) {
+        *row = 0; *occ = n + 1; *pos = 0;
+        return;
+    }
+    u32 c = 0, first = 0xffffffffu, lo = 0xffffffffu, hi = 0;
+    for (u32 i = 0; i + l <= n; i++) {
+        if (std::memcmp(t.data() + i, t.data() + s, l)) continue;
+        c++;
+        first = std::min(first, i);
+        lo = std::min(lo, e.isa[i]);
+        hi = std::max(hi, e.isa[i]);
+    }
+    EXPECT(c >= 1 && hi - lo + 1 == c);     // the occurrences' rows are an interval
+    *row = lo; *occ = c; *pos = first;
+}
+static void brute_compare(const Bytes &t, u32 a, u32 la, u32 b, u32 lb, int *order, u32 *common) {
+    u32 c = 0;
+    while (c < la && c < lb && t[a + c] == t[b + c]) c++;
+    *common = c;
+    if (c < la && c < lb) *order = t[a + c] < t[b + c] ? -1 : 1;
+    else *order = la < lb ? -1 : (la > lb ? 1 : 0);
+}
+
+// ---- one batch of each kind through the kernels, in blocks of exactly nq entries ------------------------------------------------
+struct Pair { u32 a, b; };
+struct Quad { u32 a, la, b, lb; };
+
+static void run_lce(const Bytes &t, const Esa &e, const std::vector<Pair> &q, u32 m, bool with_mm, bool expect_bad) {
+    const u64 nq = q.size();
+    std::vector<u32> va, vb;
+    for (const Pair &p : q) { va.push_back(p.a); vb.push_back(p.b); }
+    auto a = block_of(va), b = block_of(vb);
+    auto len = block_of(std::vector<u32>(nq, 0xabababab)), mm = block_of(std::vector<u32>(nq, 0xabababab));
+    u32 bad = 0;
+    launch(nq, [&] {
+        esa_lce_kernel(e.text.get(), e.n, e.isa.get(), e.lcp.get(), e.lcp_min.get(), e.lf, a.get(), b.get(), nq, m, len.get(),
+                       with_mm ? mm.get() : nullptr, &bad);
+    });
+    EXPECT((bad != 0) == expect_bad);
+    for (u64 k = 0; k < nq; k++) {
+        if (q[k].a > e.n || q[k].b > e.n) {
+            EXPECT(len[k] == 0xabababab);
+            g_refused++;
+            continue;
+        }
+        u32 wl, wm;
+        brute_lce(t, q[k].a, q[k].b, m, &wl, &wm);
+        EXPECT(len[k] == wl);
+        EXPECT(with_mm ? mm[k] == wm : mm[k] == 0xabababab);
+        EXPECT(wm <= m && q[k].a + wl <= e.n && q[k].b + wl <= e.n);
+        for (u32 x : {q[k].a, q[k].b}) {
+            g_pos0 |= x == 0;
+            g_posn1 |= e.n && x == e.n - 1;
+            g_posn |= x == e.n;
+        }
+    }
+    g_lce += nq;
+}
+
+static void run_find(const Bytes &t, const Esa &e, const std::vector<Pair> &q, u32 outs, bool expect_bad) {     // q: (start, len); outs: bit 0 first_row, 1 occ, 2 first_pos
+    const u64 nq = q.size();
+    std::vector<u32> vs, vl;
+    for (const Pair &p : q) { vs.push_back(p.a); vl.push_back(p.b); }
+    auto s = block_of(vs), l = block_of(vl);
+    auto row = block_of(std::vector<u32>(nq, 0xabababab)), occ = block_of(std::vector<u32>(nq, 0xabababab)),
+         pos = block_of(std::vector<u32>(nq, 0xabababab));
+    u32 bad = 0;
+    launch(nq, [&] {
+        esa_find_kernel(e.n, e.sa.get(), e.isa.get(), e.lcp.get(), e.sa_min.get(), e.lcp_min.get(), e.lf, s.get(), l.get(), nq,
+                        outs & 1 ? row.get() : nullptr, outs & 2 ? occ.get() : nullptr, outs & 4 ? pos.get() : nullptr, &bad);
+    });
+    EXPECT((bad != 0) == expect_bad);
+    for (u64 k = 0; k < nq; k++) {
+        if (q[k].a > e.n || q[k].b > e.n - q[k].a) {
+            EXPECT(row[k] == 0xabababab && occ[k] == 0xabababab && pos[k] == 0xabababab);
+            g_refused++;
+            continue;
+        }
+        u32 wr, wo, wp;
+        brute_find(t, e, q[k].a, q[k].b, &wr, &wo, &wp);
+        EXPECT(row[k] == (outs & 1 ? wr : 0xabababab));
+        EXPECT(occ[k] == (outs & 2 ? wo : 0xabababab));
+        EXPECT(pos[k] == (outs & 4 ? wp : 0xabababab));
+        g_len0 |= q[k].b == 0;
+        g_lenn |= e.n && q[k].b == e.n;
+        g_once |= q[k].b && wo == 1;
+    }
+    g_find += nq;
+}
+
+static void run_compare(const Bytes &t, const Esa &e, const std::vector<Quad> &q, bool with_common, bool expect_bad) {
+    const u64 nq = q.size();
+    std::vector<u32> v[4];
+    for (const Quad &p : q) { v[0].push_back(p.a); v[1].push_back(p.la); v[2].push_back(p.b); v[3].push_back(p.lb); }
+    auto a = block_of(v[0]), la = block_of(v[1]), b = block_of(v[2]), lb = block_of(v[3]);
+    auto order = block_of(std::vector<signed char>(nq, 99));
+    auto common = block_of(std::vector<u32>(nq, 0xabababab));
+    u32 bad = 0;
+    launch(nq, [&] {
+        esa_compare_kernel(e.text.get(), e.n, e.isa.get(), e.lcp.get(), e.lcp_min.get(), e.lf, a.get(), la.get(), b.get(), lb.get(), nq,
+                           order.get(), with_common ? common.get() : nullptr, &bad);
+    });
+    EXPECT((bad != 0) == expect_bad);
+    for (u64 k = 0; k < nq; k++) {
+        const Quad &p = q[k];
+        if (p.a > e.n || p.la > e.n - p.a || p.b > e.n || p.lb > e.n - p.b) {
+            EXPECT(order[k] == 99 && common[k] == 0xabababab);
+            g_refused++;
+            continue;
+        }
+        int wo;
+        u32 wc;
+        brute_compare(t, p.a, p.la, p.b, p.lb, &wo, &wc);
+        EXPECT(order[k] == wo);
+        EXPECT(common[k] == (with_common ? wc : 0xabababab));
+    }
+    g_cmp += nq;
+}
+
+static void check_text(const Bytes &t, u32 lf, u32 period, std::mt19937 &rng) {
+    const Esa e = esa_of(t, lf);
+    const u32 n = e.n;
+    std::memset(lz_climbed, 0, sizeof lz_climbed);
+    std::memset(fm_ms_climbed, 0, sizeof fm_ms_climbed);
+    std::vector<Pair> pairs, subs;
+    std::vector<Quad> quads;
+    if (n <= 40) {
+        for (u32 a = 0; a <= n; a++)
+            for (u32 b = 0; b <= n; b++) pairs.push_back({a, b});
+        for (u32 s = 0; s <= n; s++)
+            for (u32 l = 0; l <= n - s; l++) subs.push_back({s, l});
+    } else {
+        for (u32 k = 0; k < 1500; k++) pairs.push_back({(u32)(rng() % (n + 1)), (u32)(rng() % (n + 1))});
+        for (u32 i = 0; i <= n; i += 1 + n / 97) {
+            pairs.push_back({i, n});
+            pairs.push_back({n, i});
+            pairs.push_back({i, i});
+            pairs.push_back({0, i});
+            pairs.push_back({i, n - 1});
+            if (period && i + period <= n) pairs.push_back({i, i + period});
+            if (period && i + 3 * period <= n) pairs.push_back({i + 3 * period, i});
+        }
+        pairs.push_back({n, n});
+        for (u32 k = 0; k < 700; k++) {
+            const u32 s = (u32)(rng() % (n + 1)), room = n - s;
+            const u32 l = k % 3 == 0 ? (u32)(rng() % (room + 1)) : std::min<u32>(room, (u32)(rng() % 12));
+            subs.push_back({s, l});
+        }
+        subs.push_back({0, n});
+        subs.push_back({0, 0});
+        subs.push_back({n, 0});
+        subs.push_back({n - 1, 1});
+        subs.push_back({0, 1});
+        subs.push_back({n / 2, n - n / 2});
+    }
+    const size_t ns = subs.size();
+    for (u32 k = 0; k < (n <= 40 ? 4000u : 1500u) && ns; k++) {
+        const Pair x = subs[rng() % ns], y = subs[rng() % ns];
+        quads.push_back({x.a, x.b, y.a, y.b});
+        if (k % 4 == 0) quads.push_back({x.a, x.b, x.a, x.b});                                   // equal: the same place
+        if (k % 4 == 1 && y.a + x.b <= n) quads.push_back({x.a, x.b, y.a, x.b});                 // one length, another place
+        if (k % 4 == 2 && x.b) quads.push_back({x.a, x.b, x.a, (u32)(rng() % x.b)});             // a proper prefix
+        if (k % 4 == 3) quads.push_back({x.a, 0, y.a, y.b});                                     // len 0
+        if (period && x.a + period + x.b <= n) quads.push_back({x.a, x.b, x.a + period, x.b});   // equal, at another place
+    }
+    const u64 turns = esa_seen[4];
+    for (u32 m : {0u, 1u, 2u, 4u, 16u}) run_lce(t, e, pairs, m, m != 2, false);
+    EXPECT(n < 2 || esa_seen[4] > turns);
+    run_find(t, e, subs, 7, false);
+    if (n <= 40 || g_texts % 5 == 0)
+        for (u32 outs = 1; outs < 7; outs++) run_find(t, e, subs, outs, false);     // each combination of null outputs
+    run_compare(t, e, quads, true, false);
+    run_compare(t, e, quads, false, false);
+    // queries that leave the text, among ones that do not
+    {
+        std::vector<Pair> bad_pairs = {{0, 0}, {n + 1, 0}, {0, n + 1}, {0xffffffffu, 0xffffffffu}, {n, n}, {0x80000000u, n}};
+        run_lce(t, e, bad_pairs, 3, true, true);
+        std::vector<Pair> bad_subs = {{0, n}, {n + 1, 0}, {0, n + 1}, {n, 1}, {1, 0xffffffffu}, {0xffffffffu, 2}, {n, 0}, {5, 0xfffffffcu}};
+        if (n == 0) bad_subs.pop_back(), bad_subs.push_back({0, 2});
+        run_find(t, e, bad_subs, 7, true);
+        std::vector<Quad> bad_quads = {{0, n, 0, n}, {n + 1, 0, 0, 0}, {0, 0, n + 1, 0}, {0, n + 1, 0, 0}, {0, 0, 0, n + 1},
+                                       {n, 1, 0, 0}, {0, 0, 0xffffffffu, 0xffffffffu}, {n, 0, n, 0}};
+        run_compare(t, e, bad_quads, true, true);
+    }
+    if (lf == 2) {
+        for (u32 v = 0; v <= FM_MS_MAXLEV; v++) {
+            g_down[v] += fm_ms_climbed[0][v];
+            g_up[v] += fm_ms_climbed[1][v];
+            g_min[v] += lz_climbed[v];
+        }
+        g_maxlev4 = std::max(g_maxlev4, e.nlev);
+    }
+    g_texts++;
+}
+
+static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
+    Bytes t(n);
+    for (u8 &b : t) b = sigma > 4 ? (u8)(rng() % sigma + 1) : (u8)("ACGT"[rng() % sigma]);
+    return t;
+}
+static Bytes periodic(u32 n, u32 p) {
+    Bytes t(n);
+    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
+    return t;
+}
+static Bytes fibonacci(u32 n) {
+    std::string a = "A", b = "AB";
+    while (b.size() < n) {
+        const std::string c = b + a;
+        a = b;
+        b = c;
+    }
+    return Bytes(b.begin(), b.begin() + n);
+}
+
+int main() {
+    std::mt19937 rng(0xE5A);
+    for (u32 lf : {2u, 6u}) {
+        check_text(Bytes(), lf, 0, rng);
+        for (u32 n : {1u, 2u, 3u, 5u, 8u, 9u, 13u, 17u, 24u, 40u, 63u, 64u, 65u, 257u, 300u, 640u, 1100u, 2200u}) {
+            check_text(Bytes(n, 'A'), lf, 1, rng);
+            for (u32 p : {2u, 3u, 7u}) check_text(periodic(n, p), lf, p, rng);
+            check_text(fibonacci(n), lf, 0, rng);
+            for (u32 sigma : {2u, 4u, 200u}) check_text(random_text(rng, n, sigma), lf, 0, rng);
+            if (n > 1100) continue;
+            Bytes twice = random_text(rng, n, 4);   // a text followed by its own copy; a text whose last byte is new
+            twice.insert(twice.end(), twice.begin(), twice.begin() + n);
+            check_text(twice, lf, n, rng);
+            twice.back() = 'Z';
+            check_text(twice, lf, n, rng);
+        }
+        // one wide group that does not hold position 0: the upward search and the range minimum over sa scan the top level of the
+        // fan-out-4 tree
+        Bytes wide(2601, 'A');
+        wide[0] = 'B';
+        check_text(wide, lf, 1, rng);
+    }
+    for (u32 v = 0; v <= g_maxlev4; v++) EXPECT(g_down[v] > 0 && g_up[v] > 0 && g_min[v] > 0);     // every level of the fan-out-4 tree
+    EXPECT(g_maxlev4 >= 5);
+    EXPECT(esa_seen[0] > 0 && esa_seen[1] > 0);     // the direct compare and the range minimum each decided an extension
+    EXPECT(esa_seen[2] > 0 && esa_seen[3] > 0);     // the clamp fired, behind a range minimum and behind a direct compare
+    EXPECT(esa_seen[4] > 0);                        // all m + 1 turns taken
+    EXPECT(esa_seen[5] > 0 && esa_seen[6] > 0 && esa_seen[7] > 0);     // a == b, position n, len = 0
+    EXPECT(esa_seen[8] > 0 && esa_seen[8] == g_refused);                // every query that leaves the text was refused, no other
+    EXPECT(g_pos0 && g_posn1 && g_posn && g_len0 && g_lenn && g_once);
+    std::printf("ok: the queries on the kept ESA of %llu texts: %llu extensions, %llu finds, %llu compares, %llu refused; every tree "
+                "level reached at fan-out 4 (%u levels) by both searches and by the range minimum\n",
+                (unsigned long long)g_texts, (unsigned long long)g_lce, (unsigned long long)g_find, (unsigned long long)g_cmp,
+                (unsigned long long)g_refused, g_maxlev4);
+    return 0;
+}

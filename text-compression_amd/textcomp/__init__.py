@@ -1301,6 +1301,21 @@ class Context:
             self._check(self.lib.tc_fm_build_sampled_dev(self.handle, p, d_text.numel(), int(sa_rate), C.byref(h)))
         return FMIndexHandle(self, None, _handle=h, _n=d_text.numel())
 
+    # ----------------------------------------------------------- the kept enhanced suffix array
+    def esa_build(self, text):
+        """the enhanced suffix array of text, kept on the device for any number of queries and analyses: tc_esa_build"""
+        return ESAHandle(self, text)
+
+    def esa_build_dev(self, d_text):
+        """the same of a text that already lies in HBM (a torch uint8 tensor on this context's device; the handle keeps its
+        own copy): tc_esa_build_dev"""
+        import torch
+        torch.cuda.synchronize()
+        h = C.c_void_p()
+        p = C.c_void_p(d_text.data_ptr()) if d_text.numel() else None
+        self._check(self.lib.tc_esa_build_dev(self.handle, p, d_text.numel(), C.byref(h)))
+        return ESAHandle(self, None, _handle=h)
+
 
 class FMIndexHandle:
     """`tc_fm`: the device-resident FM-index of one text."""
@@ -1763,6 +1778,198 @@ class FMIndexHandle:
             raise TcError(rc, "tc_fm_info")
         return dict(N=int(N.value), sigma=int(sig.value), c_sym=cs[:sig.value].copy(),
                     c_val=cv[:sig.value].copy(), primary=int(prim.value))
+
+
+class ESAHandle:
+    """`tc_esa`: the device-resident enhanced suffix array of one text -- the text, sa, isa, lcp and two min trees -- built
+    once.  Queries may come from any Context on the handle's device (ctx=...); by default from the one that built it."""
+
+    WHAT = {"text": _lib.TC_ESA_TEXT, "sa": _lib.TC_ESA_SA, "isa": _lib.TC_ESA_ISA, "lcp": _lib.TC_ESA_LCP}
+
+    def __init__(self, ctx, text, _handle=None):
+        self._ctx = ctx
+        if _handle is None:
+            t = _u8(text)
+            _handle = C.c_void_p()
+            ctx._check(ctx.lib.tc_esa_build(ctx.handle, _ptr(t) if len(t) else None, len(t), C.byref(_handle)))
+        self._h = _handle
+        self.n = int(ctx.lib.tc_esa_n(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._ctx.lib.tc_esa_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def device_bytes(self, part=0):
+        """device bytes the handle holds: part 0 = everything, 1 = the text, 2 = sa, 3 = isa, 4 = lcp and its min tree,
+        5 = the min tree of sa"""
+        return int(self._ctx.lib.tc_esa_device_bytes(self._h, int(part)))
+
+    def _what(self, what):
+        w = self.WHAT.get(what, what)
+        if w not in self.WHAT.values():
+            raise ValueError("what is 'text', 'sa', 'isa' or 'lcp', not %r" % (what,))
+        return w
+
+    def _range(self, w, first, count):
+        have = self.n if w == _lib.TC_ESA_TEXT else self.n + 1
+        return int(first), int(have - first if count is None else count)
+
+    def read(self, what, first=0, count=None, ctx=None):
+        """entries [first, first + count) of 'text' (uint8) or 'sa', 'isa', 'lcp' (uint32) -> numpy array: tc_esa_read"""
+        ctx = ctx or self._ctx
+        w = self._what(what)
+        first, count = self._range(w, first, count)
+        out = np.empty(max(count, 0), np.uint8 if w == _lib.TC_ESA_TEXT else np.uint32)
+        ctx._check(ctx.lib.tc_esa_read(ctx.handle, self._h, w, first, count & (2 ** 64 - 1), _ptr(out) if len(out) else None, 0))
+        return out
+
+    def read_dev(self, what, first=0, count=None, ctx=None):
+        """the same to a fresh tensor on the device (uint8, or int32 holding the 32-bit entries)"""
+        import torch
+        ctx = ctx or self._ctx
+        w = self._what(what)
+        first, count = self._range(w, first, count)
+        out = torch.empty(max(count, 0), dtype=torch.uint8 if w == _lib.TC_ESA_TEXT else torch.int32, device="cuda:%d" % ctx.device)
+        torch.cuda.synchronize()
+        ctx._check(ctx.lib.tc_esa_read(ctx.handle, self._h, w, first, count & (2 ** 64 - 1),
+                                       C.c_void_p(out.data_ptr()) if out.numel() else None, 1))
+        return out
+
+    @staticmethod
+    def _u32s(*arrays):
+        out = [np.ascontiguousarray(a, dtype=np.uint32).ravel() for a in arrays]
+        if any(len(a) != len(out[0]) for a in out):
+            raise ValueError("the query arrays must have one length")
+        return out
+
+    @staticmethod
+    def _i32s(*tensors):
+        import torch
+        for t in tensors:
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != tensors[0].numel():
+                raise ValueError("the query tensors must be contiguous int32 tensors of one length")
+        return [C.c_void_p(t.data_ptr()) if t.numel() else None for t in tensors]
+
+    def lce(self, a, b, max_mismatch=0, mm=False, ctx=None):
+        """len[q] = how far the positions a[q] and b[q] (0 .. n) agree with at most max_mismatch mismatches -> uint32 array, or
+        (len, mismatches) with mm=True: tc_esa_lce"""
+        ctx = ctx or self._ctx
+        a, b = self._u32s(a, b)
+        ln = np.zeros(len(a), np.uint32)
+        m = np.zeros(len(a), np.uint32) if mm else None
+        ctx._check(ctx.lib.tc_esa_lce(ctx.handle, self._h, _ptr(a), _ptr(b), len(a), int(max_mismatch), _ptr(ln), _ptr(m)))
+        return (ln, m) if mm else ln
+
+    def lce_dev(self, d_a, d_b, max_mismatch=0, mm=False, ctx=None):
+        """the same on int32 tensors resident on the device -> int32 tensor(s): tc_esa_lce_dev"""
+        import torch
+        ctx = ctx or self._ctx
+        pa, pb = self._i32s(d_a, d_b)
+        nq = d_a.numel()
+        ln = torch.zeros(nq, dtype=torch.int32, device=d_a.device)
+        m = torch.zeros(nq, dtype=torch.int32, device=d_a.device) if mm else None
+        torch.cuda.synchronize()
+        ctx._check(ctx.lib.tc_esa_lce_dev(ctx.handle, self._h, pa, pb, nq, int(max_mismatch),
+                                          C.c_void_p(ln.data_ptr()) if nq else None, C.c_void_p(m.data_ptr()) if mm and nq else None))
+        return (ln, m) if mm else ln
+
+    def find(self, start, length, first_pos=True, ctx=None):
+        """the substrings text[start[q] : start[q] + length[q]] -> (first_row, occ[, first_pos]), uint32 arrays: the suffix-array
+        interval [first_row, first_row + occ) and the earliest occurrence: tc_esa_find"""
+        ctx = ctx or self._ctx
+        s, l = self._u32s(start, length)
+        out = [np.zeros(len(s), np.uint32) for _ in range(3 if first_pos else 2)]
+        ctx._check(ctx.lib.tc_esa_find(ctx.handle, self._h, _ptr(s), _ptr(l), len(s), _ptr(out[0]), _ptr(out[1]),
+                                       _ptr(out[2]) if first_pos else None))
+        return tuple(out)
+
+    def find_dev(self, d_start, d_length, first_pos=True, ctx=None):
+        """the same on int32 tensors resident on the device -> int32 tensors: tc_esa_find_dev"""
+        import torch
+        ctx = ctx or self._ctx
+        ps, pl = self._i32s(d_start, d_length)
+        nq = d_start.numel()
+        out = [torch.zeros(nq, dtype=torch.int32, device=d_start.device) for _ in range(3 if first_pos else 2)]
+        po = [C.c_void_p(o.data_ptr()) if nq else None for o in out] + ([] if first_pos else [None])
+        torch.cuda.synchronize()
+        if nq:
+            ctx._check(ctx.lib.tc_esa_find_dev(ctx.handle, self._h, ps, pl, nq, *po))
+        return tuple(out)
+
+    def compare(self, a_start, a_len, b_start, b_len, common=False, ctx=None):
+        """order[q] = -1, 0, 1 as text[a_start : a_start + a_len] sorts before, equals, sorts behind text[b_start : b_start + b_len]
+        -> int8 array, or (order, common prefix lengths) with common=True: tc_esa_compare"""
+        ctx = ctx or self._ctx
+        a, la, b, lb = self._u32s(a_start, a_len, b_start, b_len)
+        order = np.zeros(len(a), np.int8)
+        c = np.zeros(len(a), np.uint32) if common else None
+        ctx._check(ctx.lib.tc_esa_compare(ctx.handle, self._h, _ptr(a), _ptr(la), _ptr(b), _ptr(lb), len(a), _ptr(order), _ptr(c)))
+        return (order, c) if common else order
+
+    def compare_dev(self, d_a_start, d_a_len, d_b_start, d_b_len, common=False, ctx=None):
+        """the same on int32 tensors resident on the device -> int8 tensor (and int32 tensor): tc_esa_compare_dev"""
+        import torch
+        ctx = ctx or self._ctx
+        ps = self._i32s(d_a_start, d_a_len, d_b_start, d_b_len)
+        nq = d_a_start.numel()
+        order = torch.zeros(nq, dtype=torch.int8, device=d_a_start.device)
+        c = torch.zeros(nq, dtype=torch.int32, device=d_a_start.device) if common else None
+        torch.cuda.synchronize()
+        ctx._check(ctx.lib.tc_esa_compare_dev(ctx.handle, self._h, *ps, nq, C.c_void_p(order.data_ptr()) if nq else None,
+                                              C.c_void_p(c.data_ptr()) if common and nq else None))
+        return (order, c) if common else order
+
+    # ---- further analyses on the arrays the handle keeps: the sort is paid once
+    def arrays(self):
+        """-> (d_text, d_sa, d_lcp, d_isa): the device addresses of the handle's arrays, valid until close: tc_esa_arrays"""
+        p = [C.c_void_p() for _ in range(4)]
+        rc = self._ctx.lib.tc_esa_arrays(self._h, *(C.byref(x) for x in p))
+        if rc != 0:
+            raise TcError(rc, "tc_esa_arrays")
+        return tuple(x.value for x in p)
+
+    def kmers(self, k, min_occ=1, max_occ=0, cap=None, ctx=None):
+        """the k-mers of the text -> (pos, occ, row), int32 tensors on the device, as Context.kmers_dev answers them, from the
+        handle's sa and lcp: tc_kmers_esa_dev"""
+        ctx = ctx or self._ctx
+        _, psa, plcp, _ = self.arrays()
+        N = self.n + 1
+        return ctx._kmers_retry(lambda p, o, r, nk: ctx.lib.tc_kmers_esa_dev(ctx.handle, psa, plcp, N, k, min_occ, max_occ, p, o, r, nk),
+                                "cuda:%d" % ctx.device, cap)
+
+    def kmer_spectrum(self, k, bins=256, ctx=None):
+        """-> (hist, an int64 tensor of `bins` entries on the device, distinct, total): tc_kmer_spectrum_esa_dev"""
+        import torch
+        ctx = ctx or self._ctx
+        _, psa, plcp, _ = self.arrays()
+        d_hist = torch.empty(max(bins, 1), dtype=torch.int64, device="cuda:%d" % ctx.device)
+        distinct, total = C.c_uint64(), C.c_uint64()
+        torch.cuda.synchronize()
+        ctx._check(ctx.lib.tc_kmer_spectrum_esa_dev(ctx.handle, psa, plcp, self.n + 1, k, bins, C.c_void_p(d_hist.data_ptr()),
+                                                    C.byref(distinct), C.byref(total)))
+        return d_hist, int(distinct.value), int(total.value)
+
+    def kmer_profile(self, kmax, unique=True, ctx=None):
+        """-> (distinct, unique), uint64 host arrays of kmax entries: tc_kmer_profile_esa_dev"""
+        ctx = ctx or self._ctx
+        _, _, plcp, _ = self.arrays()
+        d = np.empty(max(kmax, 1), np.uint64)
+        u = np.empty(max(kmax, 1), np.uint64) if unique else None
+        ctx._check(ctx.lib.tc_kmer_profile_esa_dev(ctx.handle, plcp, self.n + 1, kmax, _ptr(d), _ptr(u) if unique else None))
+        return d[:kmax], (u[:kmax] if unique else None)
 
 
 _DEFAULT = None

@@ -20,6 +20,8 @@ TC_MAX_N = 0x7ffffff0
 TC_REPEAT_MAXIMAL, TC_REPEAT_SUPERMAXIMAL = 0, 1
 TC_COVER_ALL, TC_COVER_LATER = 0, 1
 TC_PAL_MAX_MISMATCH = 16
+TC_ESA_MAX_MISMATCH = 16
+TC_ESA_TEXT, TC_ESA_SA, TC_ESA_ISA, TC_ESA_LCP = 1, 2, 3, 4   # `what` of tc_esa_read
 TC_LCP_SHORT_CAP = 256   # csrc/tc_lcp.hpp: comparisons of the LCP array longer than this leave the one-lane kernel
 
 ERR_NAMES = {-1: "TC_ERR_ARG", -2: "TC_ERR_CAPACITY", -3: "TC_ERR_MALFORMED", -4: "TC_ERR_HIP",
@@ -111,6 +113,19 @@ SYMBOLS = [
     ("tc_cover_spans_dev", _INT, [_P, _P, _U64, _U32, _P, _P, _PU64, _PU64]),
     ("tc_cover_mask_dev", _INT, [_P, _P, _P, _U64, _U32, _P, _P, _PU64]),
     ("tc_cover_dedup_dev", _INT, [_P, _P, _P, _U64, _U32, _P, _PU64, _PU64]),
+    ("tc_esa_build", _INT, [_P, _P, _U64, C.POINTER(_P)]),
+    ("tc_esa_build_dev", _INT, [_P, _P, _U64, C.POINTER(_P)]),
+    ("tc_esa_free", None, [_P]),
+    ("tc_esa_n", _U64, [_P]),
+    ("tc_esa_device_bytes", _U64, [_P, _INT]),
+    ("tc_esa_arrays", _INT, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    ("tc_esa_read", _INT, [_P, _P, _INT, _U64, _U64, _P, _INT]),
+    ("tc_esa_lce", _INT, [_P, _P, _P, _P, _U64, _U32, _P, _P]),
+    ("tc_esa_lce_dev", _INT, [_P, _P, _P, _P, _U64, _U32, _P, _P]),
+    ("tc_esa_find", _INT, [_P, _P, _P, _P, _U64, _P, _P, _P]),
+    ("tc_esa_find_dev", _INT, [_P, _P, _P, _P, _U64, _P, _P, _P]),
+    ("tc_esa_compare", _INT, [_P, _P, _P, _P, _P, _P, _U64, _P, _P]),
+    ("tc_esa_compare_dev", _INT, [_P, _P, _P, _P, _P, _P, _U64, _P, _P]),
     ("tc_kmers", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_esa_dev", _INT, [_P, _P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _PU64]),
