@@ -1,7 +1,7 @@
 // tc_cov_host.hpp -- host side of the repeat cover (tc_cov.hpp has the kernels and the method): scratch, the launch sequence, and
 // the bodies of tc_repeat_spans / tc_repeat_mask / tc_repeat_dedup, their _dev forms and the three tc_cover_*_dev calls over a
-// caller's array of lengths.  Included by textcomp.hip after tc_sus_host.hpp; it follows the ESA plan of sus_prepare (sa_build,
-// then lcp_device over the sort's dead buffers) and calls lz_build_tree.
+// caller's array of lengths.  Included by textcomp.hip after tc_esa_plan.hpp: the ESA is esa_plan's, with nothing kept but sa
+// and lcp.
 #pragma once
 #include "tc_cov.hpp"
 
@@ -27,20 +27,15 @@ struct CovCore {
 // returns ahead of the overlay mark; behind it, over the sort's and then the LCP's dead buffers, len (4 bytes per text byte), the
 // min tree of lcp (4 / (f - 1); only where a row is searched: q > 2, or LATER), that of sa (the same; LATER only) and the core's
 // tiles: 12 bytes per text byte and a little -- the sort's own need behind the first 8 where that is larger.
-struct CovWork {
-    u8 *d_text = nullptr;
-    u32 *d_sa = nullptr, *d_lcp = nullptr;
-    LcpScratch lcp_ws;
-    u32 lf = 0, tree_levels = 0, tree_words = 0;    // the trees are over the N = n + 1 rows
-    u32 tree_off[FM_MS_MAXLEV + 1], tree_cnt[FM_MS_MAXLEV + 1];
+struct CovWork : Esa {
+    MinTree tree;           // both trees are over the N = n + 1 rows
     u32 *len = nullptr, *lcp_min = nullptr, *sa_min = nullptr;
     CovCore core;
     void carve(const tc_ctx *ctx, Arena &A, u64 n, bool search, bool later) {
         len = A.get<u32>(n);
-        lf = fm_log2(ctx->fm_lcp_fanout ? ctx->fm_lcp_fanout : FM_LCP_FANOUT);
-        tree_levels = fm_ms_tree_shape((u32)(n + 1), lf, tree_off, tree_cnt, &tree_words);
-        if (search) lcp_min = A.get<u32>(tree_words);
-        if (later) sa_min = A.get<u32>(tree_words);
+        tree.shape(ctx, (u32)(n + 1));
+        if (search) lcp_min = A.get<u32>(tree.words);
+        if (later) sa_min = A.get<u32>(tree.words);
         core.carve(A, n);
     }
 };
@@ -164,40 +159,6 @@ static void cov_finish(tc_ctx *ctx, const CovCore &C, const u32 *d_len, const u8
     tc_sync_check(ctx);
 }
 
-// The ESA of the text (n >= 1) on the context's stream, as sus_prepare builds it.  outputs(A) carves what a host form returns,
-// ahead of everything that is overlaid.
-template <class F>
-static void cov_prepare(tc_ctx *ctx, CovWork &W, const u8 *text, u64 n, bool dev, bool search, bool later, F &&outputs) {
-    const u64 N = n + 1;
-    ctx->stats = tc_stats{};
-    ctx->stats.n = n; ctx->stats.N = N;
-    u64 primary = 0;
-    auto plan = [&](Arena &A, bool dry) {
-        W.d_text = dev ? const_cast<u8 *>(text) : A.get<u8>(n + 16);
-        u32 *p = A.get<u32>(N);     // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
-        W.d_sa = dry ? reinterpret_cast<u32 *>(sizeof(u32)) : p;
-        W.d_lcp = A.get<u32>(N);
-        outputs(A);
-        const size_t mark = A.off;
-        u8 *d_L = A.get<u8>(N + 16);    // behind the mark: the last column dies with the sort
-        sa_build(ctx, A, W.d_text, n, W.d_sa, d_L, &primary, nullptr, dry);
-        A.rewind(mark);
-        W.lcp_ws.carve(ctx, A, n);
-        A.rewind(mark);
-        W.carve(ctx, A, n, search, later);
-    };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.peak);
-    if (!dev) {     // the text is the first carve: upload it between the reserve and the run, as lcp_array_host_entry does
-        Arena A0(ctx->ws);
-        tc_h2d(ctx, A0.get<u8>(n + 16), text, n);
-    }
-    Arena A(ctx->ws);
-    plan(A, false);
-    lcp_device(ctx, W.lcp_ws, W.d_text, n, W.d_sa, W.d_lcp);
-}
-
 // tc_repeat_spans, tc_repeat_mask, tc_repeat_dedup and their _dev forms
 static void repeat_cover_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 min_len, u32 min_occ, u32 kind, CovCall c, bool dev) {
     if (min_occ < 2) TC_FAIL(ctx, TC_ERR_ARG, "min_occ is at least 2");
@@ -213,26 +174,28 @@ static void repeat_cover_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 min_len, 
     u8 *d_out = c.out;
     const u64 slots = c.cap < n ? c.cap : n;
     CovWork W;
-    cov_prepare(ctx, W, text, n, dev, search, later, [&](Arena &A) {
-        if (dev) return;
-        if (c.what == COV_SPANS && !c.sizes_only) {
-            d_start = A.get<u32>(slots + 1);
-            d_slen = A.get<u32>(slots + 1);
-        } else if (c.what == COV_MASK) {
-            d_out = A.get<u8>(n + 16);
-        } else if (c.what == COV_DEDUP && !c.sizes_only) {
-            d_out = A.get<u8>(slots + 16);
-        }
-    });
+    esa_plan(ctx, W, text, n, dev,
+             [&](Arena &A) {
+                 if (dev) return;
+                 if (c.what == COV_SPANS && !c.sizes_only) {
+                     d_start = A.get<u32>(slots + 1);
+                     d_slen = A.get<u32>(slots + 1);
+                 } else if (c.what == COV_MASK) {
+                     d_out = A.get<u8>(n + 16);
+                 } else if (c.what == COV_DEDUP && !c.sizes_only) {
+                     d_out = A.get<u8>(slots + 16);
+                 }
+             },
+             [&](Arena &A) { W.carve(ctx, A, n, search, later); });
     const u64 N = n + 1;
     tc_memset_async(ctx, W.len, 0, n * sizeof(u32));
-    if (search) lz_build_tree(ctx, W, W.d_lcp, W.lcp_min);
+    if (search) W.tree.build(ctx, W.d_lcp, W.lcp_min);
     if (later) {
-        lz_build_tree(ctx, W, W.d_sa, W.sa_min);
-        cov_seed_kernel<true><<<tc_cdiv(N, FM_MS_NT), FM_MS_NT, 0, ctx->stream>>>(W.d_sa, W.d_lcp, W.sa_min, W.lcp_min, (u32)N, W.lf, min_len,
+        W.tree.build(ctx, W.d_sa, W.sa_min);
+        cov_seed_kernel<true><<<tc_cdiv(N, FM_MS_NT), FM_MS_NT, 0, ctx->stream>>>(W.d_sa, W.d_lcp, W.sa_min, W.lcp_min, (u32)N, W.tree.lf, min_len,
                                                                                  min_occ, W.len);
     } else {
-        cov_seed_kernel<false><<<tc_cdiv(N, FM_MS_NT), FM_MS_NT, 0, ctx->stream>>>(W.d_sa, W.d_lcp, nullptr, W.lcp_min, (u32)N, W.lf, min_len,
+        cov_seed_kernel<false><<<tc_cdiv(N, FM_MS_NT), FM_MS_NT, 0, ctx->stream>>>(W.d_sa, W.d_lcp, nullptr, W.lcp_min, (u32)N, W.tree.lf, min_len,
                                                                                   min_occ, W.len);
     }
     TC_LAUNCH_CHECK(ctx);

@@ -1,7 +1,7 @@
 // tc_esa_host.hpp -- host side of the kept enhanced suffix array (tc_esa.hpp has the kernels and the method): the handle, its
 // build, tc_esa_read, and the bodies of tc_esa_lce / tc_esa_find / tc_esa_compare and their _dev forms.  Included by textcomp.hip
-// after tc_cov_host.hpp; the build is the ESA plan of cov_prepare (sa_build, then lcp_device over the sort's dead buffers) with
-// the handle's own arrays as its outputs, then tr_isa_kernel and lz_build_tree twice.
+// after tc_esa_plan.hpp; the build is its lower layer (esa_sort: the workspace holds scratch only, the arrays are the handle's
+// own), then lcp_device, tr_isa_kernel and the two min trees.
 #pragma once
 #include "tc_esa.hpp"
 
@@ -13,15 +13,14 @@ static_assert(TC_ESA_MAX_MISMATCH == ESA_MAX_MISMATCH, "esa_lce_kernel takes at 
 struct tc_esa {
     int device = 0;
     u64 n = 0, N = 0;
-    u32 lf = 0, tree_levels = 0, tree_words = 0;        // both trees are over the N rows: one shape
-    u32 tree_off[FM_MS_MAXLEV + 1], tree_cnt[FM_MS_MAXLEV + 1];
+    MinTree tree;               // both trees are over the N rows: one shape
     u8 *d_text = nullptr;
     u32 *d_sa = nullptr, *d_isa = nullptr, *d_lcp = nullptr, *d_lcp_min = nullptr, *d_sa_min = nullptr;
 };
 
 static u64 esa_text_bytes(const tc_esa *e) { return (e->n + 16 + 15) & ~(u64)15; }
 static u64 esa_rows_bytes(const tc_esa *e) { return (e->N * sizeof(u32) + 15) & ~(u64)15; }
-static u64 esa_tree_bytes(const tc_esa *e) { return (u64)e->tree_words * sizeof(u32); }
+static u64 esa_tree_bytes(const tc_esa *e) { return (u64)e->tree.words * sizeof(u32); }
 
 static void esa_release(tc_esa *e) {
     if (!e) return;
@@ -60,8 +59,7 @@ static void esa_build_entry(tc_ctx *ctx, const u8 *text, u64 n, tc_esa **out, bo
     e->N = N;
     try {
         hipStream_t s = ctx->stream;
-        e->lf = fm_log2(ctx->fm_lcp_fanout ? ctx->fm_lcp_fanout : FM_LCP_FANOUT);
-        e->tree_levels = fm_ms_tree_shape((u32)N, e->lf, e->tree_off, e->tree_cnt, &e->tree_words);
+        e->tree.shape(ctx, (u32)N);
         TC_HIP(ctx, hipMalloc((void **)&e->d_text, esa_text_bytes(e)));
         TC_HIP(ctx, hipMalloc((void **)&e->d_sa, esa_rows_bytes(e)));
         TC_HIP(ctx, hipMalloc((void **)&e->d_isa, esa_rows_bytes(e)));
@@ -74,14 +72,8 @@ static void esa_build_entry(tc_ctx *ctx, const u8 *text, u64 n, tc_esa **out, bo
             else tc_h2d(ctx, e->d_text, text, n);
             ctx->stats = tc_stats{};
             ctx->stats.n = n; ctx->stats.N = N;
-            u64 primary = 0;
             LcpScratch lcp_ws;
-            tc_ws_plan(ctx, 0, [&](Arena &A, bool dry) {        // the workspace holds scratch only
-                u8 *d_L = A.get<u8>(N + 16);                    // the last column dies with the sort
-                sa_build(ctx, A, e->d_text, n, e->d_sa, d_L, &primary, nullptr, dry);
-                A.rewind(0);
-                lcp_ws.carve(ctx, A, n);
-            });
+            tc_ws_plan(ctx, 0, [&](Arena &A, bool dry) { esa_sort(ctx, A, e->d_text, n, e->d_sa, lcp_ws, dry); });
             lcp_device(ctx, lcp_ws, e->d_text, n, e->d_sa, e->d_lcp);
         } else {    // the one-row ESA, as tc_suffix_array_dev and tc_lcp_array_dev make it
             tc_memset_async(ctx, e->d_sa, 0, sizeof(u32));
@@ -89,8 +81,8 @@ static void esa_build_entry(tc_ctx *ctx, const u8 *text, u64 n, tc_esa **out, bo
         }
         tr_isa_kernel<<<tc_cdiv(N, TR_NT), TR_NT, 0, s>>>(e->d_sa, (u32)N, e->d_isa, ctx->d_err);
         TC_LAUNCH_CHECK(ctx);
-        lz_build_tree(ctx, *e, e->d_lcp, e->d_lcp_min);
-        lz_build_tree(ctx, *e, e->d_sa, e->d_sa_min);
+        e->tree.build(ctx, e->d_lcp, e->d_lcp_min);
+        e->tree.build(ctx, e->d_sa, e->d_sa_min);
         tc_sync_check(ctx);
     } catch (...) {
         esa_release(e);
@@ -161,7 +153,7 @@ static void esa_lce_entry(tc_ctx *ctx, const tc_esa *e, const u32 *a, const u32 
     void *out[2] = {len, mm};
     const u32 size[2] = {4, 4};
     esa_run_batch(ctx, in, 2, out, size, 2, nq, dev, [&](const EsaBatch &B) {
-        esa_lce_kernel<<<tc_cdiv(nq, FM_MS_NT), FM_MS_NT, 0, ctx->stream>>>(e->d_text, (u32)e->n, e->d_isa, e->d_lcp, e->d_lcp_min, e->lf, B.in[0],
+        esa_lce_kernel<<<tc_cdiv(nq, FM_MS_NT), FM_MS_NT, 0, ctx->stream>>>(e->d_text, (u32)e->n, e->d_isa, e->d_lcp, e->d_lcp_min, e->tree.lf, B.in[0],
                                                                           B.in[1], nq, max_mismatch, static_cast<u32 *>(B.out[0]),
                                                                           static_cast<u32 *>(B.out[1]), B.d_bad);
     });
@@ -179,7 +171,7 @@ static void esa_find_entry(tc_ctx *ctx, const tc_esa *e, const u32 *start, const
     const u32 size[3] = {4, 4, 4};
     esa_run_batch(ctx, in, 2, out, size, 3, nq, dev, [&](const EsaBatch &B) {
         esa_find_kernel<<<tc_cdiv(nq, FM_MS_NT), FM_MS_NT, 0, ctx->stream>>>((u32)e->n, e->d_sa, e->d_isa, e->d_lcp, e->d_sa_min, e->d_lcp_min,
-                                                                           e->lf, B.in[0], B.in[1], nq, static_cast<u32 *>(B.out[0]),
+                                                                           e->tree.lf, B.in[0], B.in[1], nq, static_cast<u32 *>(B.out[0]),
                                                                            static_cast<u32 *>(B.out[1]), static_cast<u32 *>(B.out[2]),
                                                                            B.d_bad);
     });
@@ -195,7 +187,7 @@ static void esa_compare_entry(tc_ctx *ctx, const tc_esa *e, const u32 *a_start, 
     void *out[2] = {order, common};
     const u32 size[2] = {1, 4};
     esa_run_batch(ctx, in, 4, out, size, 2, nq, dev, [&](const EsaBatch &B) {
-        esa_compare_kernel<<<tc_cdiv(nq, FM_MS_NT), FM_MS_NT, 0, ctx->stream>>>(e->d_text, (u32)e->n, e->d_isa, e->d_lcp, e->d_lcp_min, e->lf,
+        esa_compare_kernel<<<tc_cdiv(nq, FM_MS_NT), FM_MS_NT, 0, ctx->stream>>>(e->d_text, (u32)e->n, e->d_isa, e->d_lcp, e->d_lcp_min, e->tree.lf,
                                                                               B.in[0], B.in[1], B.in[2], B.in[3], nq,
                                                                               static_cast<signed char *>(B.out[0]),
                                                                               static_cast<u32 *>(B.out[1]), B.d_bad);

@@ -533,6 +533,8 @@ __global__ __launch_bounds__(256) void fm_extract_walk_kernel(const u64 *__restr
 #include "tc_fm_mm.hpp"   // fm_mm_kernel: count / locate within Hamming distance k
 #include "tc_fm_factor.hpp"   // fm_factor_kernel: the longest-match parse; the small kernels of its inverse
 #include "tc_fm_ms.hpp"   // fm_ms_kernel: matching statistics; the min tree over the LCP array; the small kernels of the MEMs
+static inline u32 fm_log2(u32 v) { return 31u - (u32)__builtin_clz(v); }   // v: a power of two
+#include "tc_esa_plan.hpp"   // MinTree: the shape and the build of that tree
 
 #endif  // __HIPCC__
 
@@ -593,8 +595,7 @@ static void fm_alloc_bits2(tc_ctx *ctx, tc_fm *fm, size_t bytes) {
 // text_rate k >= 1: the index also keeps the text samples (d_isa), scattered from the same suffix array before it goes.
 // with_lcp: the index also keeps the LCP array and its min tree, made by lcp_device while the text and the full suffix array
 // are still there (both in the workspace on a sampled index); the LCP scratch overlays the sort's buffers, which are dead by
-// then, as in lcp_array_host_entry, so the one dry run sizes the peak of both.
-static inline u32 fm_log2(u32 v) { return 31u - (u32)__builtin_clz(v); }   // v: a power of two
+// then, as in esa_sort (tc_esa_plan.hpp; the carve order here is this build's own), so the one dry run sizes the peak of both.
 static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 *text_dev = nullptr, u32 sa_rate = 1,
                               u32 text_rate = 0, bool with_lcp = false) {
     tc_fm *fm = new tc_fm();
@@ -611,20 +612,17 @@ static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 
         TC_HIP(ctx, hipMalloc((void **)&fm->d_tab, 768 * sizeof(u32)));
         u8 *d_text = nullptr;
         u32 *d_sa = fm->d_sa;
-        u32 tree_off[FM_MS_MAXLEV + 1], tree_cnt[FM_MS_MAXLEV + 1], tree_words = 0, tree_levels = 0;
+        MinTree tree;
         LcpScratch lcp_ws;
         if (with_lcp) {
-            fm->lcp_fan_log2 = fm_log2(ctx->fm_lcp_fanout ? ctx->fm_lcp_fanout : FM_LCP_FANOUT);
-            tree_levels = fm_ms_tree_shape((u32)N, fm->lcp_fan_log2, tree_off, tree_cnt, &tree_words);
-            fm->lmin_words = tree_words;
+            tree.shape(ctx, (u32)N);
+            fm->lcp_fan_log2 = tree.lf;
+            fm->lmin_words = tree.words;
             TC_HIP(ctx, hipMalloc((void **)&fm->d_lcp, N * sizeof(u32)));
-            TC_HIP(ctx, hipMalloc((void **)&fm->d_lmin, (size_t)tree_words * sizeof(u32)));
+            TC_HIP(ctx, hipMalloc((void **)&fm->d_lmin, (size_t)tree.words * sizeof(u32)));
         }
         auto plan = [&](Arena &A, bool dry) {
-            if (sampled) {   // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
-                u32 *p = A.get<u32>(N);
-                d_sa = dry ? reinterpret_cast<u32 *>(sizeof(u32)) : p;
-            }
+            if (sampled) d_sa = esa_sa_arg(A.get<u32>(N), dry);
             if (text_dev) {
                 d_text = const_cast<u8 *>(text_dev);
             } else {
@@ -643,14 +641,7 @@ static tc_fm *fm_build_device(tc_ctx *ctx, const u8 *text_host, u64 n, const u8 
         tc_ws_plan(ctx, 0, plan);
         if (with_lcp) {
             lcp_device(ctx, lcp_ws, d_text, n, d_sa, fm->d_lcp);
-            const u32 *src = fm->d_lcp;
-            for (u32 k = 1; k <= tree_levels; k++) {   // one small kernel per level, each over the one below
-                u32 *dst = fm->d_lmin + tree_off[k];
-                fm_lmin_kernel<<<tc_cdiv(((u64)tree_cnt[k] + 3) & ~(u64)3, 256), 256, 0, s>>>(src, tree_cnt[k - 1], fm->lcp_fan_log2, dst,
-                                                                                            tree_cnt[k]);
-                TC_LAUNCH_CHECK(ctx);
-                src = dst;
-            }
+            tree.build(ctx, fm->d_lcp, fm->d_lmin);
         }
         // C[c] = #symbols of text.'$' smaller than c ('$' = Nothing counts once)
         u32 tab[768];

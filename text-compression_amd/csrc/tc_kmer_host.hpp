@@ -1,8 +1,8 @@
 // tc_kmer_host.hpp -- host side of the k-mer list, spectrum and profile (tc_kmer.hpp has the kernels and the definitions):
 // scratch, the launch sequences, and the bodies of tc_kmers / tc_kmers_dev / tc_kmers_esa_dev, tc_kmer_spectrum /
-// tc_kmer_spectrum_esa_dev and tc_kmer_profile / tc_kmer_profile_esa_dev.  Included by textcomp.hip after tc_rep_host.hpp,
-// whose ESA plan (a dry Arena, sa_build, then lcp_device over the sort's dead buffers) the text forms follow; they keep no
-// last column and build no tree, and then run the launch sequence of the _esa_dev form.
+// tc_kmer_spectrum_esa_dev and tc_kmer_profile / tc_kmer_profile_esa_dev.  Included by textcomp.hip after tc_esa_plan.hpp:
+// the text forms build their ESA by esa_plan (no last column kept, no tree) and then run the launch sequence of the _esa_dev
+// form.
 #pragma once
 #include "tc_kmer.hpp"
 
@@ -54,15 +54,7 @@ static u64 km_list_run(tc_ctx *ctx, const KmWork &W, const u32 *d_sa, const u32 
     km_carries(ctx, W, d_lcp, N, k);
     km_pass_kernel<KM_COUNT><<<W.ntiles, KM_NT, 0, s>>>(d_sa, d_lcp, N, k, min_occ, max_occ, al, W.carry, W.cnt, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
     TC_LAUNCH_CHECK(ctx);
-    const u64 *d_total = tc_scan64(ctx, W.cnt, W.ntiles, W.tsum, W.offs);
-    tc_d2h(ctx, &ctx->h_scalars[9], d_total, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 need = ctx->h_scalars[9];
-    *nk = need;
-    if (need > cap && !sizes_only) {
-        tc_sync_check(ctx);
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu k-mer slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    }
+    const u64 need = tc_read_total(ctx, W.cnt, W.ntiles, W.tsum, W.offs, cap, sizes_only, nk, "k-mer");
     if (!sizes_only && need) {
         km_pass_kernel<KM_FILL><<<W.ntiles, KM_NT, 0, s>>>(d_sa, d_lcp, N, k, min_occ, max_occ, al, W.carry, nullptr, W.offs, d_pos, d_occ, d_row, nullptr, 0, nullptr);
         TC_LAUNCH_CHECK(ctx);
@@ -106,55 +98,6 @@ static void km_profile_run(tc_ctx *ctx, const KmWork &W, const u32 *d_lcp, u64 N
     }
 }
 
-// The ESA of a text in the calling context's workspace, as repeats_entry builds it.  pre(A) carves what outlives the sort
-// (a host form's output arrays), post(A) the scratch over the sort's and the LCP's dead buffers.  n >= 1.
-struct KmEsa {
-    u8 *d_text = nullptr;
-    u32 *d_sa = nullptr, *d_lcp = nullptr;
-    LcpScratch lcp_ws;
-};
-template <class Pre, class Post>
-static void km_build_esa(tc_ctx *ctx, const u8 *text, u64 n, u32 *sa, bool dev, KmEsa &E, Pre &&pre, Post &&post) {
-    const u64 N = n + 1;
-    ctx->stats = tc_stats{};
-    ctx->stats.n = n; ctx->stats.N = N;
-    u64 primary = 0;
-    auto plan = [&](Arena &A, bool dry) {
-        E.d_text = dev ? const_cast<u8 *>(text) : A.get<u8>(n + 16);
-        u32 *p = dev && sa ? sa : A.get<u32>(N);    // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
-        E.d_sa = dry ? reinterpret_cast<u32 *>(sizeof(u32)) : p;
-        E.d_lcp = A.get<u32>(N);
-        pre(A);
-        const size_t mark = A.off;
-        u8 *d_L = A.get<u8>(N + 16);                // behind the mark: the last column dies with the sort
-        sa_build(ctx, A, E.d_text, n, E.d_sa, d_L, &primary, nullptr, dry);
-        A.rewind(mark);
-        E.lcp_ws.carve(ctx, A, n);
-        A.rewind(mark);
-        post(A);
-    };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.peak);
-    if (!dev) {     // the text is the first carve: upload it between the reserve and the run, as lcp_array_host_entry does
-        Arena A0(ctx->ws);
-        tc_h2d(ctx, A0.get<u8>(n + 16), text, n);
-    }
-    Arena A(ctx->ws);
-    plan(A, false);
-    lcp_device(ctx, E.lcp_ws, E.d_text, n, E.d_sa, E.d_lcp);
-}
-
-// n = 0 of a text form: one row, 0, as tc_suffix_array
-static void km_empty_sa(tc_ctx *ctx, u32 *sa, bool dev) {
-    if (sa && dev) {
-        tc_memset_async(ctx, sa, 0, sizeof(u32));
-        tc_sync_check(ctx);
-    } else if (sa) {
-        sa[0] = 0;
-    }
-}
-
 // tc_kmers, tc_kmers_dev
 static void kmers_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 k, u32 min_occ, u32 max_occ, u32 *sa, u32 *kpos, u32 *kocc,
                         u32 *krow, u64 *nk, bool dev) {
@@ -164,24 +107,26 @@ static void kmers_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 k, u32 min_occ, 
     bool sizes_only;
     km_list_args(ctx, k, min_occ, max_occ, kpos, kocc, cap, &sizes_only);
     if (n == 0) {
-        km_empty_sa(ctx, sa, dev);
+        esa_empty_sa(ctx, sa, dev);
         return;
     }
     if (!text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
     const u64 N = n + 1;
     const u64 slots = cap < n ? cap : n;        // (a text of n bytes has at most n k-mers)
     u32 *d_pos = kpos, *d_occ = kocc, *d_row = krow;
-    KmEsa E;
+    Esa E;
     KmWork W;
-    km_build_esa(ctx, text, n, sa, dev, E,
-                 [&](Arena &A) {
-                     if (!dev && !sizes_only) {
-                         d_pos = A.get<u32>(slots + 1);
-                         d_occ = A.get<u32>(slots + 1);
-                         if (krow) d_row = A.get<u32>(slots + 1);
-                     }
-                 },
-                 [&](Arena &A) { W.carve(A, N, true, 0); });
+    EsaOpts o;
+    o.sa = dev ? sa : nullptr;
+    esa_plan(ctx, E, text, n, dev,
+             [&](Arena &A) {
+                 if (!dev && !sizes_only) {
+                     d_pos = A.get<u32>(slots + 1);
+                     d_occ = A.get<u32>(slots + 1);
+                     if (krow) d_row = A.get<u32>(slots + 1);
+                 }
+             },
+             [&](Arena &A) { W.carve(A, N, true, 0); }, o);
     const u64 need = km_list_run(ctx, W, E.d_sa, E.d_lcp, N, k, min_occ, max_occ, d_pos, d_occ, d_row, cap, sizes_only, nk);
     if (!dev && !sizes_only && need) {
         tc_d2h(ctx, kpos, d_pos, need * sizeof(u32));
@@ -224,10 +169,9 @@ static void kmer_spectrum_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 k, u32 b
     if (!text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
     const u64 N = n + 1;
     u64 *d_hist = nullptr;
-    KmEsa E;
+    Esa E;
     KmWork W;
-    km_build_esa(ctx, text, n, nullptr, false, E, [&](Arena &A) { d_hist = A.get<u64>(bins); },
-                 [&](Arena &A) { W.carve(A, N, false, 0); });
+    esa_plan(ctx, E, text, n, false, [&](Arena &A) { d_hist = A.get<u64>(bins); }, [&](Arena &A) { W.carve(A, N, false, 0); });
     km_spectrum_run(ctx, W, E.d_sa, E.d_lcp, N, k, bins, d_hist);
     tc_d2h(ctx, hist, d_hist, (size_t)bins * sizeof(u64));
     tc_d2h(ctx, &ctx->h_scalars[9], W.word, sizeof(u64));
@@ -262,9 +206,9 @@ static void kmer_profile_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 kmax, u64
     }
     if (!text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
     const u64 N = n + 1;
-    KmEsa E;
+    Esa E;
     KmWork W;
-    km_build_esa(ctx, text, n, nullptr, false, E, [](Arena &) {}, [&](Arena &A) { W.carve(A, N, false, kmax); });
+    esa_plan(ctx, E, text, n, false, [](Arena &) {}, [&](Arena &A) { W.carve(A, N, false, kmax); });
     km_profile_run(ctx, W, E.d_lcp, N, kmax, distinct, unique);
 }
 

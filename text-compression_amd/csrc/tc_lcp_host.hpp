@@ -1,6 +1,7 @@
 // tc_lcp_host.hpp -- host side of the LCP array (tc_lcp.hpp has the kernels and the algorithm): scratch, the launch
-// sequence, and the bodies of tc_suffix_array_dev / tc_lcp_array_dev / tc_lcp_array / tc_lcp_summary_dev.  Included by
-// tc_fm_host.hpp (lcp_device makes the LCP part of an index) and textcomp.hip, after tc_encode_host.hpp (sa_build, the copy helpers).
+// sequence, and the bodies of tc_suffix_array_dev / tc_lcp_array_dev / tc_lcp_summary_dev (tc_lcp_array, which sorts first, is
+// in tc_esa_plan.hpp).  Included by tc_fm_host.hpp (lcp_device makes the LCP part of an index) and textcomp.hip, after
+// tc_encode_host.hpp (sa_build, the copy helpers).
 #pragma once
 #include "tc_lcp.hpp"
 
@@ -89,48 +90,6 @@ static void lcp_array_dev_entry(tc_ctx *ctx, const u8 *d_text, u64 n, const u32 
     LcpScratch W;
     tc_ws_plan(ctx, 0, [&](Arena &A, bool) { W.carve(ctx, A, n); });
     lcp_device(ctx, W, d_text, n, d_sa, d_lcp);
-    tc_sync_check(ctx);
-}
-
-// tc_lcp_array: upload, sort, LCP, download.  The LCP scratch overlays the sort's buffers, which are dead by then.
-static void lcp_array_host_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 *sa, u32 *lcp) {
-    if (n > TC_MAX_N || !lcp) TC_FAIL(ctx, TC_ERR_ARG, "bad argument");
-    if (n == 0) {
-        if (sa) sa[0] = 0;
-        lcp[0] = 0;
-        return;
-    }
-    if (!text) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    const u64 N = n + 1;
-    ctx->stats = tc_stats{};
-    ctx->stats.n = n; ctx->stats.N = N;
-    u8 *d_text = nullptr;
-    u32 *d_sa = nullptr, *d_lcp = nullptr;
-    u64 primary = 0;
-    LcpScratch W;
-    auto plan = [&](Arena &A, bool dry) {
-        d_text = A.get<u8>(n + 16);
-        d_sa = A.get<u32>(N);
-        d_lcp = A.get<u32>(N);
-        const size_t mark = A.off;
-        u8 *d_L = A.get<u8>(N + 16);
-        sa_build(ctx, A, d_text, n, d_sa, d_L, &primary, nullptr, dry);
-        A.rewind(mark);
-        W.carve(ctx, A, n);
-    };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.peak);
-    // the text is the first carve: upload it between the reserve and the run, as bwt_host does
-    {
-        Arena A0(ctx->ws);
-        tc_h2d(ctx, A0.get<u8>(n + 16), text, n);
-    }
-    Arena A(ctx->ws);
-    plan(A, false);
-    lcp_device(ctx, W, d_text, n, d_sa, d_lcp);
-    if (sa) tc_d2h(ctx, sa, d_sa, N * sizeof(u32));
-    tc_d2h(ctx, lcp, d_lcp, N * sizeof(u32));
     tc_sync_check(ctx);
 }
 

@@ -1,20 +1,17 @@
 // tc_lz_host.hpp -- host side of the LPF array, the LZ77 parse and its inverse (tc_lz.hpp has the kernels and the
 // algorithm): scratch, the launch sequences, and the bodies of tc_lpf_array / tc_lz_parse / tc_lz_unparse and their _dev
-// forms.  Included by textcomp.hip after tc_lcp_host.hpp (lcp_device, LcpScratch) and tc_fm_host.hpp (the min tree).
+// forms.  Included by textcomp.hip after tc_esa_plan.hpp (esa_plan, MinTree).
 #pragma once
 #include "tc_lz.hpp"
 
 // the tile of this context's parses: LZ_TILE unless the debug interface set another (tc_dbg_lz_set_tile)
 static u32 lz_tile(const tc_ctx *ctx) { return ctx->lz_tile ? ctx->lz_tile : LZ_TILE; }
 
-// What one LPF / parse call holds in the workspace: the text (host forms), the enhanced suffix array, and -- over the
-// sort's and then the LCP's dead buffers -- the two min trees, the packed (lpf, src) array and the parse's tables.
-struct LzWork {
-    u8 *d_text = nullptr;
-    u32 *d_sa = nullptr, *d_lcp = nullptr;
-    LcpScratch lcp_ws;
-    u32 lf = 0, tree_levels = 0, tree_words = 0;
-    u32 tree_off[FM_MS_MAXLEV + 1], tree_cnt[FM_MS_MAXLEV + 1];
+// What one LPF / parse call holds in the workspace: the ESA of esa_plan (tc_esa_plan.hpp) with what the host forms return
+// ahead of the mark, and -- over the sort's and then the LCP's dead buffers -- the two min trees, the packed (lpf, src) array
+// and the parse's tables.
+struct LzWork : Esa {
+    MinTree tree;
     u32 *sa_min = nullptr, *lcp_min = nullptr;
     u64 *pack = nullptr;    // n entries: src << 32 | lpf
     u32 ltile = 0, ntiles = 0;
@@ -22,10 +19,9 @@ struct LzWork {
     u32 *entry = nullptr;   // one word per tile
     u64 *cnt = nullptr, *offs = nullptr, *tsum = nullptr;
     void carve(const tc_ctx *ctx, Arena &A, u64 n, bool parse) {
-        lf = fm_log2(ctx->fm_lcp_fanout ? ctx->fm_lcp_fanout : FM_LCP_FANOUT);
-        tree_levels = fm_ms_tree_shape((u32)(n + 1), lf, tree_off, tree_cnt, &tree_words);
-        sa_min = A.get<u32>(tree_words);
-        lcp_min = A.get<u32>(tree_words);
+        tree.shape(ctx, (u32)(n + 1));
+        sa_min = A.get<u32>(tree.words);
+        lcp_min = A.get<u32>(tree.words);
         pack = A.get<u64>(n);
         if (!parse) return;
         ltile = fm_log2(lz_tile(ctx));
@@ -38,56 +34,14 @@ struct LzWork {
     }
 };
 
-// the min tree over src[0 .. N) into lmin, one small kernel per level, each over the one below (Work: LzWork, or the
-// RepWork of tc_rep_host.hpp -- what holds lf and the tree's shape)
-template <class Work>
-static void lz_build_tree(tc_ctx *ctx, const Work &W, const u32 *src, u32 *lmin) {
-    for (u32 k = 1; k <= W.tree_levels; k++) {
-        u32 *dst = lmin + W.tree_off[k];
-        fm_lmin_kernel<<<tc_cdiv(((u64)W.tree_cnt[k] + 3) & ~(u64)3, 256), 256, 0, ctx->stream>>>(src, W.tree_cnt[k - 1], W.lf, dst,
-                                                                                                W.tree_cnt[k]);
-        TC_LAUNCH_CHECK(ctx);
-        src = dst;
-    }
-}
-
-// Sort, LCP array, the two trees and lz_lpf_kernel, n >= 1, on the context's stream: W.pack holds (lpf, src) of every
-// position afterwards.  text is the caller's device text (dev) or its host text, which becomes the workspace's first
-// carve; outputs(A) carves what the host forms return, ahead of everything that is overlaid.  The LCP scratch overlays
-// the sort's buffers, this file's scratch the LCP's: each is dead by the time the next is written.
+// The ESA, the two trees and lz_lpf_kernel, n >= 1, on the context's stream: W.pack holds (lpf, src) of every position
+// afterwards.  text is the caller's device text (dev) or its host text; outputs(A) carves what the host forms return.
 template <class F>
 static void lz_lpf_device(tc_ctx *ctx, LzWork &W, const u8 *text, u64 n, bool dev, bool parse, F &&outputs) {
-    const u64 N = n + 1;
-    ctx->stats = tc_stats{};
-    ctx->stats.n = n; ctx->stats.N = N;
-    u64 primary = 0;
-    auto plan = [&](Arena &A, bool dry) {
-        W.d_text = dev ? const_cast<u8 *>(text) : A.get<u8>(n + 16);
-        u32 *p = A.get<u32>(N);     // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
-        W.d_sa = dry ? reinterpret_cast<u32 *>(sizeof(u32)) : p;
-        W.d_lcp = A.get<u32>(N);
-        outputs(A);
-        const size_t mark = A.off;
-        u8 *d_L = A.get<u8>(N + 16);
-        sa_build(ctx, A, W.d_text, n, W.d_sa, d_L, &primary, nullptr, dry);
-        A.rewind(mark);
-        W.lcp_ws.carve(ctx, A, n);
-        A.rewind(mark);
-        W.carve(ctx, A, n, parse);
-    };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.peak);
-    if (!dev) {     // the text is the first carve: upload it between the reserve and the run, as lcp_array_host_entry does
-        Arena A0(ctx->ws);
-        tc_h2d(ctx, A0.get<u8>(n + 16), text, n);
-    }
-    Arena A(ctx->ws);
-    plan(A, false);
-    lcp_device(ctx, W.lcp_ws, W.d_text, n, W.d_sa, W.d_lcp);
-    lz_build_tree(ctx, W, W.d_sa, W.sa_min);
-    lz_build_tree(ctx, W, W.d_lcp, W.lcp_min);
-    lz_lpf_kernel<<<tc_cdiv(n, 256), 256, 0, ctx->stream>>>(W.d_sa, W.d_lcp, W.sa_min, W.lcp_min, (u32)N, W.lf, W.pack);
+    esa_plan(ctx, W, text, n, dev, outputs, [&](Arena &A) { W.carve(ctx, A, n, parse); });
+    W.tree.build(ctx, W.d_sa, W.sa_min);
+    W.tree.build(ctx, W.d_lcp, W.lcp_min);
+    lz_lpf_kernel<<<tc_cdiv(n, 256), 256, 0, ctx->stream>>>(W.d_sa, W.d_lcp, W.sa_min, W.lcp_min, (u32)(n + 1), W.tree.lf, W.pack);
     TC_LAUNCH_CHECK(ctx);
 }
 
@@ -101,17 +55,15 @@ static void lz_tile_launch(tc_ctx *ctx, const LzWork &W, u64 n, u32 *d_ph_src, u
     TC_LAUNCH_CHECK(ctx);
 }
 
-// steps a to c of the parse and the scan of the tiles' counts: returns the number of phrases (the host waits for it)
-static u64 lz_phrase_starts(tc_ctx *ctx, const LzWork &W, u64 n) {
+// steps a to c of the parse and the scan of the tiles' counts: returns the number of phrases (tc_read_total: the host waits
+// for it, *nph is set, a capacity that is too small throws)
+static u64 lz_phrase_starts(tc_ctx *ctx, const LzWork &W, u64 n, u64 cap, bool sizes_only, u64 *nph) {
     lz_tile_launch<0>(ctx, W, n, nullptr, nullptr);
     tc_memset_async(ctx, W.entry, 0xff, (size_t)W.ntiles * sizeof(u32));
     lz_chain_kernel<<<1, 64, 0, ctx->stream>>>(W.exitp, (u32)n, W.ltile, W.entry);
     TC_LAUNCH_CHECK(ctx);
     lz_tile_launch<1>(ctx, W, n, nullptr, nullptr);
-    const u64 *d_total = tc_scan64(ctx, W.cnt, W.ntiles, W.tsum, W.offs);
-    tc_d2h(ctx, &ctx->h_scalars[9], d_total, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return ctx->h_scalars[9];
+    return tc_read_total(ctx, W.cnt, W.ntiles, W.tsum, W.offs, cap, sizes_only, nph, "phrase");
 }
 
 // tc_lpf_array, tc_lpf_array_dev
@@ -152,12 +104,7 @@ static void lz_parse_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 *ph_src, u32 
         d_ph_src = A.get<u32>(slots + 1);
         d_ph_len = A.get<u32>(slots + 1);
     });
-    const u64 need = lz_phrase_starts(ctx, W, n);
-    *nph = need;
-    if (need > cap && !sizes_only) {
-        tc_sync_check(ctx);
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu phrase slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    }
+    const u64 need = lz_phrase_starts(ctx, W, n, cap, sizes_only, nph);
     if (!sizes_only) {
         lz_tile_launch<2>(ctx, W, n, d_ph_src, d_ph_len);
         if (!dev) {

@@ -1,7 +1,7 @@
 // tc_maw_host.hpp -- host side of the minimal absent words (tc_maw.hpp has the kernels and the definitions): scratch, the
 // launch sequence, and the bodies of tc_absent_words / tc_absent_words_dev and tc_absent_word_profile /
-// tc_absent_word_profile_dev.  Included by textcomp.hip after tc_rep_host.hpp, whose ESA plan (sa_build, then lcp_device
-// over the sort's dead buffers), rep_left_kernel and lz_build_tree it follows and calls.
+// tc_absent_word_profile_dev.  Included by textcomp.hip after tc_esa_plan.hpp (the ESA is esa_plan's, with the last column
+// kept and the sort's byte counts) and tc_rep_host.hpp (rep_left_kernel).
 #pragma once
 #include "tc_maw.hpp"
 
@@ -12,14 +12,10 @@
 // per text byte, plus the min tree (4 / (f - 1)), the OR tree (carved at its wide size, 32 / (f - 1), before the alphabet is
 // known; the narrow instance uses a quarter of it) and 16 bytes per tile of FM_MS_NT rows; the sort's own need where that is
 // larger.  The list's 9 bytes per word lie ahead of the mark in the host form.
-struct MawWork {
-    u8 *d_text = nullptr, *d_L = nullptr;
-    u32 *d_sa = nullptr, *d_lcp = nullptr;
-    LcpScratch lcp_ws;
-    u32 lf = 0, tree_levels = 0, tree_words = 0;
-    u32 tree_off[FM_MS_MAXLEV + 1], tree_cnt[FM_MS_MAXLEV + 1];
+struct MawWork : Esa {
+    MinTree tree;
     u32 *lcp_min = nullptr;
-    u64 *ortree = nullptr;  // 4 tree_words: level k starts at word tree_off[k] * (wide ? 4 : 1)
+    u64 *ortree = nullptr;  // 4 tree.words: level k starts at word tree.off[k] * (wide ? 4 : 1)
     u64 *flag = nullptr;    // N entries: the flags, then (as u32) the word count of every row
     u64 *chg = nullptr;     // N entries
     u64 *csum = nullptr;    // the scan's tile sums
@@ -28,10 +24,9 @@ struct MawWork {
     u64 *hist = nullptr;    // the profile: kmax + 1 bins and the total
     void carve(const tc_ctx *ctx, Arena &A, u64 n, u32 kmax) {
         const u64 N = n + 1;
-        lf = fm_log2(ctx->fm_lcp_fanout ? ctx->fm_lcp_fanout : FM_LCP_FANOUT);
-        tree_levels = fm_ms_tree_shape((u32)N, lf, tree_off, tree_cnt, &tree_words);
-        lcp_min = A.get<u32>(tree_words);
-        ortree = A.get<u64>(4 * (size_t)tree_words);
+        tree.shape(ctx, (u32)N);
+        lcp_min = A.get<u32>(tree.words);
+        ortree = A.get<u64>(4 * (size_t)tree.words);
         flag = A.get<u64>(N);
         chg = A.get<u64>(N);
         csum = A.get<u64>(tc_cdiv(N, SCAN_TILE) + 2);
@@ -52,41 +47,19 @@ struct MawWork {
 template <class F>
 static bool maw_prepare(tc_ctx *ctx, MawWork &W, const u8 *text, u64 n, bool dev, u32 kmax, MawArgs &P, F &&outputs) {
     const u64 N = n + 1;
-    ctx->stats = tc_stats{};
-    ctx->stats.n = n; ctx->stats.N = N;
-    u64 primary = 0;
     u32 counts[256] = {};
-    auto plan = [&](Arena &A, bool dry) {
-        W.d_text = dev ? const_cast<u8 *>(text) : A.get<u8>(n + 16);
-        u32 *p = A.get<u32>(N);     // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
-        W.d_sa = dry ? reinterpret_cast<u32 *>(sizeof(u32)) : p;
-        W.d_lcp = A.get<u32>(N);
-        W.d_L = A.get<u8>(N + 16);  // ahead of the mark: the last column outlives the sort
-        outputs(A);
-        const size_t mark = A.off;
-        sa_build(ctx, A, W.d_text, n, W.d_sa, W.d_L, &primary, counts, dry);
-        A.rewind(mark);
-        W.lcp_ws.carve(ctx, A, n);
-        A.rewind(mark);
-        W.carve(ctx, A, n, kmax);
-    };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.peak);
-    if (!dev) {     // the text is the first carve: upload it between the reserve and the run, as lcp_array_host_entry does
-        Arena A0(ctx->ws);
-        tc_h2d(ctx, A0.get<u8>(n + 16), text, n);
-    }
-    Arena A(ctx->ws);
-    plan(A, false);
+    EsaOpts o;
+    o.keep_L = true;
+    o.counts = counts;
+    esa_plan(ctx, W, text, n, dev, outputs, [&](Arena &A) { W.carve(ctx, A, n, kmax); }, o);
     hipStream_t s = ctx->stream;
-    lcp_device(ctx, W.lcp_ws, W.d_text, n, W.d_sa, W.d_lcp);
-    lz_build_tree(ctx, W, W.d_lcp, W.lcp_min);
+    const u64 primary = W.primary;
+    W.tree.build(ctx, W.d_lcp, W.lcp_min);
     rep_left_kernel<<<tc_cdiv(N, 256), 256, 0, s>>>(W.d_L, (u32)N, (u32)primary, W.flag);
     TC_LAUNCH_CHECK(ctx);
     tc_scan64(ctx, W.flag, N, W.csum, W.chg);
     P.lcp = W.d_lcp; P.lmin = W.lcp_min; P.sa = W.d_sa; P.chg = W.chg; P.L = W.d_L; P.ortree = W.ortree;
-    P.N = (u32)N; P.lf = W.lf; P.primary = (u32)primary;
+    P.N = (u32)N; P.lf = W.tree.lf; P.primary = (u32)primary;
     u32 sigma = 0;
     for (u32 i = 0; i < 4; i++) P.alpha[i] = 0;
     for (u32 v = 0; v < 256; v++) {
@@ -97,11 +70,11 @@ static bool maw_prepare(tc_ctx *ctx, MawWork &W, const u8 *text, u64 n, bool dev
     const bool wide = sigma > 64;
     const u32 words = wide ? 4u : 1u;
     const u64 *src = nullptr;
-    for (u32 k = 1; k <= W.tree_levels; k++) {      // the OR tree, level over level: level 1 from the last column
-        u64 *dst = W.ortree + (size_t)W.tree_off[k] * words;
-        const u32 grid = tc_cdiv(W.tree_cnt[k], 256);
-        if (wide) maw_tree_kernel<true><<<grid, 256, 0, s>>>(P, src, W.tree_cnt[k - 1], dst, W.tree_cnt[k]);
-        else maw_tree_kernel<false><<<grid, 256, 0, s>>>(P, src, W.tree_cnt[k - 1], dst, W.tree_cnt[k]);
+    for (u32 k = 1; k <= W.tree.levels; k++) {      // the OR tree, level over level: level 1 from the last column
+        u64 *dst = W.ortree + (size_t)W.tree.off[k] * words;
+        const u32 grid = tc_cdiv(W.tree.cnt[k], 256);
+        if (wide) maw_tree_kernel<true><<<grid, 256, 0, s>>>(P, src, W.tree.cnt[k - 1], dst, W.tree.cnt[k]);
+        else maw_tree_kernel<false><<<grid, 256, 0, s>>>(P, src, W.tree.cnt[k - 1], dst, W.tree.cnt[k]);
         TC_LAUNCH_CHECK(ctx);
         src = dst;
     }
@@ -145,15 +118,7 @@ static void absent_words_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 min_len, 
         }
     });
     maw_rows<MAW_COUNT>(ctx, W, P, wide, 0, nullptr, nullptr, nullptr, 0);
-    const u64 *d_total = tc_scan64(ctx, W.cnt, W.ntiles, W.tsum, W.offs);
-    tc_d2h(ctx, &ctx->h_scalars[9], d_total, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const u64 need = ctx->h_scalars[9];
-    *nmaw = need;
-    if (need > cap && !sizes_only) {
-        tc_sync_check(ctx);
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu word slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    }
+    const u64 need = tc_read_total(ctx, W.cnt, W.ntiles, W.tsum, W.offs, cap, sizes_only, nmaw, "word");
     if (!sizes_only && need) {
         maw_rows<MAW_FILL>(ctx, W, P, wide, need, d_left, d_pos, d_len, 0);
         if (!dev) {

@@ -1,8 +1,7 @@
 // tc_pal_host.hpp -- host side of the palindromes / inverted repeats of a text (tc_pal.hpp has the kernels and the
 // method): scratch, the launch sequence, and the bodies of tc_palindromes / tc_longest_palindrome and their _dev forms.
-// Included by textcomp.hip after tc_tr_host.hpp, whose ESA plan (sa_build, lcp_device over the sort's dead buffers, the
-// inverse array by tr_isa_kernel) it follows once, over the 2n bytes of the joint text, and tc_lz_host.hpp's
-// lz_build_tree.
+// Included by textcomp.hip after tc_esa_plan.hpp, whose lower layer (esa_sort: the sort, then the LCP scratch over its dead
+// buffers) it runs over the 2n bytes of the joint text, which a kernel makes first, and tc_tr_host.hpp (tr_isa_kernel).
 #pragma once
 #include "tc_pal.hpp"
 
@@ -15,8 +14,7 @@
 struct PalWork {
     u8 *d_text = nullptr, *d_sigma = nullptr, *d_S = nullptr;
     u32 *d_sa = nullptr, *isa = nullptr, *lcp = nullptr;
-    u32 lf = 0, tree_levels = 0, tree_words = 0;
-    u32 tree_off[FM_MS_MAXLEV + 1], tree_cnt[FM_MS_MAXLEV + 1];
+    MinTree tree;
     u32 *lcp_min = nullptr;
     LcpScratch lcp_ws;
     u64 *word = nullptr;        // 2n - 1 entries: len << 32 | mm, 0 for none
@@ -28,13 +26,11 @@ struct PalWork {
         const u64 N = 2 * n + 1;
         d_sigma = A.get<u8>(256);
         d_S = A.get<u8>(2 * n + 16);
-        u32 *p = A.get<u32>(N);     // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
-        d_sa = dry ? reinterpret_cast<u32 *>(sizeof(u32)) : p;
+        d_sa = esa_sa_arg(A.get<u32>(N), dry);
         isa = A.get<u32>(N);
         lcp = A.get<u32>(N);
-        lf = fm_log2(ctx->fm_lcp_fanout ? ctx->fm_lcp_fanout : FM_LCP_FANOUT);
-        tree_levels = fm_ms_tree_shape((u32)N, lf, tree_off, tree_cnt, &tree_words);
-        lcp_min = A.get<u32>(tree_words);
+        tree.shape(ctx, (u32)N);
+        lcp_min = A.get<u32>(tree.words);
     }
     // what follows the ESA, over its dead buffers
     void carve_words(Arena &A, u64 n) {
@@ -79,38 +75,27 @@ static void pal_words_device(tc_ctx *ctx, PalWork &W, const u8 *text, u64 n, con
     };
     {   // the three overlays behind the mark: the sort, the LCP array, the words
         Arena dry(nullptr);
-        u64 primary = 0;
         kept(dry, true);
-        dry.get<u8>(N + 16);
-        sa_build(ctx, dry, W.d_S, n2, W.d_sa, nullptr, &primary, nullptr, true);
-        dry.rewind(mark);
-        W.lcp_ws.carve(ctx, dry, n2);
+        esa_sort(ctx, dry, W.d_S, n2, W.d_sa, W.lcp_ws, true);
         dry.rewind(mark);
         W.carve_words(dry, n);
         tc_ws_reserve(ctx, dry.peak);
     }
-    if (!dev) {     // the text is the first carve: upload it between the reserve and the run, as lcp_array_host_entry does
-        Arena A0(ctx->ws);
-        tc_h2d(ctx, A0.get<u8>(n + 16), text, n);
-    }
+    if (!dev) esa_fill_text(ctx, text, n, nullptr, 0, false);
     Arena A(ctx->ws);
     kept(A, false);
     hipStream_t s = ctx->stream;
     tc_h2d(ctx, W.d_sigma, sigma, 256);
     pal_joint_kernel<<<tc_cdiv(n, PAL_NT), PAL_NT, 0, s>>>(W.d_text, (u32)n, W.d_sigma, W.d_S);
     TC_LAUNCH_CHECK(ctx);
-    u64 primary = 0;
-    u8 *d_L = A.get<u8>(N + 16);
-    sa_build(ctx, A, W.d_S, n2, W.d_sa, d_L, &primary, nullptr, false);
-    A.rewind(mark);
-    W.lcp_ws.carve(ctx, A, n2);
+    esa_sort(ctx, A, W.d_S, n2, W.d_sa, W.lcp_ws, false);
     lcp_device(ctx, W.lcp_ws, W.d_S, n2, W.d_sa, W.lcp);
     tr_isa_kernel<<<tc_cdiv(N, TR_NT), TR_NT, 0, s>>>(W.d_sa, (u32)N, W.isa, ctx->d_err);
     TC_LAUNCH_CHECK(ctx);
     A.rewind(mark);
     W.carve_words(A, n);
-    lz_build_tree(ctx, W, W.lcp, W.lcp_min);
-    pal_centre_kernel<<<tc_cdiv(n2 - 1, FM_MS_NT), FM_MS_NT, 0, s>>>(W.d_S, (u32)n, W.isa, W.lcp, W.lcp_min, W.lf, max_mismatch, min_len,
+    W.tree.build(ctx, W.lcp, W.lcp_min);
+    pal_centre_kernel<<<tc_cdiv(n2 - 1, FM_MS_NT), FM_MS_NT, 0, s>>>(W.d_S, (u32)n, W.isa, W.lcp, W.lcp_min, W.tree.lf, max_mismatch, min_len,
                                                                     W.word);
     TC_LAUNCH_CHECK(ctx);
 }
@@ -140,15 +125,7 @@ static void palindromes_entry(tc_ctx *ctx, const u8 *text, u64 n, const u8 *comp
     hipStream_t s = ctx->stream;
     pal_count_kernel<<<W.ntiles, PAL_NT, 0, s>>>(W.word, centres, W.cnt);
     TC_LAUNCH_CHECK(ctx);
-    const u64 *d_total = tc_scan64(ctx, W.cnt, W.ntiles, W.tsum, W.offs);
-    tc_d2h(ctx, &ctx->h_scalars[9], d_total, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 need = ctx->h_scalars[9];
-    *npal = need;
-    if (need > cap && !sizes_only) {
-        tc_sync_check(ctx);
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu palindrome slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    }
+    const u64 need = tc_read_total(ctx, W.cnt, W.ntiles, W.tsum, W.offs, cap, sizes_only, npal, "palindrome");
     if (!sizes_only && need) {
         pal_fill_kernel<<<W.ntiles, PAL_NT, 0, s>>>(W.word, centres, W.offs, need, d_start, d_len, d_mm);
         TC_LAUNCH_CHECK(ctx);

@@ -408,6 +408,22 @@ static const u64 *tc_scan64(tc_ctx *ctx, const u64 *in, u64 n, u64 *tsum, u64 *o
     TC_LAUNCH_CHECK(ctx);
     return tsum + tiles;
 }
+// Count, scan, read the total, check the capacity -- what stands between a list's count pass and its fill pass: offs[0 .. n) =
+// the exclusive scan of counts[0 .. n), and the host waits for the total.  *count is set to it; above cap, unless sizes_only,
+// that is TC_ERR_CAPACITY ("need <total> <noun> slots, have <cap>").  Returns the total.
+static u64 tc_read_total(tc_ctx *ctx, const u64 *counts, u64 n, u64 *tsum, u64 *offs, u64 cap, bool sizes_only, u64 *count,
+                         const char *noun) {
+    const u64 *d_total = tc_scan64(ctx, counts, n, tsum, offs);
+    TC_HIP(ctx, hipMemcpyAsync(&ctx->h_scalars[9], d_total, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    TC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const u64 need = ctx->h_scalars[9];
+    *count = need;
+    if (need > cap && !sizes_only) {
+        tc_sync_check(ctx);
+        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu %s slots, have %llu", (unsigned long long)need, noun, (unsigned long long)cap);
+    }
+    return need;
+}
 
 // one lane per run fills its slice; runs >= 32 are filled by the whole wave; runs >= RLE_HUGE are
 // queued and filled by the whole grid afterwards (a block of "AAAA..." is a handful of runs)

@@ -1,7 +1,6 @@
 // tc_sus_host.hpp -- host side of the unique substrings (tc_sus.hpp has the kernels and the method): scratch, the launch
 // sequence, and the bodies of tc_unique_prefixes, tc_unique_substrings, tc_shortest_unique and their _dev forms.  Included by
-// textcomp.hip after tc_maw_host.hpp; it follows the ESA plan of maw_prepare (sa_build, then lcp_device over the sort's dead
-// buffers) without the last column, and calls lz_build_tree.
+// textcomp.hip after tc_esa_plan.hpp: the ESA is esa_plan's, with nothing kept but sa and lcp.
 #pragma once
 #include "tc_sus.hpp"
 
@@ -14,15 +13,11 @@
 //             byte, 32 with the host form's two arrays
 // -- the sort's own need behind the first 8 where that is larger.
 enum { SUS_PREFIX = 0, SUS_LIST = 1, SUS_POINT = 2 };
-struct SusWork {
-    u8 *d_text = nullptr;
-    u32 *d_sa = nullptr, *d_lcp = nullptr;
-    LcpScratch lcp_ws;
+struct SusWork : Esa {
     u32 *up = nullptr;
     u32 ntiles = 0;
     u64 *cnt = nullptr, *offs = nullptr, *tsum = nullptr;       // the list
-    u32 lf = 0, tree_levels = 0, tree_words = 0;                // the point call: the tree is over the n entries of mlen
-    u32 tree_off[FM_MS_MAXLEV + 1], tree_cnt[FM_MS_MAXLEV + 1];
+    MinTree tree;                                               // the point call: the tree is over the n entries of mlen
     u32 *mlen = nullptr, *mlen_min = nullptr, *pred = nullptr, *nxt = nullptr, *tmax = nullptr, *tmin = nullptr;
     void carve(const tc_ctx *ctx, Arena &A, u64 n, int what, u32 *up_dev) {
         up = up_dev ? up_dev : A.get<u32>(n + 1);
@@ -32,10 +27,9 @@ struct SusWork {
             offs = A.get<u64>(ntiles + 1);
             tsum = A.get<u64>(tc_cdiv(ntiles, SCAN_TILE) + 2);
         } else if (what == SUS_POINT) {
-            lf = fm_log2(ctx->fm_lcp_fanout ? ctx->fm_lcp_fanout : FM_LCP_FANOUT);
-            tree_levels = fm_ms_tree_shape((u32)n, lf, tree_off, tree_cnt, &tree_words);
+            tree.shape(ctx, (u32)n);
             mlen = A.get<u32>(n + 4);       // (level 0 of the tree is read 16 bytes at a time)
-            mlen_min = A.get<u32>(tree_words);
+            mlen_min = A.get<u32>(tree.words);
             pred = A.get<u32>(n);
             nxt = A.get<u32>(n + 1);
             tmax = A.get<u32>(ntiles);
@@ -49,33 +43,7 @@ struct SusWork {
 template <class F>
 static void sus_prepare(tc_ctx *ctx, SusWork &W, const u8 *text, u64 n, bool dev, int what, u32 *up_dev, F &&outputs) {
     const u64 N = n + 1;
-    ctx->stats = tc_stats{};
-    ctx->stats.n = n; ctx->stats.N = N;
-    u64 primary = 0;
-    auto plan = [&](Arena &A, bool dry) {
-        W.d_text = dev ? const_cast<u8 *>(text) : A.get<u8>(n + 16);
-        u32 *p = A.get<u32>(N);     // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
-        W.d_sa = dry ? reinterpret_cast<u32 *>(sizeof(u32)) : p;
-        W.d_lcp = A.get<u32>(N);
-        outputs(A);
-        const size_t mark = A.off;
-        u8 *d_L = A.get<u8>(N + 16);    // behind the mark: the last column dies with the sort
-        sa_build(ctx, A, W.d_text, n, W.d_sa, d_L, &primary, nullptr, dry);
-        A.rewind(mark);
-        W.lcp_ws.carve(ctx, A, n);
-        A.rewind(mark);
-        W.carve(ctx, A, n, what, up_dev);
-    };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.peak);
-    if (!dev) {     // the text is the first carve: upload it between the reserve and the run, as lcp_array_host_entry does
-        Arena A0(ctx->ws);
-        tc_h2d(ctx, A0.get<u8>(n + 16), text, n);
-    }
-    Arena A(ctx->ws);
-    plan(A, false);
-    lcp_device(ctx, W.lcp_ws, W.d_text, n, W.d_sa, W.d_lcp);
+    esa_plan(ctx, W, text, n, dev, outputs, [&](Arena &A) { W.carve(ctx, A, n, what, up_dev); });
     sus_prefix_kernel<<<tc_cdiv(N, FM_MS_NT), FM_MS_NT, 0, ctx->stream>>>(W.d_sa, W.d_lcp, (u32)N, W.up);
     TC_LAUNCH_CHECK(ctx);
 }
@@ -115,15 +83,7 @@ static void unique_substrings_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 min_
     hipStream_t s = ctx->stream;
     sus_mark_kernel<SUS_COUNT><<<W.ntiles, SUS_NT, 0, s>>>(W.up, (u32)n, min_len, max_len, nullptr, nullptr, W.cnt, nullptr, 0, nullptr, nullptr);
     TC_LAUNCH_CHECK(ctx);
-    const u64 *d_total = tc_scan64(ctx, W.cnt, W.ntiles, W.tsum, W.offs);
-    tc_d2h(ctx, &ctx->h_scalars[9], d_total, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 need = ctx->h_scalars[9];
-    *nmus = need;
-    if (need > cap && !sizes_only) {
-        tc_sync_check(ctx);
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu MUS slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    }
+    const u64 need = tc_read_total(ctx, W.cnt, W.ntiles, W.tsum, W.offs, cap, sizes_only, nmus, "MUS");
     if (!sizes_only && need) {
         sus_mark_kernel<SUS_FILL><<<W.ntiles, SUS_NT, 0, s>>>(W.up, (u32)n, min_len, max_len, nullptr, nullptr, nullptr, W.offs, need, d_start, d_len);
         TC_LAUNCH_CHECK(ctx);
@@ -158,8 +118,8 @@ static void shortest_unique_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 *sus_s
     TC_LAUNCH_CHECK(ctx);
     sus_scan_kernel<<<W.ntiles, SUS_NT, 0, s>>>(W.pred, W.mlen, (u32)n, W.tmax, W.tmin, W.nxt);
     TC_LAUNCH_CHECK(ctx);
-    lz_build_tree(ctx, W, W.mlen, W.mlen_min);
-    sus_point_kernel<<<tc_cdiv(n, FM_MS_NT), FM_MS_NT, 0, s>>>(W.mlen, W.mlen_min, W.pred, W.nxt, (u32)n, W.lf, d_start, d_len);
+    W.tree.build(ctx, W.mlen, W.mlen_min);
+    sus_point_kernel<<<tc_cdiv(n, FM_MS_NT), FM_MS_NT, 0, s>>>(W.mlen, W.mlen_min, W.pred, W.nxt, (u32)n, W.tree.lf, d_start, d_len);
     TC_LAUNCH_CHECK(ctx);
     if (!dev) {
         if (sus_start) tc_d2h(ctx, sus_start, d_start, n * sizeof(u32));

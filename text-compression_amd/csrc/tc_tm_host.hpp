@@ -1,7 +1,7 @@
 // tc_tm_host.hpp -- host side of the comparison of two texts (tc_tm.hpp has the kernels and the method): scratch, the
 // launch sequence, and the bodies of tc_text_match_stats / tc_text_mems / tc_text_lcs, their _dev forms and
-// tc_mems_from_stats_dev.  Included by textcomp.hip after tc_lz_host.hpp, whose ESA plan (sa_build, then lcp_device over
-// the sort's dead buffers) and lz_build_tree it follows, and tc_lcp_host.hpp, whose summary kernel is the LCS reduction.
+// tc_mems_from_stats_dev.  Included by textcomp.hip after tc_esa_plan.hpp (the ESA is esa_plan's, over the two texts copied
+// into one) and tc_lcp_host.hpp, whose summary kernel is the LCS reduction.
 #pragma once
 #include "tc_tm.hpp"
 
@@ -23,13 +23,9 @@ struct TmMemWork {
 // sort that is 1 (text) + 4 (sa) + 4 (lcp) + 8 (flags / trow, qrow) + 8 (cnt) = 25 bytes per byte of the two texts, plus
 // the tree (4 / (f - 1)), up to 12 per query byte for the three results and 16 bytes per tile of the MEM filter; the
 // sort's own need where that is larger.
-struct TmWork {
-    u8 *d_text = nullptr;
-    u32 *d_sa = nullptr, *d_lcp = nullptr;
+struct TmWork : Esa {
     u32 *d_len = nullptr, *d_pos = nullptr, *d_occ = nullptr;   // a entries each; pos and occ may stay null
-    LcpScratch lcp_ws;
-    u32 lf = 0, tree_levels = 0, tree_words = 0;
-    u32 tree_off[FM_MS_MAXLEV + 1], tree_cnt[FM_MS_MAXLEV + 1];
+    MinTree tree;
     u32 *lcp_min = nullptr;
     u64 *flag = nullptr;    // N + 1 entries; then trow (b words) and qrow (a words)
     u64 *cnt = nullptr;     // N + 1 entries
@@ -38,9 +34,8 @@ struct TmWork {
     TmMemWork mem;
     void carve(const tc_ctx *ctx, Arena &A, u64 a, u64 b) {
         const u64 N = a + b + 1;
-        lf = fm_log2(ctx->fm_lcp_fanout ? ctx->fm_lcp_fanout : FM_LCP_FANOUT);
-        tree_levels = fm_ms_tree_shape((u32)N, lf, tree_off, tree_cnt, &tree_words);
-        lcp_min = A.get<u32>(tree_words);
+        tree.shape(ctx, (u32)N);
+        lcp_min = A.get<u32>(tree.words);
         flag = A.get<u64>(N + 1);
         cnt = A.get<u64>(N + 1);
         csum = A.get<u64>(tc_cdiv(N + 1, SCAN_TILE) + 2);
@@ -58,38 +53,12 @@ struct TmWork {
 template <class F>
 static void tm_stats_device(tc_ctx *ctx, TmWork &W, const u8 *query, u64 a, const u8 *target, u64 b, bool dev, F &&outputs) {
     const u64 n = a + b, N = n + 1;
-    ctx->stats = tc_stats{};
-    ctx->stats.n = n; ctx->stats.N = N;
-    u64 primary = 0;
-    auto plan = [&](Arena &A, bool dry) {
-        W.d_text = A.get<u8>(n + 16);
-        u32 *p = A.get<u32>(N);     // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
-        W.d_sa = dry ? reinterpret_cast<u32 *>(sizeof(u32)) : p;
-        W.d_lcp = A.get<u32>(N);
-        outputs(A);
-        const size_t mark = A.off;
-        u8 *d_L = A.get<u8>(N + 16);
-        sa_build(ctx, A, W.d_text, n, W.d_sa, d_L, &primary, nullptr, dry);
-        A.rewind(mark);
-        W.lcp_ws.carve(ctx, A, n);
-        A.rewind(mark);
-        W.carve(ctx, A, a, b);
-    };
-    Arena dry(nullptr);
-    plan(dry, true);
-    tc_ws_reserve(ctx, dry.peak);
+    EsaOpts o;
+    o.text2 = target;
+    o.n2 = b;
+    esa_plan(ctx, W, query, a, dev, outputs, [&](Arena &A) { W.carve(ctx, A, a, b); }, o);
     hipStream_t s = ctx->stream;
-    {   // the text is the first carve: fill it between the reserve and the run, as lcp_array_host_entry does
-        Arena A0(ctx->ws);
-        u8 *x = A0.get<u8>(n + 16);
-        const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-        TC_HIP(ctx, hipMemcpyAsync(x, query, a, kind, s));
-        TC_HIP(ctx, hipMemcpyAsync(x + a, target, b, kind, s));
-    }
-    Arena A(ctx->ws);
-    plan(A, false);
-    lcp_device(ctx, W.lcp_ws, W.d_text, n, W.d_sa, W.d_lcp);
-    lz_build_tree(ctx, W, W.d_lcp, W.lcp_min);
+    W.tree.build(ctx, W.d_lcp, W.lcp_min);
     tm_flag_kernel<<<tc_cdiv(N + 1, 256), 256, 0, s>>>(W.d_sa, (u32)N, (u32)a, (u32)n, W.flag);
     TC_LAUNCH_CHECK(ctx);
     tc_scan64(ctx, W.flag, N + 1, W.csum, W.cnt);
@@ -97,10 +66,10 @@ static void tm_stats_device(tc_ctx *ctx, TmWork &W, const u8 *query, u64 a, cons
     TC_LAUNCH_CHECK(ctx);
     const u32 grid = tc_cdiv(a, FM_MS_NT);
     if (W.d_pos || W.d_occ)
-        tm_row_kernel<true><<<grid, FM_MS_NT, 0, s>>>(W.d_sa, W.d_lcp, W.lcp_min, (u32)N, W.lf, W.cnt, W.trow(), W.qrow(b), (u32)a, (u32)b,
+        tm_row_kernel<true><<<grid, FM_MS_NT, 0, s>>>(W.d_sa, W.d_lcp, W.lcp_min, (u32)N, W.tree.lf, W.cnt, W.trow(), W.qrow(b), (u32)a, (u32)b,
                                                      TM_ALL, W.d_len, W.d_pos, W.d_occ);
     else
-        tm_row_kernel<false><<<grid, FM_MS_NT, 0, s>>>(W.d_sa, W.d_lcp, W.lcp_min, (u32)N, W.lf, W.cnt, W.trow(), W.qrow(b), (u32)a, (u32)b,
+        tm_row_kernel<false><<<grid, FM_MS_NT, 0, s>>>(W.d_sa, W.d_lcp, W.lcp_min, (u32)N, W.tree.lf, W.cnt, W.trow(), W.qrow(b), (u32)a, (u32)b,
                                                       TM_ALL, W.d_len, nullptr, nullptr);
     TC_LAUNCH_CHECK(ctx);
 }
@@ -141,17 +110,14 @@ static void text_match_stats_entry(tc_ctx *ctx, const u8 *query, u64 a, const u8
 }
 
 // The MEM filter over d_len / d_pos (a >= 1 entries, in HBM) on the context's stream: the count (the host waits for it),
-// and -- unless sizes_only, or the count is above cap -- the fill.  Returns the count.
+// and -- unless sizes_only -- the fill.  Returns the count; a capacity that is too small throws after *nmem is set.
 static u64 tm_mems_filter(tc_ctx *ctx, const TmMemWork &M, const u32 *d_len, const u32 *d_pos, u64 a, u32 min_len, u32 *d_start,
-                          u32 *d_mpos, u32 *d_mlen, u64 cap, bool sizes_only) {
+                          u32 *d_mpos, u32 *d_mlen, u64 cap, bool sizes_only, u64 *nmem) {
     hipStream_t s = ctx->stream;
     tm_mem_count_kernel<<<M.ntiles, TM_NT, 0, s>>>(d_len, a, min_len, M.cnt);
     TC_LAUNCH_CHECK(ctx);
-    const u64 *d_total = tc_scan64(ctx, M.cnt, M.ntiles, M.tsum, M.offs);
-    tc_d2h(ctx, &ctx->h_scalars[9], d_total, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 need = ctx->h_scalars[9];
-    if (sizes_only || need > cap || need == 0) return need;
+    const u64 need = tc_read_total(ctx, M.cnt, M.ntiles, M.tsum, M.offs, cap, sizes_only, nmem, "MEM");
+    if (sizes_only || need == 0) return need;
     tm_mem_fill_kernel<<<M.ntiles, TM_NT, 0, s>>>(d_len, d_pos, a, min_len, M.offs, need, d_start, d_mpos, d_mlen);
     TC_LAUNCH_CHECK(ctx);
     return need;
@@ -180,10 +146,8 @@ static void mems_from_stats_entry(tc_ctx *ctx, const u32 *d_ms_len, const u32 *d
     *nmem = 0;
     TmMemWork M;
     tc_ws_plan(ctx, 0, [&](Arena &A, bool) { M.carve(A, a); });
-    const u64 need = tm_mems_filter(ctx, M, d_ms_len, d_ms_pos, a, min_len, d_mem_start, d_mem_pos, d_mem_len, cap, sizes_only);
-    *nmem = need;
+    tm_mems_filter(ctx, M, d_ms_len, d_ms_pos, a, min_len, d_mem_start, d_mem_pos, d_mem_len, cap, sizes_only, nmem);
     tc_sync_check(ctx);
-    if (need > cap && !sizes_only) TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu MEM slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
 }
 
 // tc_text_mems, tc_text_mems_dev.  mem_start = mem_pos = mem_len = null with capacity 0 is the sizes-only form.
@@ -206,12 +170,7 @@ static void text_mems_entry(tc_ctx *ctx, const u8 *query, u64 a, const u8 *targe
         d_mpos = A.get<u32>(slots + 1);
         d_mlen = A.get<u32>(slots + 1);
     });
-    const u64 need = tm_mems_filter(ctx, W.mem, W.d_len, W.d_pos, a, min_len, d_start, d_mpos, d_mlen, cap, sizes_only);
-    *nmem = need;
-    if (need > cap && !sizes_only) {
-        tc_sync_check(ctx);
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu MEM slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    }
+    const u64 need = tm_mems_filter(ctx, W.mem, W.d_len, W.d_pos, a, min_len, d_start, d_mpos, d_mlen, cap, sizes_only, nmem);
     if (!dev && !sizes_only && need) {
         tc_d2h(ctx, mem_start, d_start, need * sizeof(u32));
         tc_d2h(ctx, mem_pos, d_mpos, need * sizeof(u32));
@@ -245,7 +204,7 @@ static void text_lcs_entry(tc_ctx *ctx, const u8 *query, u64 a, const u8 *target
     *sum = ctx->h_scalars[9];
     if (best == 0 || at >= a) return;
     u32 *one = reinterpret_cast<u32 *>(W.red);
-    tm_row_kernel<true><<<tc_cdiv(a, FM_MS_NT), FM_MS_NT, 0, s>>>(W.d_sa, W.d_lcp, W.lcp_min, (u32)(a + b + 1), W.lf, W.cnt, W.trow(), W.qrow(b),
+    tm_row_kernel<true><<<tc_cdiv(a, FM_MS_NT), FM_MS_NT, 0, s>>>(W.d_sa, W.d_lcp, W.lcp_min, (u32)(a + b + 1), W.tree.lf, W.cnt, W.trow(), W.qrow(b),
                                                                 (u32)a, (u32)b, (u32)at, one, one + 1, nullptr);
     TC_LAUNCH_CHECK(ctx);
     tc_d2h(ctx, &ctx->h_scalars[10], one + 1, sizeof(u32));

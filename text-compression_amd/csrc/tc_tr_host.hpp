@@ -1,7 +1,7 @@
 // tc_tr_host.hpp -- host side of the runs / tandem repeats of a text (tc_tr.hpp has the kernels and the method): scratch,
 // the launch sequence, and the body of tc_tandem_repeats / tc_tandem_repeats_dev.  Included by textcomp.hip after
-// tc_lz_host.hpp, whose ESA plan (sa_build, then lcp_device over the sort's dead buffers) and lz_build_tree it follows --
-// twice: once for the text, once for its reverse.
+// tc_esa_plan.hpp, whose lower layer (esa_sort: the sort, then the LCP scratch over its dead buffers) it runs twice behind
+// one mark: once for the text, once for its reverse.
 #pragma once
 #include "tc_tr.hpp"
 
@@ -17,8 +17,7 @@ struct TrWork {
     u8 *d_text = nullptr, *d_rtext = nullptr;
     u32 *d_sa = nullptr;
     u32 *isa = nullptr, *comp = nullptr, *lcp = nullptr, *isa_r = nullptr, *lcp_r = nullptr;
-    u32 lf = 0, tree_levels = 0, tree_words = 0;
-    u32 tree_off[FM_MS_MAXLEV + 1], tree_cnt[FM_MS_MAXLEV + 1];
+    MinTree tree;
     u32 *isa_min = nullptr, *comp_min = nullptr, *lcp_min = nullptr, *lcp_r_min = nullptr;
     LcpScratch lcp_ws;
     u32 *c_start = nullptr;     // 2 n entries
@@ -28,19 +27,17 @@ struct TrWork {
     void carve_kept(const tc_ctx *ctx, Arena &A, u64 n, bool dry) {
         const u64 N = n + 1;
         d_rtext = A.get<u8>(n + 16);
-        u32 *p = A.get<u32>(N);     // (a dry run carves without a base: any non-null value tells sa_build that the array is provided)
-        d_sa = dry ? reinterpret_cast<u32 *>(sizeof(u32)) : p;
+        d_sa = esa_sa_arg(A.get<u32>(N), dry);
         isa = A.get<u32>(N);
         comp = A.get<u32>(N);
         lcp = A.get<u32>(N);
         isa_r = A.get<u32>(N);
         lcp_r = A.get<u32>(N);
-        lf = fm_log2(ctx->fm_lcp_fanout ? ctx->fm_lcp_fanout : FM_LCP_FANOUT);
-        tree_levels = fm_ms_tree_shape((u32)N, lf, tree_off, tree_cnt, &tree_words);
-        isa_min = A.get<u32>(tree_words);
-        comp_min = A.get<u32>(tree_words);
-        lcp_min = A.get<u32>(tree_words);
-        lcp_r_min = A.get<u32>(tree_words);
+        tree.shape(ctx, (u32)N);
+        isa_min = A.get<u32>(tree.words);
+        comp_min = A.get<u32>(tree.words);
+        lcp_min = A.get<u32>(tree.words);
+        lcp_r_min = A.get<u32>(tree.words);
     }
     // what follows the two ESAs, over their dead buffers
     void carve_cand(Arena &A, u64 n) {
@@ -55,12 +52,8 @@ struct TrWork {
 // sort + LCP array of one text of n bytes behind `mark`, then isa (and comp) by scatter: W.d_sa is dead afterwards
 static void tr_esa(tc_ctx *ctx, TrWork &W, Arena &A, size_t mark, const u8 *d_text, u64 n, u32 *d_lcp, u32 *d_isa, u32 *d_comp) {
     const u64 N = n + 1;
-    u64 primary = 0;
     A.rewind(mark);
-    u8 *d_L = A.get<u8>(N + 16);
-    sa_build(ctx, A, d_text, n, W.d_sa, d_L, &primary, nullptr, false);
-    A.rewind(mark);
-    W.lcp_ws.carve(ctx, A, n);
+    esa_sort(ctx, A, d_text, n, W.d_sa, W.lcp_ws, false);
     lcp_device(ctx, W.lcp_ws, d_text, n, W.d_sa, d_lcp);
     tr_isa_kernel<<<tc_cdiv(N, TR_NT), TR_NT, 0, ctx->stream>>>(W.d_sa, (u32)N, d_isa, ctx->d_err);
     TC_LAUNCH_CHECK(ctx);
@@ -102,20 +95,13 @@ static void tandem_repeats_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 min_per
     };
     {   // the three overlays behind the mark: a sort, an LCP array, the candidates
         Arena dry(nullptr);
-        u64 primary = 0;
         kept(dry, true);
-        dry.get<u8>(N + 16);
-        sa_build(ctx, dry, W.d_text, n, W.d_sa, nullptr, &primary, nullptr, true);
-        dry.rewind(mark);
-        W.lcp_ws.carve(ctx, dry, n);
+        esa_sort(ctx, dry, W.d_text, n, W.d_sa, W.lcp_ws, true);
         dry.rewind(mark);
         W.carve_cand(dry, n);
         tc_ws_reserve(ctx, dry.peak);
     }
-    if (!dev) {     // the text is the first carve: upload it between the reserve and the run, as lcp_array_host_entry does
-        Arena A0(ctx->ws);
-        tc_h2d(ctx, A0.get<u8>(n + 16), text, n);
-    }
+    if (!dev) esa_fill_text(ctx, text, n, nullptr, 0, false);
     Arena A(ctx->ws);
     kept(A, false);
     hipStream_t s = ctx->stream;
@@ -125,27 +111,19 @@ static void tandem_repeats_entry(tc_ctx *ctx, const u8 *text, u64 n, u32 min_per
     tr_esa(ctx, W, A, mark, W.d_rtext, n, W.lcp_r, W.isa_r, nullptr);
     A.rewind(mark);
     W.carve_cand(A, n);
-    lz_build_tree(ctx, W, W.isa, W.isa_min);
-    lz_build_tree(ctx, W, W.comp, W.comp_min);
-    lz_build_tree(ctx, W, W.lcp, W.lcp_min);
-    lz_build_tree(ctx, W, W.lcp_r, W.lcp_r_min);
+    W.tree.build(ctx, W.isa, W.isa_min);
+    W.tree.build(ctx, W.comp, W.comp_min);
+    W.tree.build(ctx, W.lcp, W.lcp_min);
+    W.tree.build(ctx, W.lcp_r, W.lcp_r_min);
     const TrFilter f{min_period, max_period, min_copies, min_len};
     tr_cand_kernel<<<tc_cdiv(n, FM_MS_NT), FM_MS_NT, 0, s>>>(W.d_text, (u32)n, W.isa, W.isa_min, W.comp, W.comp_min, W.lcp, W.lcp_min,
-                                                            W.isa_r, W.lcp_r, W.lcp_r_min, W.lf, f, W.c_start, W.c_pl);
+                                                            W.isa_r, W.lcp_r, W.lcp_r_min, W.tree.lf, f, W.c_start, W.c_pl);
     TC_LAUNCH_CHECK(ctx);
     const u32 cgrid = tc_cdiv(2 * n, TR_NT);
     tc_memset_async(ctx, W.cnt, 0, n * sizeof(u64));
     tr_count_kernel<<<cgrid, TR_NT, 0, s>>>(W.c_start, W.c_pl, 2 * n, (u32)n, W.cnt);
     TC_LAUNCH_CHECK(ctx);
-    const u64 *d_total = tc_scan64(ctx, W.cnt, n, W.tsum, W.offs);
-    tc_d2h(ctx, &ctx->h_scalars[9], d_total, sizeof(u64));
-    TC_HIP(ctx, hipStreamSynchronize(s));
-    const u64 need = ctx->h_scalars[9];
-    *nrun = need;
-    if (need > cap && !sizes_only) {
-        tc_sync_check(ctx);
-        TC_FAIL(ctx, TC_ERR_CAPACITY, "need %llu run slots, have %llu", (unsigned long long)need, (unsigned long long)cap);
-    }
+    const u64 need = tc_read_total(ctx, W.cnt, n, W.tsum, W.offs, cap, sizes_only, nrun, "run");
     if (!sizes_only && need) {
         tr_fill_kernel<<<cgrid, TR_NT, 0, s>>>(W.c_start, W.c_pl, 2 * n, (u32)n, W.cnt, W.offs, need, d_start, d_len, d_period);
         TC_LAUNCH_CHECK(ctx);

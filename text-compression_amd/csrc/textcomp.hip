@@ -7,6 +7,7 @@
 #include "tc_ws_host.hpp"
 #include "tc_fm_host.hpp"
 #include "tc_lcp_host.hpp"
+#include "tc_esa_plan.hpp"
 #include "tc_lz_host.hpp"
 #include "tc_rep_host.hpp"
 #include "tc_kmer_host.hpp"
