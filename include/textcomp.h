@@ -518,6 +518,63 @@ int tc_esa_compare(tc_ctx *ctx, const tc_esa *esa, const uint32_t *a_start, cons
                    const uint32_t *b_len, uint64_t nq, int8_t *order, uint32_t *common);
 int tc_esa_compare_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_a_start, const uint32_t *d_a_len,
                        const uint32_t *d_b_start, const uint32_t *d_b_len, uint64_t nq, int8_t *d_order, uint32_t *d_common);
+/* ---- document collections on the kept ESA: document frequency and listing (not part of the reference's surface) ----
+ * The text is the concatenation of ndocs documents WITHOUT separators; doc_start[0 .. ndocs] (host memory in both forms) gives
+ * the boundaries: doc_start[0] = 0, non-decreasing, doc_start[ndocs] = n.  Empty documents are allowed.  1 <= ndocs <=
+ * TC_ESA_MAX_DOCS.  THE FIRST-BYTE RULE: an occurrence belongs to the document that holds its first byte, so an occurrence that
+ * runs across a boundary counts for the document it starts in.  A caller who must not see such matches puts a byte between the
+ * documents that their queries do not contain.  All 256 byte values stay legal in the text.
+ * tc_esa_build_docs / _dev: the handle of tc_esa_build and, over its N = n + 1 rows, da[r] = the document of sa[r]
+ * (TC_ESA_NO_DOC for row 0, the empty suffix), pv[r] = 1 + the largest row r' < r with da[r'] = da[r], 0 where there is none
+ * (pv[0] = 0xffffffff), and a min tree over pv: 8 bytes per text byte and one tree more, about 21.2 in all.  A doc_start that
+ * breaks the rules is TC_ERR_ARG before any device work.  n = 0 with all documents empty builds the one-row handle.  A failed build
+ * releases everything and leaves *out NULL.  Every query and analysis of a plain handle works on a handle with documents
+ * unchanged.  tc_esa_ndocs: 0 for a plain handle.  tc_esa_doc_arrays: the device pointers (each out-pointer may be NULL), valid
+ * until tc_esa_free.  tc_esa_read takes what = 5 (da), 6 (pv), 7 (doc_start, ndocs + 1 entries); tc_esa_device_bytes part 6 (da +
+ * doc_start) and part 7 (pv + its min tree), 0 on a plain handle; on every handle parts 1 .. 7 sum to part 0.
+ * THE QUERIES are over substrings text[start .. start + len) as tc_esa_find takes them.  On a plain handle: TC_ERR_ARG.
+ * DOC COUNT: df[q] is the number of distinct documents with an occurrence; with limit > 0 the count saturates at limit (limit 2
+ * asks "in more than one document?"), limit 0 counts all.  occ[q] is the number of occurrences as in tc_esa_find (occ may be
+ * NULL).  len = 0 counts the non-empty documents.
+ * DOC LIST: the documents of query q are docs[list_offs[q] .. list_offs[q + 1]), in the order of their first row in the
+ * substring's suffix-array interval; hit_pos (may be NULL) is sa of that row: one occurrence in that document.  At most limit
+ * documents per query when limit > 0.  list_offs has nq + 1 entries.  *ntotal: in = capacity of docs and hit_pos, out = the
+ * total; too small: TC_ERR_CAPACITY, *ntotal = the needed total, nothing written to docs or hit_pos (capacity 0 with NULL arrays
+ * asks for the sizes).  A sizes pass and a fill pass without atomics: two calls give identical output.
+ *   banana . bandana . ananas, doc_start = {0, 6, 13, 19}: (1, 3) "ana" has 5 occurrences in documents 1, 0, 2 with hit_pos 10,
+ *   3, 13; (0, 3) "ban" is in documents 0, 1; (2, 3) "nan" in 0, 2; (9, 1) "d" in 1; (3, 4) "anab" in 0 -- it starts in banana
+ *   and ends in bandana: the first-byte rule; (0, 0) lists every non-empty document: 1, 0, 2
+ * K-MER DOCS: the k-mers of tc_kmers_esa_dev with no occurrence filter, in the same order and with the same kmer_pos, kmer_occ
+ * and kmer_row, and kmer_df, the number of distinct documents a k-mer occurs in; filtered to min_df <= df, and df <= max_df unless
+ * max_df = 0 (no upper bound): (1, 1) lists the markers of a single document, (ndocs, 0) the k-mers every document has.  Each
+ * output may be NULL.  *nk: in = capacity of the arrays, out = the count; too small: TC_ERR_CAPACITY, *nk = the needed count,
+ * nothing written (capacity 0 with all arrays NULL asks for the count).  k = 0 is TC_ERR_ARG, k > n gives no k-mer.
+ * K-MER DOC SPECTRUM: hist[d], d = 0 .. ndocs, is the number of distinct k-mers that occur in exactly d documents (the core /
+ * shell / cloud curve; hist[0] is 0), *distinct their number: the hist sum to it.  hist is host memory, d_hist device memory.
+ *   the example above, k = 3: 11 distinct 3-mers, eight in one document, "ban" and "nan" in two, "ana" in all three (occ 5): hist
+ *   = {0, 8, 2, 1}
+ * ERRORS as for the queries above: a query that leaves the text is TC_ERR_ARG in both forms -- the kernel raises a flag, every
+ * access stays in bounds; nq = 0: TC_OK, nothing touched. */
+#define TC_ESA_MAX_DOCS 65535
+#define TC_ESA_NO_DOC 0xffffffffu
+int tc_esa_build_docs(tc_ctx *ctx, const uint8_t *text, uint64_t n, const uint32_t *doc_start, uint32_t ndocs, tc_esa **out);
+int tc_esa_build_docs_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uint32_t *doc_start, uint32_t ndocs, tc_esa **out);
+uint32_t tc_esa_ndocs(const tc_esa *esa);
+int tc_esa_doc_arrays(const tc_esa *esa, const uint32_t **d_doc_start, const uint32_t **d_da, const uint32_t **d_pv);
+int tc_esa_doc_count(tc_ctx *ctx, const tc_esa *esa, const uint32_t *start, const uint32_t *len, uint64_t nq, uint32_t limit,
+                     uint32_t *df, uint32_t *occ);
+int tc_esa_doc_count_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_start, const uint32_t *d_len, uint64_t nq, uint32_t limit,
+                         uint32_t *d_df, uint32_t *d_occ);
+int tc_esa_doc_list(tc_ctx *ctx, const tc_esa *esa, const uint32_t *start, const uint32_t *len, uint64_t nq, uint32_t limit,
+                    uint64_t *list_offs, uint32_t *docs, uint32_t *hit_pos, uint64_t *ntotal);
+int tc_esa_doc_list_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_start, const uint32_t *d_len, uint64_t nq, uint32_t limit,
+                        uint64_t *d_list_offs, uint32_t *d_docs, uint32_t *d_hit_pos, uint64_t *ntotal);
+int tc_esa_kmer_docs(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint32_t min_df, uint32_t max_df, uint32_t *kmer_pos,
+                     uint32_t *kmer_occ, uint32_t *kmer_df, uint32_t *kmer_row, uint64_t *nk);
+int tc_esa_kmer_docs_dev(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint32_t min_df, uint32_t max_df, uint32_t *d_kmer_pos,
+                         uint32_t *d_kmer_occ, uint32_t *d_kmer_df, uint32_t *d_kmer_row, uint64_t *nk);
+int tc_esa_kmer_doc_spectrum(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint64_t *hist, uint64_t *distinct);
+int tc_esa_kmer_doc_spectrum_dev(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint64_t *d_hist, uint64_t *distinct);
 /* ---- the k-mers of a text: list, abundance spectrum and all-k profile (not part of the reference's surface) ----
  * N = n + 1 rows; sa and lcp as tc_lcp_array defines them (row 0 is the empty suffix, the end of the text matches
  * nothing); lcp[0] counts as 0 whatever the array holds, and lcp[N] as 0.  For k >= 1 row q is a BOUNDARY iff lcp[q] < k;

@@ -16,11 +16,16 @@ struct tc_esa {
     MinTree tree;               // both trees are over the N rows: one shape
     u8 *d_text = nullptr;
     u32 *d_sa = nullptr, *d_isa = nullptr, *d_lcp = nullptr, *d_lcp_min = nullptr, *d_sa_min = nullptr;
+    // the document part (tc_esa_docs_host.hpp; ndocs = 0: a plain handle, the four blocks null): doc_start, ndocs + 1 entries,
+    // da and pv, N entries each, and the min tree of pv -- 8 + 4 / (f - 1) bytes per text byte more
+    u32 ndocs = 0;
+    u32 *d_doc_start = nullptr, *d_da = nullptr, *d_pv = nullptr, *d_pv_min = nullptr;
 };
 
 static u64 esa_text_bytes(const tc_esa *e) { return (e->n + 16 + 15) & ~(u64)15; }
 static u64 esa_rows_bytes(const tc_esa *e) { return (e->N * sizeof(u32) + 15) & ~(u64)15; }
 static u64 esa_tree_bytes(const tc_esa *e) { return (u64)e->tree.words * sizeof(u32); }
+static u64 esa_doc_start_bytes(const tc_esa *e) { return (((u64)e->ndocs + 1) * sizeof(u32) + 15) & ~(u64)15; }
 
 static void esa_release(tc_esa *e) {
     if (!e) return;
@@ -31,14 +36,21 @@ static void esa_release(tc_esa *e) {
     if (e->d_lcp) (void)hipFree(e->d_lcp);
     if (e->d_lcp_min) (void)hipFree(e->d_lcp_min);
     if (e->d_sa_min) (void)hipFree(e->d_sa_min);
+    if (e->d_doc_start) (void)hipFree(e->d_doc_start);
+    if (e->d_da) (void)hipFree(e->d_da);
+    if (e->d_pv) (void)hipFree(e->d_pv);
+    if (e->d_pv_min) (void)hipFree(e->d_pv_min);
     delete e;
 }
 
-// tc_esa_device_bytes: 0 all, 1 text, 2 sa, 3 isa, 4 lcp + its min tree, 5 the min tree of sa
+// tc_esa_device_bytes: 0 all, 1 text, 2 sa, 3 isa, 4 lcp + its min tree, 5 the min tree of sa; on a handle with documents
+// 6 da + doc_start, 7 pv + its min tree (0 on a plain one)
 static u64 esa_device_bytes(const tc_esa *e, int part) {
     if (!e) return 0;
     switch (part) {
-    case 0: return esa_text_bytes(e) + 3 * esa_rows_bytes(e) + 2 * esa_tree_bytes(e);
+    case 0: return esa_text_bytes(e) + 3 * esa_rows_bytes(e) + 2 * esa_tree_bytes(e) + esa_device_bytes(e, 6) + esa_device_bytes(e, 7);
+    case 6: return e->ndocs ? esa_rows_bytes(e) + esa_doc_start_bytes(e) : 0;
+    case 7: return e->ndocs ? esa_rows_bytes(e) + esa_tree_bytes(e) : 0;
     case 1: return esa_text_bytes(e);
     case 2: case 3: return esa_rows_bytes(e);
     case 4: return esa_rows_bytes(e) + esa_tree_bytes(e);
@@ -100,12 +112,14 @@ static void esa_check_handle(tc_ctx *ctx, const tc_esa *e) {
 // tc_esa_read: entries [first, first + count) of one array to host or device memory
 static void esa_read_entry(tc_ctx *ctx, const tc_esa *e, int what, u64 first, u64 count, void *dst, bool dst_on_device) {
     esa_check_handle(ctx, e);
-    if (what < 1 || what > 4) TC_FAIL(ctx, TC_ERR_ARG, "what is 1 (text), 2 (sa), 3 (isa) or 4 (lcp)");
-    const u64 have = what == 1 ? e->n : e->N, size = what == 1 ? 1 : sizeof(u32);
+    if (what < 1 || what > (e->ndocs ? 7 : 4))
+        TC_FAIL(ctx, TC_ERR_ARG, "what is 1 (text), 2 (sa), 3 (isa) or 4 (lcp); on a handle with documents also 5 (da), 6 (pv), 7 (doc_start)");
+    const u64 have = what == 1 ? e->n : what == 7 ? (u64)e->ndocs + 1 : e->N, size = what == 1 ? 1 : sizeof(u32);
     if (first > have || count > have - first) TC_FAIL(ctx, TC_ERR_ARG, "the range leaves the array (%llu entries)", (unsigned long long)have);
     if (count == 0) return;
     if (!dst) TC_FAIL(ctx, TC_ERR_ARG, "null buffer");
-    const u8 *src = what == 1 ? e->d_text : reinterpret_cast<const u8 *>(what == 2 ? e->d_sa : what == 3 ? e->d_isa : e->d_lcp);
+    const u32 *rows[8] = {nullptr, nullptr, e->d_sa, e->d_isa, e->d_lcp, e->d_da, e->d_pv, e->d_doc_start};
+    const u8 *src = what == 1 ? e->d_text : reinterpret_cast<const u8 *>(rows[what]);
     TC_HIP(ctx, hipMemcpyAsync(dst, src + first * size, count * size, dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
                                ctx->stream));
     tc_sync_check(ctx);

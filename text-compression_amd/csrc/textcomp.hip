@@ -18,6 +18,7 @@
 #include "tc_sus_host.hpp"
 #include "tc_cov_host.hpp"
 #include "tc_esa_host.hpp"
+#include "tc_esa_docs_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -488,6 +489,85 @@ int tc_esa_compare_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_a_start
                        const uint32_t *d_b_len, uint64_t nq, int8_t *d_order, uint32_t *d_common) {
     TC_API_BEGIN(ctx)
     esa_compare_entry(ctx, esa, d_a_start, d_a_len, d_b_start, d_b_len, nq, reinterpret_cast<signed char *>(d_order), d_common, true);
+    TC_API_END(ctx)
+}
+
+// document collections on the kept enhanced suffix array (no counterpart in the reference): tc_esa_docs_host.hpp
+int tc_esa_build_docs(tc_ctx *ctx, const uint8_t *text, uint64_t n, const uint32_t *doc_start, uint32_t ndocs, tc_esa **out) {
+    if (out) *out = nullptr;
+    TC_API_BEGIN(ctx)
+    esa_build_docs_entry(ctx, text, n, doc_start, ndocs, out, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_build_docs_dev(tc_ctx *ctx, const uint8_t *d_text, uint64_t n, const uint32_t *doc_start, uint32_t ndocs, tc_esa **out) {
+    if (out) *out = nullptr;
+    TC_API_BEGIN(ctx)
+    esa_build_docs_entry(ctx, d_text, n, doc_start, ndocs, out, true);
+    TC_API_END(ctx)
+}
+
+uint32_t tc_esa_ndocs(const tc_esa *esa) { return esa ? esa->ndocs : 0; }
+
+int tc_esa_doc_arrays(const tc_esa *esa, const uint32_t **d_doc_start, const uint32_t **d_da, const uint32_t **d_pv) {
+    if (!esa || !esa->ndocs) return TC_ERR_ARG;
+    if (d_doc_start) *d_doc_start = esa->d_doc_start;
+    if (d_da) *d_da = esa->d_da;
+    if (d_pv) *d_pv = esa->d_pv;
+    return TC_OK;
+}
+
+int tc_esa_doc_count(tc_ctx *ctx, const tc_esa *esa, const uint32_t *start, const uint32_t *len, uint64_t nq, uint32_t limit, uint32_t *df,
+                     uint32_t *occ) {
+    TC_API_BEGIN(ctx)
+    esa_doc_count_entry(ctx, esa, start, len, nq, limit, df, occ, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_doc_count_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_start, const uint32_t *d_len, uint64_t nq, uint32_t limit,
+                         uint32_t *d_df, uint32_t *d_occ) {
+    TC_API_BEGIN(ctx)
+    esa_doc_count_entry(ctx, esa, d_start, d_len, nq, limit, d_df, d_occ, true);
+    TC_API_END(ctx)
+}
+
+int tc_esa_doc_list(tc_ctx *ctx, const tc_esa *esa, const uint32_t *start, const uint32_t *len, uint64_t nq, uint32_t limit,
+                    uint64_t *list_offs, uint32_t *docs, uint32_t *hit_pos, uint64_t *ntotal) {
+    TC_API_BEGIN(ctx)
+    esa_doc_list_entry(ctx, esa, start, len, nq, limit, list_offs, docs, hit_pos, ntotal, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_doc_list_dev(tc_ctx *ctx, const tc_esa *esa, const uint32_t *d_start, const uint32_t *d_len, uint64_t nq, uint32_t limit,
+                        uint64_t *d_list_offs, uint32_t *d_docs, uint32_t *d_hit_pos, uint64_t *ntotal) {
+    TC_API_BEGIN(ctx)
+    esa_doc_list_entry(ctx, esa, d_start, d_len, nq, limit, d_list_offs, d_docs, d_hit_pos, ntotal, true);
+    TC_API_END(ctx)
+}
+
+int tc_esa_kmer_docs(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint32_t min_df, uint32_t max_df, uint32_t *kmer_pos, uint32_t *kmer_occ,
+                     uint32_t *kmer_df, uint32_t *kmer_row, uint64_t *nk) {
+    TC_API_BEGIN(ctx)
+    esa_kmer_docs_entry(ctx, esa, k, min_df, max_df, kmer_pos, kmer_occ, kmer_df, kmer_row, nk, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_kmer_docs_dev(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint32_t min_df, uint32_t max_df, uint32_t *d_kmer_pos,
+                         uint32_t *d_kmer_occ, uint32_t *d_kmer_df, uint32_t *d_kmer_row, uint64_t *nk) {
+    TC_API_BEGIN(ctx)
+    esa_kmer_docs_entry(ctx, esa, k, min_df, max_df, d_kmer_pos, d_kmer_occ, d_kmer_df, d_kmer_row, nk, true);
+    TC_API_END(ctx)
+}
+
+int tc_esa_kmer_doc_spectrum(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint64_t *hist, uint64_t *distinct) {
+    TC_API_BEGIN(ctx)
+    esa_kmer_doc_spectrum_entry(ctx, esa, k, hist, distinct, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_kmer_doc_spectrum_dev(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint64_t *d_hist, uint64_t *distinct) {
+    TC_API_BEGIN(ctx)
+    esa_kmer_doc_spectrum_entry(ctx, esa, k, d_hist, distinct, true);
     TC_API_END(ctx)
 }
 

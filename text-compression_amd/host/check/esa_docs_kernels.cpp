@@ -1,0 +1,470 @@
+// Stand-alone host check of the document queries on the kept enhanced suffix array (csrc/tc_esa_docs.hpp), meant to be built with
+// a host sanitizer:
+//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I text-compression_amd/csrc
+//       text-compression_amd/host/check/esa_docs_kernels.cpp -o esa_docs_kernels && ./esa_docs_kernels
+// TC_FM_MS_HOST_CHECK compiles esd_doc_of and both instances of esd_doc_kernel, with the row searches of csrc/tc_fm_ms.hpp, as plain
+// C++, as host/check/esa_kernels.cpp does for the queries of tc_esa.hpp: the HIP keywords defined away, the lanes run one after
+// another.  Everything around them is built naively here -- suffixes sorted directly, lcp by comparing neighbours, da by esd_doc_of
+// against a loop, pv by a walk back over the rows, the min trees of lcp and pv by fm_lmin_kernel at fan-outs 4 and 64 -- in heap
+// blocks of exactly the bytes the library's handle allocates, and every query and result array holds exactly the entries the call
+// defines, so a read or a store one element outside any of them stops the run.  Every answer is compared with loops over the bytes.
+// Texts: unary, periodic, Fibonacci, random over 2 and 4 letters; documents: 1, 2, 3, 7 with empty ones first, last and adjacent,
+// one per byte, and two-document splits of a unary text that put the second first row at every distance.  Queries: all substrings
+// up to 40 bytes, sampled and adversarial ones above; limits 0, 1, 2, 5; a pv -- and a tree -- of arbitrary contents; an isa that names no row; queries
+// that leave the text, which must raise the flag and read nothing: their batch runs on null arrays.  The document frequency of
+// the k-mers: the tiles of kmd_flag_kernel and kmd_pass_kernel, lane after lane, at k = 1, 2, 3, 8, 21 on every collection above and
+// on texts of one, two and three tiles of rows, against the documents of every distinct k-mer.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <random>
+#include <string>
+#include <vector>
+
+#define TC_FM_MS_HOST_CHECK
+#include "tc_esa_docs.hpp"
+
+#define EXPECT(cond)                                                              \
+    do {                                                                          \
+        if (!(cond)) {                                                            \
+            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
+            std::exit(1);                                                         \
+        }                                                                         \
+    } while (0)
+
+template <class F>
+static void launch(u64 grid, F &&kernel) {
+    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
+}
+template <class T>
+static std::unique_ptr<T[]> block_bytes(size_t bytes) {
+    EXPECT(bytes % sizeof(T) == 0);
+    return std::unique_ptr<T[]>(new T[bytes / sizeof(T) ? bytes / sizeof(T) : 1]);
+}
+template <class T>
+static std::unique_ptr<T[]> block_of(const std::vector<T> &v) {
+    std::unique_ptr<T[]> p(new T[v.size() ? v.size() : 1]);
+    std::copy(v.begin(), v.end(), p.get());
+    return p;
+}
+
+typedef std::vector<u8> Bytes;
+struct Pair { u32 a, b; };
+
+static u64 g_texts = 0, g_queries = 0, g_refused = 0, g_garbage = 0;
+static u64 g_pv_up[FM_MS_MAXLEV + 1] = {};
+static u32 g_maxlev4 = 0;
+static bool g_row1 = false, g_rowlast = false, g_len0 = false, g_empty_first = false, g_empty_last = false, g_empty_adjacent = false;
+
+// ---- the handle, naively, in the library's block sizes (tc_esa_host.hpp) -----------------------------------------------------
+struct Esa {
+    u32 n, N, lf, nlev, words, ndocs;
+    std::vector<u32> ds;
+    std::unique_ptr<u32[]> doc_start, sa, isa, lcp, da, pv, lcp_min, pv_min;
+};
+static void build_tree(const Esa &e, const u32 *src, u32 *lmin) {
+    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1], words;
+    const u32 nlev = fm_ms_tree_shape(e.N, e.lf, off, cnt, &words);
+    for (u32 k = 1; k <= nlev; k++) {
+        u32 *dst = lmin + off[k];
+        launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], e.lf, dst, cnt[k]); });
+        src = dst;
+    }
+}
+static Esa esa_of(const Bytes &t, const std::vector<u32> &ds, u32 lf) {
+    Esa e;
+    e.n = (u32)t.size();
+    e.N = e.n + 1;
+    e.lf = lf;
+    e.ds = ds;
+    e.ndocs = (u32)ds.size() - 1;
+    const u32 n = e.n, N = e.N;
+    const size_t rows = ((size_t)N * 4 + 15) & ~(size_t)15;
+    e.doc_start = block_bytes<u32>((ds.size() * 4 + 15) & ~(size_t)15);
+    std::copy(ds.begin(), ds.end(), e.doc_start.get());
+    e.sa = block_bytes<u32>(rows);
+    e.isa = block_bytes<u32>(rows);
+    e.lcp = block_bytes<u32>(rows);
+    e.da = block_bytes<u32>(rows);
+    e.pv = block_bytes<u32>(rows);
+    for (size_t i = 0; i < rows / 4; i++) e.sa[i] = e.isa[i] = e.lcp[i] = e.da[i] = e.pv[i] = 0xdeadbeefu;
+    for (u32 i = 0; i < N; i++) e.sa[i] = i;
+    std::sort(e.sa.get(), e.sa.get() + N, [&](u32 x, u32 y) {       // the empty suffix first: a proper prefix sorts first
+        const int c = std::memcmp(t.data() + x, t.data() + y, std::min(n - x, n - y));
+        return c ? c < 0 : x > y;
+    });
+    for (u32 j = 0; j < N; j++) {
+        u32 l = 0;
+        if (j) {
+            const u32 a = e.sa[j - 1], b = e.sa[j];
+            while (a + l < n && b + l < n && t[a + l] == t[b + l]) l++;
+        }
+        e.lcp[j] = l;
+        e.isa[e.sa[j]] = j;
+        // the document by the lane body of the build's first kernel, against a loop over the boundaries
+        u32 want = ESD_NO_DOC;
+        for (u32 d = 0; d < e.ndocs; d++)
+            if (ds[d] <= e.sa[j] && e.sa[j] < ds[d + 1]) want = d;
+        e.da[j] = esd_doc_of(e.doc_start.get(), e.ndocs, e.sa[j]);
+        EXPECT(e.da[j] == want);
+        u32 v = e.da[j] == ESD_NO_DOC ? 0xffffffffu : 0u;
+        for (u32 x = j; x-- > 0 && e.da[j] != ESD_NO_DOC;)
+            if (e.da[x] == e.da[j]) {
+                v = x + 1;
+                break;
+            }
+        e.pv[j] = v;
+    }
+    EXPECT(e.da[0] == ESD_NO_DOC && e.pv[0] == 0xffffffffu);
+    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1];
+    e.nlev = fm_ms_tree_shape(N, lf, off, cnt, &e.words);
+    e.lcp_min = block_bytes<u32>((size_t)e.words * 4);
+    e.pv_min = block_bytes<u32>((size_t)e.words * 4);
+    build_tree(e, e.lcp.get(), e.lcp_min.get());
+    build_tree(e, e.pv.get(), e.pv_min.get());
+    return e;
+}
+
+// ---- brute force: the rows whose suffix starts with text[s .. s + l), in row order; a document at its first such row -----------
+struct Want { std::vector<u32> docs, hits; u32 occ, lo, hi; };
+static Want brute(const Bytes &t, const Esa &e, u32 s, u32 l) {
+    Want w;
+    w.occ = 0; w.lo = 0xffffffffu; w.hi = 0;
+    for (u32 r = 0; r < e.N; r++) {
+        const u32 i = e.sa[r];
+        if (i + l > e.n || (l && std::memcmp(t.data() + i, t.data() + s, l))) continue;
+        w.occ++;
+        w.lo = std::min(w.lo, r);
+        w.hi = r + 1;
+        const u32 d = e.da[r];
+        if (d == ESD_NO_DOC || std::find(w.docs.begin(), w.docs.end(), d) != w.docs.end()) continue;
+        w.docs.push_back(d);
+        w.hits.push_back(i);
+    }
+    return w;
+}
+
+static void run_docs(const Esa &e, const std::vector<Pair> &q, const std::vector<struct Want> &wants, u32 limit, u32 outs);
+// one batch: the count instance in both of its output forms, the offsets as the host makes them, the fill instance
+static void run_docs(const Bytes &t, const Esa &e, const std::vector<Pair> &q, u32 limit, u32 outs) {    // outs: bit 0 occ, bit 1 hit_pos
+    std::vector<Want> wants;
+    for (const Pair &p : q) wants.push_back(brute(t, e, p.a, p.b));
+    run_docs(e, q, wants, limit, outs);
+}
+static void run_docs(const Esa &e, const std::vector<Pair> &q, const std::vector<Want> &wants, u32 limit, u32 outs) {
+    const u64 nq = q.size();
+    std::vector<u32> vs, vl;
+    for (const Pair &p : q) { vs.push_back(p.a); vl.push_back(p.b); }
+    auto s = block_of(vs), l = block_of(vl);
+    auto df = block_of(std::vector<u32>(nq, 0xabababab)), occ = block_of(std::vector<u32>(nq, 0xabababab));
+    auto cnt = block_of(std::vector<u64>(nq, 0xabababab));
+    u32 bad = 0;
+    launch(nq, [&] {
+        esd_doc_kernel<false>(e.n, e.sa.get(), e.isa.get(), e.lcp.get(), e.lcp_min.get(), e.da.get(), e.pv.get(), e.pv_min.get(), e.lf, e.ndocs,
+                              s.get(), l.get(), nq, limit, df.get(), outs & 1 ? occ.get() : nullptr, nullptr, nullptr, nullptr, nullptr, &bad);
+    });
+    launch(nq, [&] {
+        esd_doc_kernel<false>(e.n, e.sa.get(), e.isa.get(), e.lcp.get(), e.lcp_min.get(), e.da.get(), e.pv.get(), e.pv_min.get(), e.lf, e.ndocs,
+                              s.get(), l.get(), nq, limit, nullptr, nullptr, cnt.get(), nullptr, nullptr, nullptr, &bad);
+    });
+    EXPECT(bad == 0);
+    std::vector<u64> voffs(nq + 1, 0);
+    for (u64 k = 0; k < nq; k++) {
+        EXPECT(cnt[k] == df[k]);
+        voffs[k + 1] = voffs[k] + cnt[k];
+    }
+    const u64 total = voffs[nq];
+    auto offs = block_of(voffs);
+    auto docs = block_of(std::vector<u32>(total, 0xabababab)), hits = block_of(std::vector<u32>(total, 0xabababab));
+    launch(nq, [&] {
+        esd_doc_kernel<true>(e.n, e.sa.get(), e.isa.get(), e.lcp.get(), e.lcp_min.get(), e.da.get(), e.pv.get(), e.pv_min.get(), e.lf, e.ndocs,
+                             s.get(), l.get(), nq, limit, nullptr, nullptr, nullptr, offs.get(), docs.get(), outs & 2 ? hits.get() : nullptr, &bad);
+    });
+    EXPECT(bad == 0);
+    for (u64 k = 0; k < nq; k++) {
+        const Want &w = wants[k];      // (without a limit: a limit cuts the list)
+        EXPECT(df[k] == (limit && w.docs.size() > limit ? limit : w.docs.size()));
+        EXPECT(occ[k] == (outs & 1 ? (q[k].b ? w.occ : e.N) : 0xabababab));
+        for (u32 i = 0; i < df[k]; i++) {
+            EXPECT(docs[voffs[k] + i] == w.docs[i]);
+            EXPECT(hits[voffs[k] + i] == (outs & 2 ? w.hits[i] : 0xabababab));
+        }
+        g_len0 |= q[k].b == 0;
+        g_row1 |= q[k].b && w.lo == 1;
+        g_rowlast |= q[k].b && w.hi == e.N;
+    }
+    g_queries += nq;
+}
+
+// a pv -- and its tree -- of arbitrary contents: every access in bounds (the sanitizer's part), the loop finite, at most
+// min(limit, ndocs) documents per query, the fill inside its segment
+static void run_garbage(const Esa &e, const std::vector<Pair> &q, std::mt19937 &rng, bool garbage_tree) {
+    const size_t rows = ((size_t)e.N * 4 + 15) & ~(size_t)15;
+    auto pv = block_bytes<u32>(rows);
+    auto pv_min = block_bytes<u32>((size_t)e.words * 4);
+    for (u32 i = 0; i < e.N; i++) {
+        const u32 kind = rng() % 4;
+        pv[i] = kind == 0 ? 0u : kind == 1 ? (u32)(rng() % (e.N + 2)) : kind == 2 ? (u32)rng() : 1u;
+    }
+    if (garbage_tree)
+        for (u32 i = 0; i < e.words; i++) pv_min[i] = rng() % 3 ? (u32)(rng() % (e.N + 1)) : (u32)rng();
+    else
+        build_tree(e, pv.get(), pv_min.get());
+    const u64 nq = q.size();
+    std::vector<u32> vs, vl;
+    for (const Pair &p : q) { vs.push_back(p.a); vl.push_back(p.b); }
+    auto s = block_of(vs), l = block_of(vl);
+    for (u32 limit : {0u, 2u}) {
+        auto cnt = block_of(std::vector<u64>(nq, 0));
+        u32 bad = 0;
+        launch(nq, [&] {
+            esd_doc_kernel<false>(e.n, e.sa.get(), e.isa.get(), e.lcp.get(), e.lcp_min.get(), e.da.get(), pv.get(), pv_min.get(), e.lf, e.ndocs,
+                                  s.get(), l.get(), nq, limit, nullptr, nullptr, cnt.get(), nullptr, nullptr, nullptr, &bad);
+        });
+        std::vector<u64> voffs(nq + 1, 0);
+        for (u64 k = 0; k < nq; k++) {
+            EXPECT(cnt[k] <= e.ndocs && (!limit || cnt[k] <= limit));
+            voffs[k + 1] = voffs[k] + cnt[k];
+        }
+        auto offs = block_of(voffs);
+        auto docs = block_of(std::vector<u32>(voffs[nq], 0)), hits = block_of(std::vector<u32>(voffs[nq], 0));
+        launch(nq, [&] {
+            esd_doc_kernel<true>(e.n, e.sa.get(), e.isa.get(), e.lcp.get(), e.lcp_min.get(), e.da.get(), pv.get(), pv_min.get(), e.lf, e.ndocs,
+                                 s.get(), l.get(), nq, limit, nullptr, nullptr, nullptr, offs.get(), docs.get(), hits.get(), &bad);
+        });
+        EXPECT(bad == 0);
+        g_garbage += nq;
+    }
+}
+
+// an isa whose entries are no rows (no build writes one): the query has no interval, and its outputs are written -- 0 documents,
+// 0 occurrences -- so that the scan of the list's sizes reads no stale word
+static u64 g_no_row = 0;
+static void run_no_row(const Esa &e, const std::vector<Pair> &q) {
+    const size_t rows = ((size_t)e.N * 4 + 15) & ~(size_t)15;
+    auto isa = block_bytes<u32>(rows);
+    for (u32 i = 0; i < e.N; i++) isa[i] = i % 3 == 0 ? e.N : i % 3 == 1 ? e.N + 5u : 0xffffffffu;
+    const u64 nq = q.size();
+    std::vector<u32> vs, vl;
+    for (const Pair &p : q) { vs.push_back(p.a); vl.push_back(p.b); }
+    auto s = block_of(vs), l = block_of(vl);
+    auto df = block_of(std::vector<u32>(nq, 0xabababab)), occ = block_of(std::vector<u32>(nq, 0xabababab));
+    auto cnt = block_of(std::vector<u64>(nq, 0xabababab));
+    u32 bad = 0;
+    launch(nq, [&] {
+        esd_doc_kernel<false>(e.n, e.sa.get(), isa.get(), e.lcp.get(), e.lcp_min.get(), e.da.get(), e.pv.get(), e.pv_min.get(), e.lf, e.ndocs,
+                              s.get(), l.get(), nq, 0, df.get(), occ.get(), cnt.get(), nullptr, nullptr, nullptr, &bad);
+    });
+    EXPECT(bad == 0);
+    for (u64 k = 0; k < nq; k++) {
+        if (q[k].b == 0) continue;                  // (len = 0 does not read isa)
+        EXPECT(df[k] == 0 && occ[k] == 0 && cnt[k] == 0);
+        g_no_row++;
+    }
+}
+
+// queries that leave the text, alone in their batch: on null arrays, so a refused query that read anything would stop the run
+static void run_refused(u32 n, u32 lf) {
+    std::vector<Pair> q = {{n + 1, 0}, {0, n + 1}, {n, 1}, {1, 0xffffffffu}, {0xffffffffu, 2}, {5, 0xfffffffcu}, {0xffffffffu, 0xffffffffu}};
+    if (n < 5) q[5] = {n + 2, 0};
+    const u64 nq = q.size();
+    std::vector<u32> vs, vl;
+    for (const Pair &p : q) { vs.push_back(p.a); vl.push_back(p.b); }
+    auto s = block_of(vs), l = block_of(vl);
+    auto df = block_of(std::vector<u32>(nq, 0xabababab)), occ = block_of(std::vector<u32>(nq, 0xabababab));
+    auto cnt = block_of(std::vector<u64>(nq, 0xabababab));
+    const std::vector<u64> zero(nq + 1, 0);
+    auto offs = block_of(zero);
+    u32 bad = 0;
+    launch(nq, [&] {
+        esd_doc_kernel<false>(n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, lf, 3, s.get(), l.get(), nq, 0, df.get(), occ.get(),
+                              cnt.get(), nullptr, nullptr, nullptr, &bad);
+    });
+    EXPECT(bad == 1);
+    bad = 0;
+    launch(nq, [&] {
+        esd_doc_kernel<true>(n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, lf, 3, s.get(), l.get(), nq, 0, nullptr, nullptr, nullptr,
+                             offs.get(), nullptr, nullptr, &bad);
+    });
+    EXPECT(bad == 1);
+    for (u64 k = 0; k < nq; k++) EXPECT(df[k] == 0xabababab && occ[k] == 0xabababab && cnt[k] == 0xabababab);
+    g_refused += 2 * nq;
+}
+
+static void check_kmer_df(const Bytes &t, const Esa &e, u32 k);
+static void check_text(const Bytes &t, const std::vector<u32> &ds, u32 lf, std::mt19937 &rng) {
+    const Esa e = esa_of(t, ds, lf);
+    const u32 n = e.n;
+    for (u32 d = 0; d < e.ndocs; d++) {
+        const bool empty = ds[d] == ds[d + 1];
+        g_empty_first |= empty && d == 0 && e.ndocs > 1 && n;
+        g_empty_last |= empty && d == e.ndocs - 1 && e.ndocs > 1 && n;
+        g_empty_adjacent |= empty && d + 1 < e.ndocs && ds[d + 1] == ds[d + 2];
+    }
+    std::vector<Pair> subs;
+    if (n <= 40) {
+        for (u32 s = 0; s <= n; s++)
+            for (u32 l = 0; l <= n - s; l++) subs.push_back({s, l});
+    } else {
+        for (u32 k = 0; k < 300; k++) {
+            const u32 s = (u32)(rng() % (n + 1)), room = n - s;
+            const u32 l = k % 10 == 0 ? (u32)(rng() % (room + 1)) : std::min<u32>(room, (u32)(rng() % 6));
+            subs.push_back({s, l});
+        }
+        subs.push_back({0, n});
+        subs.push_back({n, 0});
+        subs.push_back({n - 1, 1});
+        subs.push_back({e.sa[1], 1});
+        subs.push_back({e.sa[e.N - 1], 1});
+        subs.push_back({e.sa[e.N - 1], n - e.sa[e.N - 1]});
+    }
+    std::vector<Want> wants;
+    for (const Pair &p : subs) wants.push_back(brute(t, e, p.a, p.b));
+    for (u32 limit : {0u, 1u, 2u, 5u}) run_docs(e, subs, wants, limit, limit == 1 ? 0u : limit == 2 ? 1u : 3u);
+    // the searches over the tree of pv alone: len = 0 runs no search over lcp
+    std::memset(fm_ms_climbed, 0, sizeof fm_ms_climbed);
+    run_docs(t, e, {{0, 0}, {n, 0}, {n / 2, 0}}, 0, 3);
+    if (lf == 2) {
+        for (u32 v = 0; v <= FM_MS_MAXLEV; v++) g_pv_up[v] += fm_ms_climbed[1][v];
+        g_maxlev4 = std::max(g_maxlev4, e.nlev);
+    }
+    run_garbage(e, subs, rng, false);
+    run_garbage(e, subs, rng, true);
+    run_no_row(e, subs);
+    run_refused(n, lf);
+    for (u32 k : {1u, 2u, 3u, 8u, 21u}) check_kmer_df(t, e, k);
+    g_texts++;
+}
+
+// ---- the document frequency of the k-mers: the tiles of kmd_flag_kernel and kmd_pass_kernel with their lanes run one after
+// another -- what the workgroup scans give a lane (the last boundary before it, the flags of the lanes before it) is a running
+// value here -- over the lane bodies km_mask16, km_lane_close, kmd_flags16, kmd_prefix and kmd_group_df, against the set of
+// documents of every distinct k-mer
+static u64 g_kmers = 0, g_carry_heads = 0, g_tiles_without_boundary = 0, g_long_groups = 0;
+static void check_kmer_df(const Bytes &t, const Esa &e, u32 k) {
+    const u64 N = e.N, n = e.n;
+    const u32 ntiles = (u32)(N / KM_TILE + 1);
+    std::vector<u32> mask((size_t)ntiles * KM_NT), fmask(mask.size()), lbase(mask.size()), prev1(mask.size()), inlast(ntiles);
+    std::vector<u64> fsum(ntiles), fbase(ntiles);
+    u32 run = 0;                                // the last boundary so far, + 1
+    for (u32 tile = 0; tile < ntiles; tile++) {
+        u32 flags = 0, tile_last = 0;
+        for (u32 lane = 0; lane < KM_NT; lane++) {
+            const size_t at = (size_t)tile * KM_NT + lane;
+            const u64 base = (u64)tile * KM_TILE + (u64)lane * KM_ROWS;
+            u32 w[KM_ROWS];
+            for (u32 i = 0; i < KM_ROWS; i++) w[i] = base + i < N ? e.lcp[base + i] : 0u;
+            mask[at] = km_mask16(w, base, N, k);
+            prev1[at] = run;
+            if (mask[at]) run = tile_last = km_last1(mask[at], base);
+            for (u32 i = 0; i < KM_ROWS; i++) w[i] = base + i < N ? e.pv[base + i] : 0u;
+            fmask[at] = kmd_flags16(mask[at], w, base, N, prev1[at]);
+            lbase[at] = flags;
+            flags += (u32)__builtin_popcount(fmask[at]);
+        }
+        fsum[tile] = flags;
+        const size_t t0 = (size_t)tile * KM_NT;
+        inlast[tile] = tile_last ? kmd_prefix(&lbase[t0], &fmask[t0], (u32)(tile_last - 1u - (u64)tile * KM_TILE)) : 0u;
+        g_tiles_without_boundary += tile_last == 0;
+    }
+    for (u32 tile = 1; tile < ntiles; tile++) fbase[tile] = fbase[tile - 1] + fsum[tile - 1];
+    struct Kmer { u32 pos, occ, df, row; };
+    std::vector<Kmer> got, want;
+    for (u32 tile = 0; tile < ntiles; tile++)
+        for (u32 lane = 0; lane < KM_NT; lane++) {
+            const size_t at = (size_t)tile * KM_NT + lane, t0 = (size_t)tile * KM_NT;
+            const u64 tile_base = (u64)tile * KM_TILE, base = tile_base + (u64)lane * KM_ROWS;
+            km_lane_close(mask[at], base, prev1[at], e.sa.get(), n, k, 1u, 0u, [&](u32, u32 row, u32 pos, u32 occ) {
+                got.push_back({pos, occ, kmd_group_df(row, occ, tile_base, &lbase[t0], &fmask[t0], fbase.data(), inlast.data()), row});
+                g_carry_heads += row < tile_base;
+                g_long_groups += occ > 2 * KM_TILE;
+            });
+        }
+    std::vector<u32> docs;
+    for (u32 r = 0; r < N; r++) {
+        const u32 i = e.sa[r];
+        if ((u64)i + k > n) continue;
+        if (want.empty() || std::memcmp(t.data() + want.back().pos, t.data() + i, k)) {
+            want.push_back({i, 0, 0, r});
+            docs.clear();
+        }
+        want.back().occ++;
+        if (std::find(docs.begin(), docs.end(), e.da[r]) == docs.end()) {
+            docs.push_back(e.da[r]);
+            want.back().df++;
+        }
+    }
+    EXPECT(got.size() == want.size());
+    for (size_t j = 0; j < got.size(); j++)
+        EXPECT(got[j].pos == want[j].pos && got[j].occ == want[j].occ && got[j].df == want[j].df && got[j].row == want[j].row);
+    g_kmers += got.size();
+}
+
+static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
+    Bytes t(n);
+    for (u8 &b : t) b = (u8)("ACGT"[rng() % sigma]);
+    return t;
+}
+static Bytes periodic(u32 n, u32 p) {
+    Bytes t(n);
+    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
+    return t;
+}
+static Bytes fibonacci(u32 n) {
+    std::string a = "A", b = "AB";
+    while (b.size() < n) {
+        const std::string c = b + a;
+        a = b;
+        b = c;
+    }
+    return Bytes(b.begin(), b.begin() + n);
+}
+static std::vector<u32> even_docs(u32 n, u32 ndocs) {
+    std::vector<u32> ds(ndocs + 1);
+    for (u32 d = 0; d <= ndocs; d++) ds[d] = (u32)((u64)d * n / ndocs);
+    return ds;
+}
+
+int main() {
+    std::mt19937 rng(0xD0C5);
+    for (u32 lf : {2u, 6u}) {
+        check_text(Bytes(), {0, 0}, lf, rng);
+        check_text(Bytes(), {0, 0, 0, 0}, lf, rng);
+        for (u32 n : {1u, 2u, 3u, 5u, 8u, 13u, 24u, 40u, 64u, 65u, 257u, 640u, 1100u}) {
+            std::vector<Bytes> texts = {Bytes(n, 'A'), periodic(n, 2), periodic(n, 7), fibonacci(n), random_text(rng, n, 2), random_text(rng, n, 4)};
+            for (const Bytes &t : texts) {
+                check_text(t, {0, n}, lf, rng);
+                check_text(t, {0, n / 3, n}, lf, rng);
+                check_text(t, {0, 0, n / 5, n / 5, n / 5, n / 2, n, n}, lf, rng);      // empty documents first, last and adjacent
+                if (n <= 257) check_text(t, even_docs(n, n), lf, rng);                 // a document per byte
+                if (n >= 24) check_text(t, even_docs(n, 9), lf, rng);
+            }
+        }
+        // a unary text of two documents: the rows 1 .. k are the second document's, so its first row lies k rows behind row 1,
+        // the first document's: the search over pv finds it at every level of the fan-out-4 tree
+        for (u32 k : {1u, 2u, 5u, 20u, 70u, 300u, 1200u, 2400u}) check_text(Bytes(2601, 'A'), {0, 2601 - k, 2601}, lf, rng);
+    }
+    // the k-mer tiles alone on texts of more than one and two tiles of rows: a unary text is one group over every tile
+    for (u32 n : {(u32)KM_TILE - 2, (u32)KM_TILE - 1, (u32)KM_TILE, 2u * KM_TILE - 1, 2u * KM_TILE, 3u * KM_TILE + 5}) {
+        std::vector<Bytes> texts = {Bytes(n, 'A'), periodic(n, 7), random_text(rng, n, 4)};
+        for (const Bytes &t : texts)
+            for (u32 ndocs : {1u, 3u, 300u}) {
+                const Esa e = esa_of(t, even_docs(n, ndocs), 6);
+                for (u32 k : {1u, 2u, 8u, 21u}) check_kmer_df(t, e, k);
+            }
+    }
+    EXPECT(g_kmers > 0 && g_carry_heads > 0 && g_tiles_without_boundary > 0 && g_long_groups > 0);
+    for (u32 v = 0; v <= g_maxlev4; v++) EXPECT(g_pv_up[v] > 0);        // every level of the fan-out-4 tree over pv
+    EXPECT(g_maxlev4 >= 5);
+    EXPECT(esd_seen[0] > 0 && esd_seen[1] > 0 && esd_seen[2] > 0 && esd_seen[3] > 0);     // the loop ended by each of its conditions
+    EXPECT(esd_seen[4] > 0 && esd_seen[5] == g_refused && g_no_row > 0);
+    EXPECT(g_row1 && g_rowlast && g_len0 && g_empty_first && g_empty_last && g_empty_adjacent);
+    std::printf("ok: the document queries on the kept ESA of %llu collections: %llu queries, %llu on arbitrary pv, %llu refused on null "
+                "arrays; every tree level reached at fan-out 4 (%u levels) by the search over pv; the document frequency of %llu k-mers, "
+                "%llu of them with their head in an earlier tile\n",
+                (unsigned long long)g_texts, (unsigned long long)g_queries, (unsigned long long)g_garbage, (unsigned long long)g_refused,
+                g_maxlev4, (unsigned long long)g_kmers, (unsigned long long)g_carry_heads);
+    return 0;
+}

@@ -1316,6 +1316,22 @@ class Context:
         self._check(self.lib.tc_esa_build_dev(self.handle, p, d_text.numel(), C.byref(h)))
         return ESAHandle(self, None, _handle=h)
 
+    def esa_build_docs(self, text, docs):
+        """the same of a collection: text is the concatenation of the documents, docs their boundaries doc_start[0 .. ndocs]
+        (textcomp.concat_docs makes both); the handle also answers document frequency and listing: tc_esa_build_docs"""
+        return ESAHandle(self, text, docs=docs)
+
+    def esa_build_docs_dev(self, d_text, docs):
+        """the same of a text that already lies in HBM (docs is a host array): tc_esa_build_docs_dev"""
+        import torch
+        torch.cuda.synchronize()
+        ds = np.ascontiguousarray(docs, dtype=np.uint32).ravel()
+        h = C.c_void_p()
+        p = C.c_void_p(d_text.data_ptr()) if d_text.numel() else None
+        self._check(self.lib.tc_esa_build_docs_dev(self.handle, p, d_text.numel(), _ptr(ds) if len(ds) else None, max(len(ds), 1) - 1,
+                                                   C.byref(h)))
+        return ESAHandle(self, None, _handle=h)
+
 
 class FMIndexHandle:
     """`tc_fm`: the device-resident FM-index of one text."""
@@ -1784,16 +1800,23 @@ class ESAHandle:
     """`tc_esa`: the device-resident enhanced suffix array of one text -- the text, sa, isa, lcp and two min trees -- built
     once.  Queries may come from any Context on the handle's device (ctx=...); by default from the one that built it."""
 
-    WHAT = {"text": _lib.TC_ESA_TEXT, "sa": _lib.TC_ESA_SA, "isa": _lib.TC_ESA_ISA, "lcp": _lib.TC_ESA_LCP}
+    WHAT = {"text": _lib.TC_ESA_TEXT, "sa": _lib.TC_ESA_SA, "isa": _lib.TC_ESA_ISA, "lcp": _lib.TC_ESA_LCP,
+            "da": _lib.TC_ESA_DA, "pv": _lib.TC_ESA_PV, "doc_start": _lib.TC_ESA_DOC_START}
 
-    def __init__(self, ctx, text, _handle=None):
+    def __init__(self, ctx, text, _handle=None, docs=None):
         self._ctx = ctx
         if _handle is None:
             t = _u8(text)
             _handle = C.c_void_p()
-            ctx._check(ctx.lib.tc_esa_build(ctx.handle, _ptr(t) if len(t) else None, len(t), C.byref(_handle)))
+            if docs is None:
+                ctx._check(ctx.lib.tc_esa_build(ctx.handle, _ptr(t) if len(t) else None, len(t), C.byref(_handle)))
+            else:
+                ds = np.ascontiguousarray(docs, dtype=np.uint32).ravel()
+                ctx._check(ctx.lib.tc_esa_build_docs(ctx.handle, _ptr(t) if len(t) else None, len(t), _ptr(ds) if len(ds) else None,
+                                                     max(len(ds), 1) - 1, C.byref(_handle)))
         self._h = _handle
         self.n = int(ctx.lib.tc_esa_n(self._h))
+        self.ndocs = int(ctx.lib.tc_esa_ndocs(self._h))     # 0: a plain handle
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1814,21 +1837,22 @@ class ESAHandle:
 
     def device_bytes(self, part=0):
         """device bytes the handle holds: part 0 = everything, 1 = the text, 2 = sa, 3 = isa, 4 = lcp and its min tree,
-        5 = the min tree of sa"""
+        5 = the min tree of sa, 6 = da and doc_start, 7 = pv and its min tree (6 and 7: 0 on a plain handle)"""
         return int(self._ctx.lib.tc_esa_device_bytes(self._h, int(part)))
 
     def _what(self, what):
         w = self.WHAT.get(what, what)
         if w not in self.WHAT.values():
-            raise ValueError("what is 'text', 'sa', 'isa' or 'lcp', not %r" % (what,))
+            raise ValueError("what is 'text', 'sa', 'isa', 'lcp', 'da', 'pv' or 'doc_start', not %r" % (what,))
         return w
 
     def _range(self, w, first, count):
-        have = self.n if w == _lib.TC_ESA_TEXT else self.n + 1
+        have = self.n if w == _lib.TC_ESA_TEXT else self.ndocs + 1 if w == _lib.TC_ESA_DOC_START else self.n + 1
         return int(first), int(have - first if count is None else count)
 
     def read(self, what, first=0, count=None, ctx=None):
-        """entries [first, first + count) of 'text' (uint8) or 'sa', 'isa', 'lcp' (uint32) -> numpy array: tc_esa_read"""
+        """entries [first, first + count) of 'text' (uint8) or 'sa', 'isa', 'lcp' and, on a handle with documents, 'da', 'pv',
+        'doc_start' (uint32) -> numpy array: tc_esa_read"""
         ctx = ctx or self._ctx
         w = self._what(what)
         first, count = self._range(w, first, count)
@@ -1932,6 +1956,133 @@ class ESAHandle:
                                               C.c_void_p(c.data_ptr()) if common and nq else None))
         return (order, c) if common else order
 
+    # ---- document collections (a handle of esa_build_docs): in how many documents, and in which, does a substring occur
+    def doc_arrays(self):
+        """-> (d_doc_start, d_da, d_pv): the device addresses of the document arrays, valid until close: tc_esa_doc_arrays"""
+        p = [C.c_void_p() for _ in range(3)]
+        rc = self._ctx.lib.tc_esa_doc_arrays(self._h, *(C.byref(x) for x in p))
+        if rc != 0:
+            raise TcError(rc, "tc_esa_doc_arrays")
+        return tuple(x.value for x in p)
+
+    def doc_count(self, start, length, limit=0, occ=False, ctx=None):
+        """df[q] = the number of distinct documents in which text[start[q] : start[q] + length[q]] occurs, saturating at limit
+        where limit > 0 -> uint32 array, or (df, occ) with occ=True: tc_esa_doc_count"""
+        ctx = ctx or self._ctx
+        s, l = self._u32s(start, length)
+        df = np.zeros(len(s), np.uint32)
+        oc = np.zeros(len(s), np.uint32) if occ else None
+        ctx._check(ctx.lib.tc_esa_doc_count(ctx.handle, self._h, _ptr(s), _ptr(l), len(s), int(limit), _ptr(df), _ptr(oc)))
+        return (df, oc) if occ else df
+
+    def doc_count_dev(self, d_start, d_length, limit=0, occ=False, ctx=None):
+        """the same on int32 tensors resident on the device -> int32 tensor(s): tc_esa_doc_count_dev"""
+        import torch
+        ctx = ctx or self._ctx
+        ps, pl = self._i32s(d_start, d_length)
+        nq = d_start.numel()
+        df = torch.zeros(nq, dtype=torch.int32, device=d_start.device)
+        oc = torch.zeros(nq, dtype=torch.int32, device=d_start.device) if occ else None
+        torch.cuda.synchronize()
+        ctx._check(ctx.lib.tc_esa_doc_count_dev(ctx.handle, self._h, ps, pl, nq, int(limit), C.c_void_p(df.data_ptr()) if nq else None,
+                                                C.c_void_p(oc.data_ptr()) if occ and nq else None))
+        return (df, oc) if occ else df
+
+    def doc_list(self, start, length, limit=0, hit_pos=False, ctx=None):
+        """the documents in which text[start[q] : start[q] + length[q]] occurs -> (list_offs, docs[, hit_pos]): query q's documents
+        are docs[list_offs[q] : list_offs[q + 1]], in the order of their first row in the interval; hit_pos is one occurrence in
+        each.  uint64 / uint32 arrays: tc_esa_doc_list (the sizes first, then the lists)"""
+        ctx = ctx or self._ctx
+        s, l = self._u32s(start, length)
+        offs = np.zeros(len(s) + 1, np.uint64)
+        total = C.c_uint64(0)
+        rc = ctx.lib.tc_esa_doc_list(ctx.handle, self._h, _ptr(s), _ptr(l), len(s), int(limit), _ptr(offs), None, None, C.byref(total))
+        if rc != _lib.TC_ERR_CAPACITY:
+            ctx._check(rc)
+        docs = np.zeros(total.value, np.uint32)
+        hits = np.zeros(total.value, np.uint32) if hit_pos else None
+        if total.value:
+            ctx._check(ctx.lib.tc_esa_doc_list(ctx.handle, self._h, _ptr(s), _ptr(l), len(s), int(limit), _ptr(offs), _ptr(docs), _ptr(hits),
+                                               C.byref(total)))
+        return (offs, docs, hits) if hit_pos else (offs, docs)
+
+    def doc_list_dev(self, d_start, d_length, limit=0, hit_pos=False, ctx=None):
+        """the same on int32 tensors resident on the device -> (list_offs, an int64 tensor, docs[, hit_pos], int32 tensors):
+        tc_esa_doc_list_dev"""
+        import torch
+        ctx = ctx or self._ctx
+        ps, pl = self._i32s(d_start, d_length)
+        nq = d_start.numel()
+        offs = torch.zeros(nq + 1, dtype=torch.int64, device=d_start.device)
+        total = C.c_uint64(0)
+        torch.cuda.synchronize()
+        rc = ctx.lib.tc_esa_doc_list_dev(ctx.handle, self._h, ps, pl, nq, int(limit), C.c_void_p(offs.data_ptr()), None, None, C.byref(total))
+        if rc != _lib.TC_ERR_CAPACITY:
+            ctx._check(rc)
+        docs = torch.zeros(total.value, dtype=torch.int32, device=d_start.device)
+        hits = torch.zeros(total.value, dtype=torch.int32, device=d_start.device) if hit_pos else None
+        torch.cuda.synchronize()
+        if total.value:
+            ctx._check(ctx.lib.tc_esa_doc_list_dev(ctx.handle, self._h, ps, pl, nq, int(limit), C.c_void_p(offs.data_ptr()),
+                                                   C.c_void_p(docs.data_ptr()), C.c_void_p(hits.data_ptr()) if hit_pos else None,
+                                                   C.byref(total)))
+        return (offs, docs, hits) if hit_pos else (offs, docs)
+
+    def kmer_doc_count(self, k, min_df=1, max_df=0, ctx=None):
+        """the number of distinct k-mers that occur in min_df .. max_df documents (max_df 0: no upper bound): the sizes-only form
+        of tc_esa_kmer_docs_dev"""
+        ctx = ctx or self._ctx
+        nk = C.c_uint64(0)
+        ctx._check(ctx.lib.tc_esa_kmer_docs_dev(ctx.handle, self._h, int(k), int(min_df), int(max_df), None, None, None, None, C.byref(nk)))
+        return int(nk.value)
+
+    def kmer_docs(self, k, min_df=1, max_df=0, ctx=None):
+        """the k-mers of the text with their document frequency -> (pos, occ, df, row), uint32 arrays: the k-mers of kmers(k) in the
+        same order, filtered to min_df <= df <= max_df (max_df 0: no upper bound): tc_esa_kmer_docs"""
+        ctx = ctx or self._ctx
+        need = self.kmer_doc_count(k, min_df, max_df, ctx=ctx)
+        out = [np.zeros(need, np.uint32) for _ in range(4)]
+        nk = C.c_uint64(need)
+        if need:
+            ctx._check(ctx.lib.tc_esa_kmer_docs(ctx.handle, self._h, int(k), int(min_df), int(max_df), *(_ptr(o) for o in out), C.byref(nk)))
+        return tuple(out)
+
+    def kmer_docs_dev(self, k, min_df=1, max_df=0, cap=None, ctx=None):
+        """the same -> int32 tensors on the device: tc_esa_kmer_docs_dev.  cap: the k-mer slots to try first (None: the sizes first)"""
+        import torch
+        ctx = ctx or self._ctx
+        cap = max(self.kmer_doc_count(k, min_df, max_df, ctx=ctx) if cap is None else int(cap), 1)
+        for _ in range(2):
+            out = [torch.empty(cap, dtype=torch.int32, device="cuda:%d" % ctx.device) for _ in range(4)]
+            torch.cuda.synchronize()
+            nk = C.c_uint64(cap)
+            rc = ctx.lib.tc_esa_kmer_docs_dev(ctx.handle, self._h, int(k), int(min_df), int(max_df), *(C.c_void_p(o.data_ptr()) for o in out),
+                                              C.byref(nk))
+            if rc != _lib.TC_ERR_CAPACITY:
+                break
+            cap = max(int(nk.value), 1)
+        ctx._check(rc)
+        return tuple(o[:int(nk.value)] for o in out)
+
+    def kmer_doc_spectrum(self, k, ctx=None):
+        """-> (hist, distinct): hist[d], d = 0 .. ndocs, the number of distinct k-mers that occur in exactly d documents, a uint64
+        array: tc_esa_kmer_doc_spectrum"""
+        ctx = ctx or self._ctx
+        hist = np.zeros(self.ndocs + 1, np.uint64)
+        distinct = C.c_uint64()
+        ctx._check(ctx.lib.tc_esa_kmer_doc_spectrum(ctx.handle, self._h, int(k), _ptr(hist), C.byref(distinct)))
+        return hist, int(distinct.value)
+
+    def kmer_doc_spectrum_dev(self, k, ctx=None):
+        """the same -> (hist, an int64 tensor on the device, distinct): tc_esa_kmer_doc_spectrum_dev"""
+        import torch
+        ctx = ctx or self._ctx
+        d_hist = torch.empty(self.ndocs + 1, dtype=torch.int64, device="cuda:%d" % ctx.device)
+        distinct = C.c_uint64()
+        torch.cuda.synchronize()
+        ctx._check(ctx.lib.tc_esa_kmer_doc_spectrum_dev(ctx.handle, self._h, int(k), C.c_void_p(d_hist.data_ptr()), C.byref(distinct)))
+        return d_hist, int(distinct.value)
+
     # ---- further analyses on the arrays the handle keeps: the sort is paid once
     def arrays(self):
         """-> (d_text, d_sa, d_lcp, d_isa): the device addresses of the handle's arrays, valid until close: tc_esa_arrays"""
@@ -1973,6 +2124,18 @@ class ESAHandle:
 
 
 _DEFAULT = None
+
+
+def concat_docs(docs):
+    """a list of bytes-likes -> (text, doc_start): their concatenation without separators as a uint8 array and the ndocs + 1
+    boundaries as a uint32 array, what Context.esa_build_docs takes"""
+    parts = [_u8(d) for d in docs]
+    doc_start = np.zeros(len(parts) + 1, np.uint64)
+    np.cumsum([len(p) for p in parts], out=doc_start[1:])
+    if doc_start[-1] > _lib.TC_MAX_N:
+        raise ValueError("the documents have more than TC_MAX_N bytes")
+    text = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    return np.ascontiguousarray(text, dtype=np.uint8), doc_start.astype(np.uint32)
 
 
 def absent_word_bytes(text, left, pos, ln):
