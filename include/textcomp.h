@@ -575,6 +575,57 @@ int tc_esa_kmer_docs_dev(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint32_t mi
                          uint32_t *d_kmer_occ, uint32_t *d_kmer_df, uint32_t *d_kmer_row, uint64_t *nk);
 int tc_esa_kmer_doc_spectrum(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint64_t *hist, uint64_t *distinct);
 int tc_esa_kmer_doc_spectrum_dev(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint64_t *d_hist, uint64_t *distinct);
+/* ---- cross-document matches on the kept ESA: per position and per document (not part of the reference's surface) ----
+ * Which parts of each document also occur in another document, how long are those matches, and where is the other copy?  The
+ * handle is one of tc_esa_build_docs: the text of n bytes, doc_start[0 .. ndocs] and the first-byte rule above.  The document of
+ * position i is d(i).  A position j QUALIFIES for i under kind: TC_DOC_OTHER (0): d(j) != d(i); TC_DOC_EARLIER (1): d(j) < d(i).
+ * PER POSITION (tc_esa_doc_match): among the qualifying suffixes take the lexicographic predecessor a and the successor b of
+ * suffix i; either may be missing.  La and Lb are their common-prefix lengths with suffix i in the concatenated text, -1 where
+ * missing.  L = max(La, Lb); the partner is a if La >= Lb, else b.  If L <= 0: xl[i] = 0, src[i] = TC_ESA_NO_POS, xdoc[i] =
+ * TC_ESA_NO_DOC.  Otherwise src[i] = the partner's position and xdoc[i] = its document, and xl[i] = L, or with clamp != 0 it is
+ * min(L, doc_start[d(i) + 1] - i).  The clamp is on i's own side only; the partner's side follows the first-byte rule.  In row
+ * terms, r = isa[i]: a and b are the nearest qualifying rows >= 1 above and below r, La and Lb the range minima of lcp over
+ * (a, r] and (r, b]; row 0, the empty suffix, never qualifies.  With clamp = 0, for TC_DOC_OTHER xl[i] >= L iff
+ * tc_esa_doc_count of (i, L) at limit 2 answers 2; for TC_DOC_EARLIER iff the document list of (i, L) holds a document below
+ * d(i).  Each output has n entries and may be NULL; all NULL is TC_ERR_ARG.  xl is what tc_cover_spans_dev, tc_cover_mask_dev and
+ * tc_cover_dedup_dev take: with TC_DOC_OTHER they mask or remove what a document shares with the others, with TC_DOC_EARLIER the
+ * first copy of everything stays.
+ * PER DOCUMENT (tc_esa_doc_shared), always clamped: shared[d] is the number of bytes p of document d for which some i <= p in d
+ * has clamped xl[i] >= min_len and p < i + xl[i]; shared[d] over the size of d is the containment of d in the rest (or in the
+ * earlier part) of the collection.  longest[d] is the maximum clamped xl over d's positions, 0 for an empty document; it does not
+ * depend on min_len.  ndocs entries each; either may be NULL, both NULL is TC_ERR_ARG.
+ * ERRORS: TC_ERR_ARG before any device work for a null context or handle, a plain handle (tc_esa_ndocs 0), a kind other than the
+ * two, min_len = 0.  n = 0 is TC_OK with nothing touched for match, and zeros for shared.  One document gives all-zero xl, src =
+ * TC_ESA_NO_POS and zero shared for both kinds.  Two calls give identical output.  The handle is read-only: all scratch is the
+ * calling context's workspace, so two contexts may query one handle at once.
+ *   example 1: banana . bandana . ananas, doc_start = {0, 6, 13, 19}, TC_DOC_OTHER (the clamp changes nothing here):
+ *     xl = 3 5 4 3 2 1 3 2 1 0 3 2 1 5 4 3 2 1 0
+ *     src = 6 13 14 10 11 12 0 15 16 - 3 4 5 1 2 1 2 7 -
+ *     xdoc = 1 2 2 1 1 1 0 2 2 - 0 0 0 0 0 0 0 1 -
+ *     shared at min_len 1, 2, 3 alike = {6, 6, 5}, longest = {5, 3, 5}: only the d of bandana and the last s are private
+ *   example 2: the same collection, TC_DOC_EARLIER:
+ *     xl = 0 0 0 0 0 0 3 2 1 0 3 2 1 5 4 3 2 1 0
+ *     src = - - - - - - 0 1 2 - 3 4 5 1 2 1 2 7 -
+ *     shared = {0, 6, 5}, longest = {0, 3, 5}
+ *   example 3: ab . cab . abc, doc_start = {0, 2, 5, 8}, TC_DOC_OTHER: position 0 matches abc at 5 across its own end:
+ *     unclamped xl = 3 2 1 2 1 3 2 1
+ *     xl = 2 1 1 2 1 3 2 1
+ *     src = 5 6 7 5 6 0 1 2
+ *     xdoc = 2 2 2 2 2 0 0 1
+ *     shared at min_len 1 / 2 / 3 = {2, 3, 3} / {2, 2, 3} / {0, 0, 3}, longest = {2, 2, 3}; at min_len 2 the cover is 1 1 0 1 1 1 1
+ *     1: spans (0, 2) and (3, 5), and the dedup leaves c
+ *   example 4: the same collection, TC_DOC_EARLIER:
+ *     xl = 0 0 0 2 1 3 2 1
+ *     src = - - - 0 1 0 1 2
+ *     xdoc = - - - 0 0 0 0 1
+ *     at min_len 2 the cover is 0 0 0 1 1 1 1 1 and the dedup leaves abc: the first copy of everything stays */
+#define TC_DOC_OTHER 0
+#define TC_DOC_EARLIER 1
+#define TC_ESA_NO_POS 0xffffffffu
+int tc_esa_doc_match(tc_ctx *ctx, const tc_esa *esa, int kind, int clamp, uint32_t *xl, uint32_t *src, uint32_t *xdoc);
+int tc_esa_doc_match_dev(tc_ctx *ctx, const tc_esa *esa, int kind, int clamp, uint32_t *d_xl, uint32_t *d_src, uint32_t *d_xdoc);
+int tc_esa_doc_shared(tc_ctx *ctx, const tc_esa *esa, int kind, uint32_t min_len, uint64_t *shared, uint32_t *longest);
+int tc_esa_doc_shared_dev(tc_ctx *ctx, const tc_esa *esa, int kind, uint32_t min_len, uint64_t *d_shared, uint32_t *d_longest);
 /* ---- the k-mers of a text: list, abundance spectrum and all-k profile (not part of the reference's surface) ----
  * N = n + 1 rows; sa and lcp as tc_lcp_array defines them (row 0 is the empty suffix, the end of the text matches
  * nothing); lcp[0] counts as 0 whatever the array holds, and lcp[N] as 0.  For k >= 1 row q is a BOUNDARY iff lcp[q] < k;

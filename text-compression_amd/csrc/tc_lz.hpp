@@ -56,7 +56,7 @@ FM_MS_DEVICE u32 lz_scan_min(const u32 *lv, u32 cnt, u32 lo, u32 hi, u32 m) {
 // level and ceil(log_f N) levels on any text.  (No level above T.nlev is used: the top level is one group.)
 // USER: an instance per calling file (0: lz_lpf_kernel, 1: tm_row_kernel of tc_tm.hpp, 2: tr_cand_kernel of tc_tr.hpp,
 // 3: pal_centre_kernel of tc_pal.hpp, 4: sus_point_kernel of tc_sus.hpp, 5: cov_seed_kernel of tc_cov.hpp, 6: the three query
-// kernels of tc_esa.hpp).  The function is not inlined, so
+// kernels of tc_esa.hpp, 7: esx_match_kernel of tc_esa_xdoc.hpp).  The function is not inlined, so
 // what the compiler knows of its callers shapes it: shared with tm_row_kernel, the one instance cost lz_lpf_kernel two more
 // VGPRs (36 -> 38 in the resource listing); with an instance of its own, lz_lpf_kernel is compiled as it was.
 template <int USER = 0>

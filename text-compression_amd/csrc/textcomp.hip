@@ -19,6 +19,7 @@
 #include "tc_cov_host.hpp"
 #include "tc_esa_host.hpp"
 #include "tc_esa_docs_host.hpp"
+#include "tc_esa_xdoc_host.hpp"
 #include "tc_container_host.hpp"
 #include "tc_hostio_host.hpp"
 #include "tc_generate.hpp"
@@ -568,6 +569,31 @@ int tc_esa_kmer_doc_spectrum(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint64_
 int tc_esa_kmer_doc_spectrum_dev(tc_ctx *ctx, const tc_esa *esa, uint32_t k, uint64_t *d_hist, uint64_t *distinct) {
     TC_API_BEGIN(ctx)
     esa_kmer_doc_spectrum_entry(ctx, esa, k, d_hist, distinct, true);
+    TC_API_END(ctx)
+}
+
+// cross-document matches on the kept enhanced suffix array (no counterpart in the reference): tc_esa_xdoc_host.hpp
+int tc_esa_doc_match(tc_ctx *ctx, const tc_esa *esa, int kind, int clamp, uint32_t *xl, uint32_t *src, uint32_t *xdoc) {
+    TC_API_BEGIN(ctx)
+    esa_doc_match_entry(ctx, esa, kind, clamp, xl, src, xdoc, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_doc_match_dev(tc_ctx *ctx, const tc_esa *esa, int kind, int clamp, uint32_t *d_xl, uint32_t *d_src, uint32_t *d_xdoc) {
+    TC_API_BEGIN(ctx)
+    esa_doc_match_entry(ctx, esa, kind, clamp, d_xl, d_src, d_xdoc, true);
+    TC_API_END(ctx)
+}
+
+int tc_esa_doc_shared(tc_ctx *ctx, const tc_esa *esa, int kind, uint32_t min_len, uint64_t *shared, uint32_t *longest) {
+    TC_API_BEGIN(ctx)
+    esa_doc_shared_entry(ctx, esa, kind, min_len, shared, longest, false);
+    TC_API_END(ctx)
+}
+
+int tc_esa_doc_shared_dev(tc_ctx *ctx, const tc_esa *esa, int kind, uint32_t min_len, uint64_t *d_shared, uint32_t *d_longest) {
+    TC_API_BEGIN(ctx)
+    esa_doc_shared_entry(ctx, esa, kind, min_len, d_shared, d_longest, true);
     TC_API_END(ctx)
 }
 

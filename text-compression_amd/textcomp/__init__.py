@@ -53,6 +53,8 @@ DNA_COMPLEMENT = _dna_complement()
 
 # the kinds of the repeat cover: every occurrence of repeated content, or every occurrence but the leftmost
 COVER_ALL, COVER_LATER = _lib.TC_COVER_ALL, _lib.TC_COVER_LATER
+DOC_OTHER, DOC_EARLIER = _lib.TC_DOC_OTHER, _lib.TC_DOC_EARLIER
+ESA_NO_POS = _lib.TC_ESA_NO_POS
 
 
 def _soft_mask():
@@ -2082,6 +2084,82 @@ class ESAHandle:
         torch.cuda.synchronize()
         ctx._check(ctx.lib.tc_esa_kmer_doc_spectrum_dev(ctx.handle, self._h, int(k), C.c_void_p(d_hist.data_ptr()), C.byref(distinct)))
         return d_hist, int(distinct.value)
+
+    # ---- cross-document matches: which parts of each document also occur in another (or an earlier) one, and where
+    def doc_match(self, kind=DOC_OTHER, clamp=True, src=False, doc=False, ctx=None):
+        """xl[i] = the length of the longest match of position i that starts in another document (DOC_OTHER) or in an earlier one
+        (DOC_EARLIER), clamped to the end of i's own document unless clamp=False -> uint32 array of n entries, or (xl[, src][,
+        doc]) with the partner's position (ESA_NO_POS: none) and document (TC_ESA_NO_DOC: none): tc_esa_doc_match"""
+        ctx = ctx or self._ctx
+        out = [np.zeros(self.n, np.uint32) for _ in range(1 + bool(src) + bool(doc))]
+        ps = _ptr(out[1]) if src else None
+        pd = _ptr(out[-1]) if doc else None
+        ctx._check(ctx.lib.tc_esa_doc_match(ctx.handle, self._h, int(kind), int(bool(clamp)), _ptr(out[0]), ps, pd))
+        return tuple(out) if src or doc else out[0]
+
+    def doc_match_dev(self, kind=DOC_OTHER, clamp=True, src=False, doc=False, ctx=None):
+        """the same -> int32 tensor(s) on the device holding the 32-bit entries: tc_esa_doc_match_dev"""
+        import torch
+        ctx = ctx or self._ctx
+        out = [torch.zeros(self.n, dtype=torch.int32, device="cuda:%d" % ctx.device) for _ in range(1 + bool(src) + bool(doc))]
+        po = [C.c_void_p(o.data_ptr()) if self.n else None for o in out]
+        torch.cuda.synchronize()
+        ctx._check(ctx.lib.tc_esa_doc_match_dev(ctx.handle, self._h, int(kind), int(bool(clamp)), po[0], po[1] if src else None,
+                                                po[-1] if doc else None))
+        return tuple(out) if src or doc else out[0]
+
+    def doc_shared(self, min_len=1, kind=DOC_OTHER, ctx=None):
+        """-> (shared, longest): per document the bytes that lie in a clamped match of at least min_len bytes (a uint64 array) and the
+        longest clamped match (a uint32 array): tc_esa_doc_shared"""
+        ctx = ctx or self._ctx
+        shared = np.zeros(self.ndocs, np.uint64)
+        longest = np.zeros(self.ndocs, np.uint32)
+        ctx._check(ctx.lib.tc_esa_doc_shared(ctx.handle, self._h, int(kind), int(min_len), _ptr(shared), _ptr(longest)))
+        return shared, longest
+
+    def doc_shared_dev(self, min_len=1, kind=DOC_OTHER, ctx=None):
+        """the same -> (an int64 tensor, an int32 tensor) on the device: tc_esa_doc_shared_dev"""
+        import torch
+        ctx = ctx or self._ctx
+        shared = torch.zeros(self.ndocs, dtype=torch.int64, device="cuda:%d" % ctx.device)
+        longest = torch.zeros(self.ndocs, dtype=torch.int32, device="cuda:%d" % ctx.device)
+        torch.cuda.synchronize()
+        ctx._check(ctx.lib.tc_esa_doc_shared_dev(ctx.handle, self._h, int(kind), int(min_len), C.c_void_p(shared.data_ptr()) if self.ndocs else None,
+                                                 C.c_void_p(longest.data_ptr()) if self.ndocs else None))
+        return shared, longest
+
+    def shared_spans_dev(self, min_len, kind=DOC_OTHER, cap=None, ctx=None):
+        """-> (start, len, covered): the maximal stretches of the text that clamped matches of at least min_len bytes cover:
+        doc_match_dev(clamp=True), then Context.cover_spans_dev"""
+        ctx = ctx or self._ctx
+        return ctx.cover_spans_dev(self.doc_match_dev(kind=kind, clamp=True, ctx=ctx), min_len, cap=cap)
+
+    def shared_mask_dev(self, min_len, kind=DOC_OTHER, map=None, ctx=None):
+        """-> (out, covered): the text with what each document shares with the others (DOC_EARLIER: with earlier ones) masked:
+        doc_match_dev(clamp=True), then Context.cover_mask_dev on the handle's text"""
+        ctx = ctx or self._ctx
+        return ctx.cover_mask_dev(self.doc_match_dev(kind=kind, clamp=True, ctx=ctx), self.read_dev("text", ctx=ctx), min_len, map=map)
+
+    def shared_dedup_dev(self, min_len, kind=DOC_OTHER, cap=None, ctx=None):
+        """-> (out, covered): the text without the covered bytes; with DOC_EARLIER the first copy of everything stays:
+        doc_match_dev(clamp=True), then Context.cover_dedup_dev on the handle's text"""
+        ctx = ctx or self._ctx
+        return ctx.cover_dedup_dev(self.doc_match_dev(kind=kind, clamp=True, ctx=ctx), self.read_dev("text", ctx=ctx), min_len, cap=cap)
+
+    def shared_spans(self, min_len, kind=DOC_OTHER, cap=None, ctx=None):
+        """shared_spans_dev -> (start, len, covered) with uint32 host arrays"""
+        s, l, cov = self.shared_spans_dev(min_len, kind=kind, cap=cap, ctx=ctx)
+        return s.cpu().numpy().view(np.uint32), l.cpu().numpy().view(np.uint32), cov
+
+    def shared_mask(self, min_len, kind=DOC_OTHER, map=None, ctx=None):
+        """shared_mask_dev -> (out, covered) with a uint8 host array"""
+        out, cov = self.shared_mask_dev(min_len, kind=kind, map=map, ctx=ctx)
+        return out.cpu().numpy(), cov
+
+    def shared_dedup(self, min_len, kind=DOC_OTHER, cap=None, ctx=None):
+        """shared_dedup_dev -> (out, covered) with a uint8 host array"""
+        out, cov = self.shared_dedup_dev(min_len, kind=kind, cap=cap, ctx=ctx)
+        return out.cpu().numpy(), cov
 
     # ---- further analyses on the arrays the handle keeps: the sort is paid once
     def arrays(self):

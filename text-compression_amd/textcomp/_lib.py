@@ -25,6 +25,8 @@ TC_ESA_TEXT, TC_ESA_SA, TC_ESA_ISA, TC_ESA_LCP = 1, 2, 3, 4   # `what` of tc_esa
 TC_ESA_DA, TC_ESA_PV, TC_ESA_DOC_START = 5, 6, 7              # on a handle with documents
 TC_ESA_MAX_DOCS = 65535
 TC_ESA_NO_DOC = 0xffffffff
+TC_DOC_OTHER, TC_DOC_EARLIER = 0, 1
+TC_ESA_NO_POS = 0xffffffff
 TC_LCP_SHORT_CAP = 256   # csrc/tc_lcp.hpp: comparisons of the LCP array longer than this leave the one-lane kernel
 
 ERR_NAMES = {-1: "TC_ERR_ARG", -2: "TC_ERR_CAPACITY", -3: "TC_ERR_MALFORMED", -4: "TC_ERR_HIP",
@@ -141,6 +143,10 @@ SYMBOLS = [
     ("tc_esa_kmer_docs_dev", _INT, [_P, _P, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_esa_kmer_doc_spectrum", _INT, [_P, _P, _U32, _P, _PU64]),
     ("tc_esa_kmer_doc_spectrum_dev", _INT, [_P, _P, _U32, _P, _PU64]),
+    ("tc_esa_doc_match", _INT, [_P, _P, _INT, _INT, _P, _P, _P]),
+    ("tc_esa_doc_match_dev", _INT, [_P, _P, _INT, _INT, _P, _P, _P]),
+    ("tc_esa_doc_shared", _INT, [_P, _P, _INT, _U32, _P, _P]),
+    ("tc_esa_doc_shared_dev", _INT, [_P, _P, _INT, _U32, _P, _P]),
     ("tc_kmers", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_dev", _INT, [_P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _P, _PU64]),
     ("tc_kmers_esa_dev", _INT, [_P, _P, _P, _U64, _U32, _U32, _U32, _P, _P, _P, _PU64]),
