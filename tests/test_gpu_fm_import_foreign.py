@@ -7,7 +7,7 @@ at the query, or by TC_OK with the answer the contents define, and every kernel 
 defines that answer from the bytes of the string alone, so every comparison here is exact: the same numbers, or TcMalformed
 where the model says MALFORMED.  What a device test cannot see -- a read outside a part -- is seen on the CPU: by the
 model's accessors (tests/test_fm_wire_ref.py) and, for the loop of fm_count_kernel, by host/check/fm_count_kernels.cpp under
-a sanitizer (tests/test_fm_count_host_check.py).
+a sanitizer (tests/test_host_checks.py).
 
 The base indexes (tests/fm_foreign_cases.py: four texts, four builds each) are built by the library and compared part for
 part with the model's builder first; the damaged strings are made from them.  Every damaged string is imported on a second

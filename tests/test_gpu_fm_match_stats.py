@@ -4,7 +4,7 @@ smallest shapes at which the kernel can go wrong (rank-line and tree-group bound
 does not hold, texts whose shrinks cross many groups of the min tree at the default fan-out and at fan-out 4, a divergent
 batch of more than one workgroup), through the host and the _dev entry points, on a full index and on sampled ones, with
 and without text samples.  Which levels of the tree the searches reach cannot be seen from here: host/check/fm_ms_kernels.cpp
-(tests/test_fm_match_stats_host_check.py) asserts that."""
+(tests/test_host_checks.py) asserts that."""
 import ctypes as C
 
 import numpy as np

@@ -5,7 +5,7 @@ smallest shapes at which the kernels can go wrong: the group boundaries of the m
 fan-out 4, texts whose nearest smaller row is far and whose range minima span many groups, tile boundaries of the
 phrase-start steps at a tile of 64 positions (tc_dbg_lz_set_tile) and one run at the library's tile, phrase lists no greedy
 parser writes, and the capacity / sizes-only / error protocol.  Which tree levels the range minimum reaches cannot be seen
-from here: host/check/lz_kernels.cpp (tests/test_lz_host_check.py) asserts that."""
+from here: host/check/lz_kernels.cpp (tests/test_host_checks.py) asserts that."""
 import ctypes as C
 import os
 import re

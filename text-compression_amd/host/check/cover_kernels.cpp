@@ -3,44 +3,21 @@
 //       text-compression_amd/host/check/cover_kernels.cpp -o cover_kernels && ./cover_kernels
 // TC_FM_MS_HOST_CHECK compiles cov_seed_kernel (both instances), cov_reach and cov_lane_bits, the range minimum of
 // csrc/tc_lz.hpp and the row searches of csrc/tc_fm_ms.hpp as plain C++, as host/check/sus_kernels.cpp does for the unique
-// substrings: the HIP keywords defined away, the lanes run one after another.  Everything around them is built naively here --
-// suffixes sorted directly, the LCP array by comparing neighbours, the two min trees by fm_lmin_kernel level over level at
-// fan-outs 4 and 64, the tiles' maxima, the spine and the scan inside a tile by running loops in the kernels' own geometry
+// substrings: the HIP keywords defined away, the lanes run one after another.  Everything around them is built naively -- by
+// check_common.hpp and check_esa.hpp the suffixes sorted directly, the LCP array by comparing neighbours, the two min trees by
+// fm_lmin_kernel level over level at fan-outs 4 and 64; here the tiles' maxima, the spine and the scan inside a tile by running loops in the kernels' own geometry
 // (COV_TILE positions per tile, COV_ITEMS in a row per lane) -- in heap blocks of exactly the entries the library's arrays hold,
 // so a read or a store one element outside any of them stops the run.  Every seed is compared with a dictionary of the L-mers,
 // every cover, span, mask and dedup with a difference array over the seeds; on the texts of at most 24 bytes the cover is in turn
 // held against every substring of at least L bytes.  Texts: unary, periodic (2, 3, 7), Fibonacci, random over 1, 2, 4 and 200
 // letters, a text followed by its copy, one letter and then 2600 times another; and the general form on arrays no text produces: all zero, one long entry, entries of
 // 0xffffffff, random lengths.  The kernels around the lanes need a workgroup: they are checked on the device only.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <map>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_cov.hpp"
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-
-typedef std::vector<u8> Bytes;
 struct Span {
     u32 s, len;
     bool operator==(const Span &o) const { return s == o.s && len == o.len; }
@@ -175,39 +152,16 @@ struct Esa {
     std::unique_ptr<u32[]> sa, lcp;
 };
 static Esa esa_of(const Bytes &text) {
-    const u32 n = (u32)text.size(), N = n + 1;
-    Esa e{block<u32>(N), block<u32>(N)};
-    for (u32 i = 0; i < N; i++) e.sa[i] = i;
-    std::sort(e.sa.get(), e.sa.get() + N, [&](u32 x, u32 y) {       // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    for (u32 j = 0; j < N; j++) {
-        u32 l = 0;
-        if (j) {
-            const u32 a = e.sa[j - 1], b = e.sa[j];
-            while (a + l < n && b + l < n && text[a + l] == text[b + l]) l++;
-        }
-        e.lcp[j] = l;
-    }
-    return e;
+    const std::vector<u32> sa = sort_suffixes(text);
+    return Esa{block_of(sa), block_of(lcp_of(text, sa))};
 }
 
 static void check_text(const Bytes &text, u32 lf) {
     const u32 n = (u32)text.size(), N = n + 1;
     const Esa e = esa_of(text);
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1], words;
-    const u32 nlev = fm_ms_tree_shape(N, lf, off, cnt, &words);
-    auto lcp_min = block<u32>(words), sa_min = block<u32>(words);
-    for (int which = 0; which < 2; which++) {
-        const u32 *src = which ? e.sa.get() : e.lcp.get();
-        u32 *lmin = which ? sa_min.get() : lcp_min.get();
-        for (u32 k = 1; k <= nlev; k++) {
-            u32 *dst = lmin + off[k];
-            launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], lf, dst, cnt[k]); });
-            src = dst;
-        }
-    }
+    const MinTree lcp_tree = min_tree_of(e.lcp.get(), N, lf), sa_tree = min_tree_of(e.sa.get(), N, lf);
+    const u32 nlev = lcp_tree.nlev;
+    const u32 *lcp_min = lcp_tree.lmin.get(), *sa_min = sa_tree.lmin.get();
     memset(lz_climbed, 0, sizeof lz_climbed);
     memset(fm_ms_climbed, 0, sizeof fm_ms_climbed);
     const u32 params[][2] = {{1, 2}, {1, 4}, {2, 2}, {2, 3}, {3, 2}, {3, 3}, {5, 5}, {20, 2}, {n, 2}, {n + 1, 2}, {n > 1 ? n - 1 : 1, 2}, {1, n + 2}};
@@ -219,11 +173,11 @@ static void check_text(const Bytes &text, u32 lf) {
             for (u32 i = 0; i < n; i++) len[i] = 0;
             const u64 by_rows = cov_seen[4];
             if (later) {
-                launch(N, [&] { cov_seed_kernel<true>(e.sa.get(), e.lcp.get(), sa_min.get(), lcp_min.get(), N, lf, L, q, len.get()); });
+                launch(N, [&] { cov_seed_kernel<true>(e.sa.get(), e.lcp.get(), sa_min, lcp_min, N, lf, L, q, len.get()); });
             } else if (q == 2) {    // (the library builds no tree for this call)
                 launch(N, [&] { cov_seed_kernel<false>(e.sa.get(), e.lcp.get(), nullptr, nullptr, N, lf, L, q, len.get()); });
             } else {
-                launch(N, [&] { cov_seed_kernel<false>(e.sa.get(), e.lcp.get(), nullptr, lcp_min.get(), N, lf, L, q, len.get()); });
+                launch(N, [&] { cov_seed_kernel<false>(e.sa.get(), e.lcp.get(), nullptr, lcp_min, N, lf, L, q, len.get()); });
             }
             const std::vector<u32> want = brute_seeds(text, L, q, later);
             std::vector<u32> got, copy(len.get(), len.get() + n);
@@ -263,26 +217,6 @@ static void check_array(const std::vector<u32> &v, u32 L) {
     std::copy(v.begin(), v.end(), len.get());
     check_cover(len.get(), v, n, L, nullptr);
     g_arrays++;
-}
-
-static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
-    Bytes t(n);
-    for (u8 &b : t) b = sigma > 4 ? (u8)(rng() % sigma + 1) : (u8)("ACGT"[rng() % sigma]);
-    return t;
-}
-static Bytes periodic(u32 n, u32 p) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string a = "A", b = "AB";
-    while (b.size() < n) {
-        const std::string c = b + a;
-        a = b;
-        b = c;
-    }
-    return Bytes(b.begin(), b.begin() + n);
 }
 
 int main() {

@@ -4,7 +4,7 @@
 //       text-compression_amd/host/check/esa_docs_kernels.cpp -o esa_docs_kernels && ./esa_docs_kernels
 // TC_FM_MS_HOST_CHECK compiles esd_doc_of and both instances of esd_doc_kernel, with the row searches of csrc/tc_fm_ms.hpp, as plain
 // C++, as host/check/esa_kernels.cpp does for the queries of tc_esa.hpp: the HIP keywords defined away, the lanes run one after
-// another.  Everything around them is built naively here -- suffixes sorted directly, lcp by comparing neighbours, da by esd_doc_of
+// another.  Everything around them is built naively -- suffixes sorted directly, lcp by comparing neighbours, da by esd_doc_of
 // against a loop, pv by a walk back over the rows, the min trees of lcp and pv by fm_lmin_kernel at fan-outs 4 and 64 -- in heap
 // blocks of exactly the bytes the library's handle allocates, and every query and result array holds exactly the entries the call
 // defines, so a read or a store one element outside any of them stops the run.  Every answer is compared with loops over the bytes.
@@ -14,43 +14,11 @@
 // that leave the text, which must raise the flag and read nothing: their batch runs on null arrays.  The document frequency of
 // the k-mers: the tiles of kmd_flag_kernel and kmd_pass_kernel, lane after lane, at k = 1, 2, 3, 8, 21 on every collection above and
 // on texts of one, two and three tiles of rows, against the documents of every distinct k-mer.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_esa_docs.hpp"
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block_bytes(size_t bytes) {
-    EXPECT(bytes % sizeof(T) == 0);
-    return std::unique_ptr<T[]>(new T[bytes / sizeof(T) ? bytes / sizeof(T) : 1]);
-}
-template <class T>
-static std::unique_ptr<T[]> block_of(const std::vector<T> &v) {
-    std::unique_ptr<T[]> p(new T[v.size() ? v.size() : 1]);
-    std::copy(v.begin(), v.end(), p.get());
-    return p;
-}
-
-typedef std::vector<u8> Bytes;
 struct Pair { u32 a, b; };
 
 static u64 g_texts = 0, g_queries = 0, g_refused = 0, g_garbage = 0;
@@ -64,15 +32,6 @@ struct Esa {
     std::vector<u32> ds;
     std::unique_ptr<u32[]> doc_start, sa, isa, lcp, da, pv, lcp_min, pv_min;
 };
-static void build_tree(const Esa &e, const u32 *src, u32 *lmin) {
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1], words;
-    const u32 nlev = fm_ms_tree_shape(e.N, e.lf, off, cnt, &words);
-    for (u32 k = 1; k <= nlev; k++) {
-        u32 *dst = lmin + off[k];
-        launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], e.lf, dst, cnt[k]); });
-        src = dst;
-    }
-}
 static Esa esa_of(const Bytes &t, const std::vector<u32> &ds, u32 lf) {
     Esa e;
     e.n = (u32)t.size();
@@ -80,7 +39,7 @@ static Esa esa_of(const Bytes &t, const std::vector<u32> &ds, u32 lf) {
     e.lf = lf;
     e.ds = ds;
     e.ndocs = (u32)ds.size() - 1;
-    const u32 n = e.n, N = e.N;
+    const u32 N = e.N;
     const size_t rows = ((size_t)N * 4 + 15) & ~(size_t)15;
     e.doc_start = block_bytes<u32>((ds.size() * 4 + 15) & ~(size_t)15);
     std::copy(ds.begin(), ds.end(), e.doc_start.get());
@@ -90,19 +49,11 @@ static Esa esa_of(const Bytes &t, const std::vector<u32> &ds, u32 lf) {
     e.da = block_bytes<u32>(rows);
     e.pv = block_bytes<u32>(rows);
     for (size_t i = 0; i < rows / 4; i++) e.sa[i] = e.isa[i] = e.lcp[i] = e.da[i] = e.pv[i] = 0xdeadbeefu;
-    for (u32 i = 0; i < N; i++) e.sa[i] = i;
-    std::sort(e.sa.get(), e.sa.get() + N, [&](u32 x, u32 y) {       // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(t.data() + x, t.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
+    const std::vector<u32> sa = sort_suffixes(t), lcp = lcp_of(t, sa), isa = inverse_of(sa);
+    std::copy(sa.begin(), sa.end(), e.sa.get());
+    std::copy(lcp.begin(), lcp.end(), e.lcp.get());
+    std::copy(isa.begin(), isa.end(), e.isa.get());
     for (u32 j = 0; j < N; j++) {
-        u32 l = 0;
-        if (j) {
-            const u32 a = e.sa[j - 1], b = e.sa[j];
-            while (a + l < n && b + l < n && t[a + l] == t[b + l]) l++;
-        }
-        e.lcp[j] = l;
-        e.isa[e.sa[j]] = j;
         // the document by the lane body of the build's first kernel, against a loop over the boundaries
         u32 want = ESD_NO_DOC;
         for (u32 d = 0; d < e.ndocs; d++)
@@ -118,12 +69,11 @@ static Esa esa_of(const Bytes &t, const std::vector<u32> &ds, u32 lf) {
         e.pv[j] = v;
     }
     EXPECT(e.da[0] == ESD_NO_DOC && e.pv[0] == 0xffffffffu);
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1];
-    e.nlev = fm_ms_tree_shape(N, lf, off, cnt, &e.words);
-    e.lcp_min = block_bytes<u32>((size_t)e.words * 4);
-    e.pv_min = block_bytes<u32>((size_t)e.words * 4);
-    build_tree(e, e.lcp.get(), e.lcp_min.get());
-    build_tree(e, e.pv.get(), e.pv_min.get());
+    MinTree lcp_tree = min_tree_of(e.lcp.get(), N, lf), pv_tree = min_tree_of(e.pv.get(), N, lf);
+    e.nlev = lcp_tree.nlev;
+    e.words = lcp_tree.words;
+    e.lcp_min = std::move(lcp_tree.lmin);
+    e.pv_min = std::move(pv_tree.lmin);
     return e;
 }
 
@@ -203,15 +153,13 @@ static void run_docs(const Esa &e, const std::vector<Pair> &q, const std::vector
 static void run_garbage(const Esa &e, const std::vector<Pair> &q, std::mt19937 &rng, bool garbage_tree) {
     const size_t rows = ((size_t)e.N * 4 + 15) & ~(size_t)15;
     auto pv = block_bytes<u32>(rows);
-    auto pv_min = block_bytes<u32>((size_t)e.words * 4);
     for (u32 i = 0; i < e.N; i++) {
         const u32 kind = rng() % 4;
         pv[i] = kind == 0 ? 0u : kind == 1 ? (u32)(rng() % (e.N + 2)) : kind == 2 ? (u32)rng() : 1u;
     }
+    auto pv_min = garbage_tree ? block<u32>(e.words) : min_tree_of(pv.get(), e.N, e.lf).lmin;
     if (garbage_tree)
         for (u32 i = 0; i < e.words; i++) pv_min[i] = rng() % 3 ? (u32)(rng() % (e.N + 1)) : (u32)rng();
-    else
-        build_tree(e, pv.get(), pv_min.get());
     const u64 nq = q.size();
     std::vector<u32> vs, vl;
     for (const Pair &p : q) { vs.push_back(p.a); vl.push_back(p.b); }
@@ -402,25 +350,6 @@ static void check_kmer_df(const Bytes &t, const Esa &e, u32 k) {
     g_kmers += got.size();
 }
 
-static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
-    Bytes t(n);
-    for (u8 &b : t) b = (u8)("ACGT"[rng() % sigma]);
-    return t;
-}
-static Bytes periodic(u32 n, u32 p) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string a = "A", b = "AB";
-    while (b.size() < n) {
-        const std::string c = b + a;
-        a = b;
-        b = c;
-    }
-    return Bytes(b.begin(), b.begin() + n);
-}
 static std::vector<u32> even_docs(u32 n, u32 ndocs) {
     std::vector<u32> ds(ndocs + 1);
     for (u32 d = 0; d <= ndocs; d++) ds[d] = (u32)((u64)d * n / ndocs);

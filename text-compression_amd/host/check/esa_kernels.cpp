@@ -4,53 +4,18 @@
 //       text-compression_amd/host/check/esa_kernels.cpp -o esa_kernels && ./esa_kernels
 // TC_FM_MS_HOST_CHECK compiles esa_lce_kernel, esa_find_kernel and esa_compare_kernel, the range minimum of csrc/tc_lz.hpp and
 // the row searches of csrc/tc_fm_ms.hpp as plain C++, as host/check/cover_kernels.cpp does for the repeat cover: the HIP keywords
-// defined away, the lanes run one after another.  Everything around them is built naively here -- suffixes sorted directly, the
-// LCP array by comparing neighbours, the inverse by a scatter, the two min trees by fm_lmin_kernel level over level at fan-outs 4
-// and 64 -- in heap blocks of exactly the bytes the library's handle allocates (the text with its 16 bytes of padding, the three
+// defined away, the lanes run one after another.  Everything around them is built naively by check_common.hpp and check_esa.hpp --
+// suffixes sorted directly, the LCP array by comparing neighbours, the inverse by a scatter, the two min trees by fm_lmin_kernel
+// level over level at fan-outs 4 and 64 -- and copied here into heap blocks of exactly the bytes the library's handle allocates (the text with its 16 bytes of padding, the three
 // row arrays rounded up to 16 bytes, the trees' words), and every query and result array holds exactly nq entries, so a read or a
 // store one element outside any of them stops the run.  Every answer is compared with loops over the bytes.  Texts: unary,
 // periodic (2, 3, 7), Fibonacci, random over 2, 4 and 200 letters, a text followed by its copy, one letter and then 2600 times
 // another.  Queries: all pairs and all substrings on the texts of at most 40 bytes; on the longer ones sampled pairs and the
 // adversarial ones -- (i, i + period), (i, n), (n, n), (i, i), positions 0, n - 1 and n, len = 0 and len = n, substrings that
 // occur once -- and queries that leave the text, which must raise the flag and touch nothing outside the blocks.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
-
 #define TC_FM_MS_HOST_CHECK
 #include "tc_esa.hpp"
-
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-// a heap block of exactly `bytes` bytes
-template <class T>
-static std::unique_ptr<T[]> block_bytes(size_t bytes) {
-    EXPECT(bytes % sizeof(T) == 0);
-    return std::unique_ptr<T[]>(new T[bytes / sizeof(T) ? bytes / sizeof(T) : 1]);
-}
-template <class T>
-static std::unique_ptr<T[]> block_of(const std::vector<T> &v) {
-    std::unique_ptr<T[]> p(new T[v.size() ? v.size() : 1]);
-    std::copy(v.begin(), v.end(), p.get());
-    return p;
-}
-
-typedef std::vector<u8> Bytes;
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
 static u64 g_texts = 0, g_lce = 0, g_find = 0, g_cmp = 0, g_refused = 0;
 static u64 g_down[FM_MS_MAXLEV + 1] = {}, g_up[FM_MS_MAXLEV + 1] = {}, g_min[FM_MS_MAXLEV + 1] = {};
@@ -77,33 +42,15 @@ static Esa esa_of(const Bytes &t, u32 lf) {
     e.isa = block_bytes<u32>(rows);
     e.lcp = block_bytes<u32>(rows);
     for (size_t i = 0; i < rows / 4; i++) e.sa[i] = e.isa[i] = e.lcp[i] = 0xdeadbeefu;   // (what lies behind row N - 1 is never an answer)
-    for (u32 i = 0; i < N; i++) e.sa[i] = i;
-    std::sort(e.sa.get(), e.sa.get() + N, [&](u32 x, u32 y) {       // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(t.data() + x, t.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    for (u32 j = 0; j < N; j++) {
-        u32 l = 0;
-        if (j) {
-            const u32 a = e.sa[j - 1], b = e.sa[j];
-            while (a + l < n && b + l < n && t[a + l] == t[b + l]) l++;
-        }
-        e.lcp[j] = l;
-        e.isa[e.sa[j]] = j;
-    }
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1];
-    e.nlev = fm_ms_tree_shape(N, lf, off, cnt, &e.words);
-    e.lcp_min = block_bytes<u32>((size_t)e.words * 4);
-    e.sa_min = block_bytes<u32>((size_t)e.words * 4);
-    for (int which = 0; which < 2; which++) {
-        const u32 *src = which ? e.sa.get() : e.lcp.get();
-        u32 *lmin = which ? e.sa_min.get() : e.lcp_min.get();
-        for (u32 k = 1; k <= e.nlev; k++) {
-            u32 *dst = lmin + off[k];
-            launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], lf, dst, cnt[k]); });
-            src = dst;
-        }
-    }
+    const std::vector<u32> sa = sort_suffixes(t), lcp = lcp_of(t, sa), isa = inverse_of(sa);
+    std::copy(sa.begin(), sa.end(), e.sa.get());
+    std::copy(lcp.begin(), lcp.end(), e.lcp.get());
+    std::copy(isa.begin(), isa.end(), e.isa.get());
+    MinTree lcp_tree = min_tree_of(e.lcp.get(), N, lf), sa_tree = min_tree_of(e.sa.get(), N, lf);
+    e.nlev = lcp_tree.nlev;
+    e.words = lcp_tree.words;
+    e.lcp_min = std::move(lcp_tree.lmin);
+    e.sa_min = std::move(sa_tree.lmin);
     return e;
 }
 
@@ -316,26 +263,6 @@ static void check_text(const Bytes &t, u32 lf, u32 period, std::mt19937 &rng) {
         g_maxlev4 = std::max(g_maxlev4, e.nlev);
     }
     g_texts++;
-}
-
-static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
-    Bytes t(n);
-    for (u8 &b : t) b = sigma > 4 ? (u8)(rng() % sigma + 1) : (u8)("ACGT"[rng() % sigma]);
-    return t;
-}
-static Bytes periodic(u32 n, u32 p) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string a = "A", b = "AB";
-    while (b.size() < n) {
-        const std::string c = b + a;
-        a = b;
-        b = c;
-    }
-    return Bytes(b.begin(), b.begin() + n);
 }
 
 int main() {

@@ -12,37 +12,11 @@
 // device test sees: every level of a five-level tree reached by both da searches and by the range minima, the "no qualifying row"
 // outcome on each side and on both, a run longer than two tiles, a run head in an earlier tile, the clamp fired, empty documents
 // first, last and adjacent, and a da and trees of arbitrary contents that keep every access in bounds.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_esa_xdoc.hpp"
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block(size_t count, T fill) {
-    std::unique_ptr<T[]> p(new T[count ? count : 1]);
-    std::fill(p.get(), p.get() + count, fill);
-    return p;
-}
-
-typedef std::vector<u8> Bytes;
 static u64 g_texts = 0, g_rows = 0, g_garbage = 0;
 static bool g_long_run = false, g_far_head = false, g_empty_first = false, g_empty_last = false, g_empty_adjacent = false;
 static u64 g_da_up[2][FM_MS_MAXLEV + 1] = {}, g_rmq_up[FM_MS_MAXLEV + 1] = {};
@@ -53,15 +27,6 @@ struct Esa {
     std::vector<u32> ds;
     std::unique_ptr<u32[]> doc_start, sa, lcp, da, lcp_min, da_min;
 };
-static void build_tree(const Esa &e, const u32 *src, u32 *lmin) {
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1], words;
-    const u32 nlev = fm_ms_tree_shape(e.N, e.lf, off, cnt, &words);
-    for (u32 k = 1; k <= nlev; k++) {
-        u32 *dst = lmin + off[k];
-        launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], e.lf, dst, cnt[k]); });
-        src = dst;
-    }
-}
 static u32 doc_of(const std::vector<u32> &ds, u32 p) {
     for (u32 d = 0; d + 1 < ds.size(); d++)
         if (ds[d] <= p && p < ds[d + 1]) return d;
@@ -74,33 +39,20 @@ static Esa esa_of(const Bytes &t, const std::vector<u32> &ds, u32 lf) {
     e.lf = lf;
     e.ds = ds;
     e.ndocs = (u32)ds.size() - 1;
-    const u32 n = e.n, N = e.N;
+    const u32 N = e.N;
     e.doc_start = block<u32>(ds.size(), 0);
     std::copy(ds.begin(), ds.end(), e.doc_start.get());
     // (the library rounds a row array up to 16 bytes: the 16-byte loads of the searches stay inside; fm_ms_load4 masks here)
-    e.sa = block<u32>(N, 0);
-    e.lcp = block<u32>(N, 0);
+    const std::vector<u32> sa = sort_suffixes(t);
+    e.sa = block_of(sa);
+    e.lcp = block_of(lcp_of(t, sa));
     e.da = block<u32>(N, 0);
-    for (u32 i = 0; i < N; i++) e.sa[i] = i;
-    std::sort(e.sa.get(), e.sa.get() + N, [&](u32 x, u32 y) {       // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(t.data() + x, t.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    for (u32 j = 0; j < N; j++) {
-        u32 l = 0;
-        if (j) {
-            const u32 a = e.sa[j - 1], b = e.sa[j];
-            while (a + l < n && b + l < n && t[a + l] == t[b + l]) l++;
-        }
-        e.lcp[j] = l;
-        e.da[j] = doc_of(ds, e.sa[j]);
-    }
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1];
-    e.nlev = fm_ms_tree_shape(N, lf, off, cnt, &e.words);
-    e.lcp_min = block<u32>(e.words, 0);
-    e.da_min = block<u32>(e.words, 0);
-    build_tree(e, e.lcp.get(), e.lcp_min.get());
-    build_tree(e, e.da.get(), e.da_min.get());
+    for (u32 j = 0; j < N; j++) e.da[j] = doc_of(ds, e.sa[j]);
+    MinTree lcp_tree = min_tree_of(e.lcp.get(), N, lf), da_tree = min_tree_of(e.da.get(), N, lf);
+    e.nlev = lcp_tree.nlev;
+    e.words = lcp_tree.words;
+    e.lcp_min = std::move(lcp_tree.lmin);
+    e.da_min = std::move(da_tree.lmin);
     return e;
 }
 
@@ -337,18 +289,6 @@ static void check_garbage(u32 n, u32 lf, std::mt19937 &rng) {
     }
 }
 
-static Bytes fibonacci(u32 n) {
-    Bytes a = {'a'}, b = {'a', 'b'};
-    while (b.size() < n) {
-        Bytes c = b;
-        c.insert(c.end(), a.begin(), a.end());
-        a = b;
-        b = c;
-    }
-    b.resize(n);
-    return b;
-}
-
 int main() {
     std::mt19937 rng(0xE5C);
     u32 none[2][3] = {};
@@ -372,7 +312,7 @@ int main() {
                 r4[i] = (u8)('a' + rng() % 4);
                 per[i] = (u8)"abcabca"[i % 7];
             }
-            texts.push_back(r2); texts.push_back(r4); texts.push_back(per); texts.push_back(un); texts.push_back(fibonacci(n));
+            texts.push_back(r2); texts.push_back(r4); texts.push_back(per); texts.push_back(un); texts.push_back(fibonacci(n, 'a', 'b'));
         }
         for (const Bytes &t : texts) {
             const u32 n = (u32)t.size();

@@ -2,7 +2,7 @@
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I text-compression_amd/csrc
 //       text-compression_amd/host/check/fm_count_kernels.cpp -o fm_count_kernels && ./fm_count_kernels
 // TC_FM_COUNT_HOST_CHECK compiles fm_occ, fm_occ2 and fm_count_lane -- the loop of fm_count_kernel -- as plain C++.  Every
-// index is built naively here (suffixes sorted directly, the rank lines written in the 448-bit line format bit by bit, the
+// index is built naively (suffixes sorted directly, the rank lines written in the 448-bit line format bit by bit, the
 // pair table as fm_c2_kernel makes it) with the vectors in heap blocks of exactly sigma * lines * 64 bytes, so a read one
 // word outside either of them stops the run.  Patterns lie in an 8-byte aligned block padded to 8: the loop reads aligned
 // 8-byte words.  What it walks:
@@ -16,27 +16,11 @@
 // On those the answer is the one the contents define: a naive loop here with the same rule -- an interval is stepped from
 // or reported only when 1 <= s <= e <= N -- whose every line read is checked against the vector's size.  The program
 // asserts that the damages were reached: some changed an answer, some were cut to 0 by the rule.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
 
 #define TC_FM_COUNT_HOST_CHECK
 #include "tc_fm_count.hpp"
+#include "check_common.hpp"   // EXPECT, the blocks, the naive suffix array and the texts
 
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-typedef std::vector<u8> Bytes;
 static const u32 PAIR_SIGMA = 5;   // FM_PAIR_SIGMA of tc_fm_host.hpp
 
 struct Index {
@@ -76,13 +60,7 @@ static void scan_lines(u64 *vec, u64 lines, u32 nvec) {     // word 0 = ones bef
 static void build_index(Index &ix, const Bytes &text) {
     ix.text = text;
     const u64 n = ix.n = text.size(), N = ix.N = n + 1;
-    ix.sa.resize(N);
-    for (u32 i = 0; i < N; i++) ix.sa[i] = i;
-    std::sort(ix.sa.begin(), ix.sa.end(), [&](u32 x, u32 y) {   // the empty suffix first: a proper prefix sorts first
-        const size_t lx = n - x, ly = n - y;
-        const int c = memcmp(text.data() + x, text.data() + y, std::min(lx, ly));
-        return c ? c < 0 : lx < ly;
-    });
+    ix.sa = sort_suffixes(text);
     u32 counts[256] = {};
     for (u8 b : text) counts[b]++;
     u32 sig = 0, acc = 1;                                       // fm_make_tab
@@ -99,9 +77,9 @@ static void build_index(Index &ix, const Bytes &text) {
     for (u32 c = sig; c < 256; c++) ix.tab[256 + c] = ix.tab[512 + c] = 0;
     ix.sigma = sig;
     ix.lines = N / FM_LINE_BITS + 1;
-    ix.bits.reset(new u64[ix.words(false)]());
+    ix.bits = block<u64>(ix.words(false), 0);
     ix.pairs = sig <= PAIR_SIGMA && n >= 2;
-    if (ix.pairs) ix.bits2.reset(new u64[ix.words(true)]());
+    if (ix.pairs) ix.bits2 = block<u64>(ix.words(true), 0);
     for (u64 j = 0; j < N; j++) {
         const u32 p = ix.sa[j];
         if (p == 0) {
@@ -186,7 +164,7 @@ struct Patterns {
         u64 total = 0;
         offs.assign(1, 0);
         for (const Bytes &p : list) offs.push_back(total += p.size());
-        blk.reset(new u64[total / 8 + 1]());
+        blk = block<u64>(total / 8 + 1, 0);
         u8 *d = reinterpret_cast<u8 *>(blk.get());
         for (size_t i = 0; i < list.size(); i++)
             if (!list[i].empty()) memcpy(d + offs[i], list[i].data(), list[i].size());
@@ -307,12 +285,6 @@ static void damages(Index &ix, const Patterns &P, std::mt19937 &rng, Tally *V2, 
     }
 }
 
-static Bytes random_text(std::mt19937 &rng, u64 n, const std::string &alphabet) {
-    Bytes t(n);
-    for (u8 &b : t) b = alphabet.empty() ? (u8)(rng() & 255) : (u8)alphabet[rng() % alphabet.size()];
-    return t;
-}
-
 int main() {
     std::mt19937 rng(20250214);
     Tally V2, V3, V4;
@@ -320,7 +292,7 @@ int main() {
     for (u64 n : {446u, 447u, 448u, 1342u, 1343u, 1344u})
         for (const char *alphabet : {"ACGTN", "ACGTNU", ""}) {
             Index ix;
-            build_index(ix, random_text(rng, n, alphabet));
+            build_index(ix, random_text(rng, n, *alphabet ? letters(alphabet, strlen(alphabet)) : byte_values(0, 256)));
             EXPECT(ix.lines == ix.N / FM_LINE_BITS + 1 && ix.pairs == (strlen(alphabet) == 5));
             Patterns P;
             make_patterns(P, ix.text, rng);

@@ -2,7 +2,7 @@
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -I text-compression_amd/csrc
 //       text-compression_amd/host/check/fm_ms_kernels.cpp -o fm_ms_kernels && ./fm_ms_kernels
 // TC_FM_MS_HOST_CHECK compiles the bodies of the kernels as plain C++: the HIP keywords defined away, a workgroup of one
-// lane, the lanes of a grid run one after another.  Every index is built naively here -- suffixes sorted directly, the
+// lane, the lanes of a grid run one after another.  Every index is built naively -- suffixes sorted directly, the
 // rank lines written in the 448-bit line format bit by bit, the LCP array by comparing neighbours, the min tree by
 // fm_lmin_kernel level over level at fan-outs 4 and 64 -- in heap blocks of exactly the size the library allocates, so a
 // read one element outside any of them stops the run.  What it walks:
@@ -17,65 +17,32 @@
 //   - the MEM kernels against the enumeration of all (i, l) that occur and are not contained in another.
 // It asserts that no pattern took more than 2 m + 1 turns of the inner loop, and that both searches climbed to every
 // level of a fan-out-4 tree at least once.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_fm_ms.hpp"
-
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-
-typedef std::vector<u8> Bytes;
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
 // ---- the min tree over an LCP array, by the library's kernel -------------------------------------------------------------
 struct Tree {
-    u32 N = 0, lf = 0, nlev = 0, words = 0;
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1];
-    std::unique_ptr<u32[]> lcp, lmin;
-    FmMsTree view() const {
-        FmMsTree T;
-        T.lcp = lcp.get(); T.lmin = lmin.get(); T.s_off = off; T.s_cnt = cnt; T.nlev = nlev; T.lf = lf;
-        return T;
-    }
+    u32 N = 0, lf = 0;
+    std::unique_ptr<u32[]> lcp;
+    MinTree min;
+    FmMsTree view() const { return min.view(lcp.get()); }
 };
 static void build_tree(Tree &t, const std::vector<u32> &lcp, u32 lf) {
     t.N = (u32)lcp.size();
     t.lf = lf;
-    t.nlev = fm_ms_tree_shape(t.N, lf, t.off, t.cnt, &t.words);
-    EXPECT(t.nlev >= 1 && t.cnt[t.nlev] <= (1u << lf) && t.cnt[0] == t.N);
-    t.lcp = block<u32>(t.N);
-    std::memcpy(t.lcp.get(), lcp.data(), (size_t)t.N * 4);
-    t.lmin = block<u32>(t.words);
-    const u32 *src = t.lcp.get();
-    for (u32 k = 1; k <= t.nlev; k++) {
-        u32 *dst = t.lmin.get() + t.off[k];
-        launch((t.cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, t.cnt[k - 1], lf, dst, t.cnt[k]); });
-        for (u32 j = 0; j < t.cnt[k]; j++) {        // every entry is the minimum of the rows below it
+    t.lcp = block_of(lcp);
+    t.min = min_tree_of(t.lcp.get(), t.N, lf);
+    EXPECT(t.min.nlev >= 1 && t.min.cnt[t.min.nlev] <= (1u << lf) && t.min.cnt[0] == t.N);
+    for (u32 k = 1; k <= t.min.nlev; k++) {
+        const u32 *dst = t.min.lmin.get() + t.min.off[k];
+        for (u32 j = 0; j < t.min.cnt[k]; j++) {    // every entry is the minimum of the rows below it
             const u64 span = 1ull << (lf * k);
             u32 m = 0xffffffffu;
             for (u64 r = j * span; r < (j + 1) * span && r < t.N; r++) m = std::min(m, lcp[r]);
             EXPECT(dst[j] == m);
         }
-        src = dst;
     }
 }
 
@@ -125,20 +92,9 @@ struct Index {
 static void build_index(Index &ix, const Bytes &text, u32 lf) {
     ix.text = text;
     const u32 n = ix.n = (u32)text.size(), N = ix.N = n + 1;
-    ix.sa.resize(N);
-    for (u32 i = 0; i < N; i++) ix.sa[i] = i;
-    std::sort(ix.sa.begin(), ix.sa.end(), [&](u32 x, u32 y) {     // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    ix.rank.resize(N);
-    for (u32 j = 0; j < N; j++) ix.rank[ix.sa[j]] = j;
-    ix.lcp.assign(N, 0);
-    for (u32 j = 1; j < N; j++) {
-        u32 x = ix.sa[j - 1], y = ix.sa[j], l = 0;
-        while (x + l < n && y + l < n && text[x + l] == text[y + l]) l++;
-        ix.lcp[j] = l;
-    }
+    ix.sa = sort_suffixes(text);
+    ix.rank = inverse_of(ix.sa);
+    ix.lcp = lcp_of(text, ix.sa);
     u32 counts[256] = {};
     for (u8 b : text) counts[b]++;
     ix.tab = block<u32>(768);                       // fm_make_tab of csrc/tc_fm_host.hpp
@@ -238,14 +194,14 @@ static void check_batch(const Index &ix, const std::vector<Bytes> &pats, bool sa
     const u32 *sa = sampled ? nullptr : ix.sa_blk.get();
     for (fm_ms_block = 0; fm_ms_block < npat; fm_ms_block++) {
         fm_ms_turns = 0;
-        fm_ms_kernel<true>(ix.bits.get(), ix.lines, ix.tab.get(), ix.N, ix.tree.lcp.get(), ix.tree.lmin.get(), ix.tree.lf, sa, fp,
+        fm_ms_kernel<true>(ix.bits.get(), ix.lines, ix.tab.get(), ix.N, ix.tree.lcp.get(), ix.tree.min.lmin.get(), ix.tree.lf, sa, fp,
                            d_offs.get(), npat, ms_len.get(), ms_pos.get(), ms_occ.get());
         const u64 m = pats[fm_ms_block].size();
         EXPECT(fm_ms_turns <= 2 * m + 1);
         if (m && fm_ms_turns * g_worst_turns_m > g_worst_turns_num * m) g_worst_turns_num = fm_ms_turns, g_worst_turns_m = m;
     }
     launch(npat, [&] {
-        fm_ms_kernel<false>(ix.bits.get(), ix.lines, ix.tab.get(), ix.N, ix.tree.lcp.get(), ix.tree.lmin.get(), ix.tree.lf, sa, fp,
+        fm_ms_kernel<false>(ix.bits.get(), ix.lines, ix.tab.get(), ix.N, ix.tree.lcp.get(), ix.tree.min.lmin.get(), ix.tree.lf, sa, fp,
                             d_offs.get(), npat, ms_len0.get(), nullptr, nullptr);
     });
     std::vector<u32> len, occ;
@@ -292,11 +248,6 @@ static void check_batch(const Index &ix, const std::vector<Bytes> &pats, bool sa
 }
 
 // ---- texts and patterns ------------------------------------------------------------------------------------------------
-static Bytes random_text(std::mt19937 &rng, u32 n, const Bytes &al) {
-    Bytes t(n);
-    for (u8 &b : t) b = al[rng() % al.size()];
-    return t;
-}
 static Bytes sub(std::mt19937 &rng, const Bytes &t, u32 m) {
     m = std::min<u32>(m, (u32)t.size());
     const u32 o = rng() % (t.size() - m + 1);
@@ -364,20 +315,8 @@ int main() {
         const u32 n = lf == 2 ? 1100 : 1300;
         std::vector<std::pair<Bytes, Bytes>> shapes;
         shapes.push_back({Bytes(n, 'A'), Bytes{'A'}});
-        {
-            Bytes t(n);
-            for (u32 i = 0; i < n; i++) t[i] = "ACG"[i % 3];
-            shapes.push_back({t, Bytes{'A', 'C', 'G'}});
-        }
-        {
-            std::string a = "A", b = "AB";
-            while (b.size() < n) {
-                const std::string c = b + a;
-                a = b;
-                b = c;
-            }
-            shapes.push_back({Bytes(b.begin(), b.begin() + n), Bytes{'A', 'B'}});
-        }
+        shapes.push_back({periodic(n, 3), Bytes{'A', 'C', 'G'}});
+        shapes.push_back({fibonacci(n), Bytes{'A', 'B'}});
         shapes.push_back({random_text(rng, n, Bytes{'A', 'B'}), Bytes{'A', 'B'}});
         for (auto &sh : shapes) {
             Index ix;

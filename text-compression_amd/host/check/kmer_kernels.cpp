@@ -13,29 +13,11 @@
 // NOT covered here, checked on the device only: km_load16's vector loads, km_block_excl_max and block_excl_sum (the
 // workgroup scans), km_tile_kernel's and km_carry_kernel's reductions, tc_scan64, the LDS and global atomics of the
 // spectrum and the profile, the ballot of the saturated bin.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
 
 #define TC_KM_HOST_CHECK
 #include "tc_kmer.hpp"
+#include "check_common.hpp"   // EXPECT, the blocks, the naive suffix array and the texts
 
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-typedef std::vector<u8> Bytes;
 struct Kmer {
     u32 row, pos, occ;
     bool operator==(const Kmer &o) const { return row == o.row && pos == o.pos && occ == o.occ; }
@@ -138,24 +120,9 @@ static void check_arrays(const u32 *sa, const u32 *lcp, u64 N, const std::vector
 // ---- the enhanced suffix array of a text, naively, in heap blocks of exactly N entries ------------------------------------
 static void check_text(const Bytes &text) {
     const u32 n = (u32)text.size(), N = n + 1;
-    std::vector<u32> order(N);
-    for (u32 i = 0; i < N; i++) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](u32 x, u32 y) {     // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    auto sa = block<u32>(N), lcp = block<u32>(N);
-    u32 maxl = 0;
-    for (u32 j = 0; j < N; j++) {
-        u32 l = 0;
-        if (j) {
-            const u32 a = order[j - 1], b = order[j];
-            while (a + l < n && b + l < n && text[a + l] == text[b + l]) l++;
-        }
-        sa[j] = order[j];
-        lcp[j] = l;
-        maxl = std::max(maxl, l);
-    }
+    const std::vector<u32> order = sort_suffixes(text), common = lcp_of(text, order);
+    auto sa = block_of(order), lcp = block_of(common);
+    const u32 maxl = *std::max_element(common.begin(), common.end());
     std::vector<u32> ks = {1, 2, 3, 5, 12, n, n + 1, 0xffffffffu};
     if (maxl) { ks.push_back(maxl); ks.push_back(maxl + 1); }
     ks.erase(std::remove(ks.begin(), ks.end(), 0u), ks.end());
@@ -168,25 +135,13 @@ static void check_text(const Bytes &text) {
     }
 }
 
-static Bytes periodic(u32 n, u32 p) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)('a' + i % p);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string x = "b", y = "a";
-    while (y.size() < n) { std::string z = y + x; x = y; y = z; }
-    return Bytes(y.begin(), y.begin() + n);
-}
-
 int main() {
     std::mt19937_64 rng(0x6b6d6572);
     const u32 lens[] = {1, 2, 3, 15, 16, 17, 31, 32, 33, 47, 48, 49, 255, 256, 257, 1000, 2199, 2200};
     u64 texts = 0;
     for (u32 n : lens) {
-        check_text(periodic(n, 1));
-        for (u32 p : {2u, 3u, 7u}) check_text(periodic(n, p));
-        check_text(fibonacci(n));
+        for (u32 p : {1u, 2u, 3u, 7u}) check_text(periodic(n, p, 0, "abcdefg"));     // (lower case here, as the random texts below)
+        check_text(fibonacci(n, 'a', 'b'));
         for (u32 sigma : {1u, 2u, 4u, 256u}) {
             Bytes t(n);
             for (u32 i = 0; i < n; i++) t[i] = (u8)(sigma == 256 ? rng() & 255 : 'a' + rng() % sigma);

@@ -1,8 +1,10 @@
 // Stand-alone host check of the LCP kernels (csrc/tc_lcp.hpp), meant to be built with a host sanitizer:
-//   clang++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-//           -I text-compression_amd/csrc text-compression_amd/host/check/lcp_kernels.cpp -o lcp_kernels && ./lcp_kernels
+//   g++ -O1 -g -std=c++17 -Wno-unknown-pragmas -fsanitize=address,undefined -fno-sanitize-recover=all -I text-compression_amd/csrc
+//       text-compression_amd/host/check/lcp_kernels.cpp -o lcp_kernels && ./lcp_kernels
+// (-Wno-unknown-pragmas: csrc/tc_lcp.hpp carries a "#pragma unroll" the host compiler does not know.)
 // TC_LCP_HOST_CHECK compiles the bodies of the kernels as plain C++: the HIP keywords defined away, a workgroup of one
-// lane, the workgroups of a grid run one after another in the launch order of lcp_device (csrc/tc_lcp_host.hpp).  The
+// lane, the workgroups of a grid run one after another in the launch order of lcp_device (csrc/tc_lcp_host.hpp): this
+// program keeps its own launch loop, which sets lcp_grid; EXPECT, the blocks and the reference come from check_common.hpp.  The
 // text, the suffix array and every scratch array are heap blocks of exactly the size the library carves, so a read or
 // write one element outside any of them stops the run.  What it walks:
 //   - a few hundred random small texts (alphabets 1, 2, 4, 256; lengths 1 .. 300; short caps 16, 32 and 256, so that the
@@ -17,24 +19,9 @@
 //   - the texts and arrays of tests/test_gpu_lcp_long.py (its part e: n = 1000 and 4097, the same generator): rows set
 //     to n + 1 and 0xffffffff in row 0, the middle and the last row, a value twice, row 0's value repeated, the reversed
 //     and a shuffled permutation -- walked here before the device sees them.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <vector>
-
 #define TC_LCP_HOST_CHECK
 #include "tc_lcp.hpp"
-
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
+#include "check_common.hpp"   // EXPECT, the blocks, the naive suffix array and the texts
 
 template <class F>
 static void launch(u32 grid, F &&kernel) {
@@ -43,18 +30,13 @@ static void launch(u32 grid, F &&kernel) {
 }
 static u32 cdiv(u64 a, u64 b) { return (u32)((a + b - 1) / b); }
 
-// heap blocks of the exact size: the sanitizer sees the first byte outside
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-
 // the launch sequence of lcp_device; returns the error word
 static u32 run_lcp(const std::vector<u8> &text, const std::vector<u32> &sa_in, u32 cap, u64 list_cap, std::vector<u32> &lcp_out) {
     const u32 n = (u32)text.size();
     const u64 N = (u64)n + 1;
-    auto t = block<u8>(n);
-    if (n) std::memcpy(t.get(), text.data(), n);
-    auto sa = block<u32>(N);
-    std::memcpy(sa.get(), sa_in.data(), N * 4);
+    EXPECT(sa_in.size() == N);
+    auto t = block_of(text);
+    auto sa = block_of(sa_in);
     const u32 ntiles = cdiv(N, LCP_SCAN_TILE);
     // exactly N words: the scan's full-tile path must not pass N
     auto v = block<u32>(N);
@@ -83,18 +65,8 @@ static u64 list_cap_of(u64 n, u32 cap) {   // lcp_list_cap of csrc/tc_lcp_host.h
 }
 
 static void reference(const std::vector<u8> &text, std::vector<u32> &sa, std::vector<u32> &lcp) {
-    const u32 n = (u32)text.size();
-    sa.resize(n + 1);
-    for (u32 i = 0; i <= n; i++) sa[i] = i;
-    std::sort(sa.begin(), sa.end(), [&](u32 a, u32 b) {
-        return std::lexicographical_compare(text.begin() + a, text.end(), text.begin() + b, text.end());
-    });
-    lcp.assign(n + 1, 0);
-    for (u32 j = 1; j <= n; j++) {
-        u32 a = sa[j - 1], b = sa[j], l = 0;
-        while (a + l < n && b + l < n && text[a + l] == text[b + l]) l++;
-        lcp[j] = l;
-    }
+    sa = sort_suffixes(text);
+    lcp = lcp_of(text, sa);
 }
 
 static void check_bounds(const std::vector<u32> &sa, const std::vector<u32> &lcp, u32 n) {

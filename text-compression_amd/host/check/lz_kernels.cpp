@@ -3,7 +3,7 @@
 //       text-compression_amd/host/check/lz_kernels.cpp -o lz_kernels && ./lz_kernels
 // TC_FM_MS_HOST_CHECK compiles the bodies as plain C++, as host/check/fm_ms_kernels.cpp does for the row searches that
 // the LPF kernel calls: the HIP keywords defined away, a workgroup of one lane, the lanes of a grid run one after another.
-// Everything is built naively here -- suffixes sorted directly, the LCP array by comparing neighbours, the two min trees
+// Everything is built naively -- suffixes sorted directly, the LCP array by comparing neighbours, the two min trees
 // (over the suffix array and over the LCP array) by fm_lmin_kernel level over level at fan-outs 4 and 64 -- in heap blocks
 // of exactly the size the library allocates, so a read one element outside any of them stops the run.  What it walks:
 //   - lz_range_min alone, on arrays no text has (all large, ascending, sparse small values, random), against a running
@@ -14,60 +14,23 @@
 //     Fibonacci and random texts over 1, 2, 4 and 256 letters, with n on both sides of a tree group.
 // It asserts that the range minimum climbed to every level of a fan-out-4 tree of 4096 rows at least once.  The tile
 // kernels of the parse and the rounds of the inverse need barriers between lanes: they are checked on the device only.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_lz.hpp"
-
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-
-typedef std::vector<u8> Bytes;
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
 // ---- a min tree over any u32 array, by the library's kernel ------------------------------------------------------------
 struct Tree {
-    u32 N = 0, lf = 0, nlev = 0, words = 0;
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1];
-    std::unique_ptr<u32[]> base, lmin;
-    FmMsTree view() const {
-        FmMsTree T;
-        T.lcp = base.get(); T.lmin = lmin.get(); T.s_off = off; T.s_cnt = cnt; T.nlev = nlev; T.lf = lf;
-        return T;
-    }
+    u32 N = 0;
+    std::unique_ptr<u32[]> base;
+    MinTree min;
+    FmMsTree view() const { return min.view(base.get()); }
 };
 static void build_tree(Tree &t, const std::vector<u32> &a, u32 lf) {
     t.N = (u32)a.size();
-    t.lf = lf;
-    t.nlev = fm_ms_tree_shape(t.N, lf, t.off, t.cnt, &t.words);
-    EXPECT(t.nlev >= 1 && t.cnt[t.nlev] <= (1u << lf) && t.cnt[0] == t.N);
-    t.base = block<u32>(t.N);
-    std::memcpy(t.base.get(), a.data(), (size_t)t.N * 4);
-    t.lmin = block<u32>(t.words);
-    const u32 *src = t.base.get();
-    for (u32 k = 1; k <= t.nlev; k++) {
-        u32 *dst = t.lmin.get() + t.off[k];
-        launch((t.cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, t.cnt[k - 1], lf, dst, t.cnt[k]); });
-        src = dst;
-    }
+    t.base = block_of(a);
+    t.min = min_tree_of(t.base.get(), t.N, lf);
+    EXPECT(t.min.nlev >= 1 && t.min.cnt[t.min.nlev] <= (1u << lf) && t.min.cnt[0] == t.N);
 }
 
 // ---- 1: the range minimum alone ----------------------------------------------------------------------------------------
@@ -115,13 +78,8 @@ static void range_minima(std::mt19937 &rng) {
 static u64 g_texts = 0, g_positions = 0;
 static void check_lpf(const Bytes &text, u32 lf) {
     const u32 n = (u32)text.size(), N = n + 1;
-    std::vector<u32> sa(N), rank(N), lcp(N, 0);
-    for (u32 i = 0; i < N; i++) sa[i] = i;
-    std::sort(sa.begin(), sa.end(), [&](u32 x, u32 y) {     // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    for (u32 j = 0; j < N; j++) rank[sa[j]] = j;
+    const std::vector<u32> sa = sort_suffixes(text), rank = inverse_of(sa);
+    std::vector<u32> lcp(N, 0);
     // all pairwise common prefixes: cp[i][j] = lcp(i, j), from the end of the text
     std::vector<std::vector<u32>> cp(N, std::vector<u32>(N, 0));
     for (u32 i = n; i-- > 0;)
@@ -132,7 +90,7 @@ static void check_lpf(const Bytes &text, u32 lf) {
     build_tree(tl, lcp, lf);
     auto pack = block<u64>(n);
     for (u32 i = 0; i < n; i++) pack[i] = ~0ull;
-    launch(n, [&] { lz_lpf_kernel(ts.base.get(), tl.base.get(), ts.lmin.get(), tl.lmin.get(), N, lf, pack.get()); });
+    launch(n, [&] { lz_lpf_kernel(ts.base.get(), tl.base.get(), ts.min.lmin.get(), tl.min.lmin.get(), N, lf, pack.get()); });
     for (u32 i = 0; i < n; i++) {
         u32 best = 0, lo = N, hi = N;               // the maximum over all j < i; the two neighbours among them
         for (u32 j = 0; j < i; j++) {
@@ -148,26 +106,6 @@ static void check_lpf(const Bytes &text, u32 lf) {
     }
     g_texts++;
     g_positions += n;
-}
-
-static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
-    Bytes t(n);
-    for (u8 &b : t) b = sigma == 256 ? (u8)rng() : (u8)("ACGT"[rng() % sigma]);
-    return t;
-}
-static Bytes periodic(u32 n, u32 p) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string a = "A", b = "AB";
-    while (b.size() < n) {
-        const std::string c = b + a;
-        a = b;
-        b = c;
-    }
-    return Bytes(b.begin(), b.begin() + n);
 }
 
 int main() {

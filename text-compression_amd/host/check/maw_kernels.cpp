@@ -3,7 +3,7 @@
 //       text-compression_amd/host/check/maw_kernels.cpp -o maw_kernels && ./maw_kernels
 // TC_FM_MS_HOST_CHECK compiles maw_row_body (both set widths), maw_range_or and the two row searches of csrc/tc_fm_ms.hpp
 // as plain C++, as host/check/rep_kernels.cpp does for the repeats: the HIP keywords defined away, the lanes run one after
-// another.  Everything is built naively here -- suffixes sorted directly, the LCP array by comparing neighbours, the last
+// another.  Everything is built naively -- suffixes sorted directly, the LCP array by comparing neighbours, the last
 // column from the text, the change counts by a running sum, the min tree by fm_lmin_kernel and the OR tree by plain loops,
 // level over level at fan-outs 4 and 64 -- in heap blocks of exactly the entries the library's arrays hold, so a read one
 // element outside any of them stops the run.  Every row's words, in order, under several length windows, are compared with
@@ -14,35 +14,12 @@
 // Fibonacci, random over 1, 2, 4, 64, 65 and 256 letters, a text followed by its copy, lengths 1 .. 2200 (and one of 2600,
 // the shortest at which a range OR climbs to the top of a five-level tree), each of the 256 bytes once.  The tree build and
 // the kernel around the body need a workgroup: they are checked on the device only.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
 #include <set>
-#include <string>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_maw.hpp"
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-
-typedef std::vector<u8> Bytes;
 struct Word {
     u32 a, pos, len;
     bool operator==(const Word &o) const { return a == o.a && pos == o.pos && len == o.len; }
@@ -60,25 +37,15 @@ struct Esa {
 };
 static void build_esa(Esa &e, const Bytes &text) {
     const u32 n = e.n = (u32)text.size(), N = e.N = n + 1;
-    e.sa = block<u32>(N);
-    for (u32 i = 0; i < N; i++) e.sa[i] = i;
-    std::sort(e.sa.get(), e.sa.get() + N, [&](u32 x, u32 y) {   // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    e.lcp = block<u32>(N);
+    const std::vector<u32> sa = sort_suffixes(text);
+    e.sa = block_of(sa);
+    e.lcp = block_of(lcp_of(text, sa));
     e.L = block<u8>(N);
     e.chg = block<u64>(N);
     e.left.assign(N, -1);
     for (u8 b : text) e.alpha[b >> 6] |= 1ull << (b & 63);
     for (u32 i = 0; i < 4; i++) e.sigma += (u32)__builtin_popcountll(e.alpha[i]);
     for (u32 j = 0; j < N; j++) {
-        u32 l = 0;
-        if (j) {
-            const u32 a = e.sa[j - 1], b = e.sa[j];
-            while (a + l < n && b + l < n && text[a + l] == text[b + l]) l++;
-        }
-        e.lcp[j] = l;
         if (e.sa[j] == 0) e.primary = j;
         e.left[j] = e.sa[j] ? (int)text[e.sa[j] - 1] : -1;
         e.L[j] = e.sa[j] ? text[e.sa[j] - 1] : (u8)0;             // the sentinel slot holds byte 0, as sa_build writes it
@@ -172,22 +139,15 @@ static void check_text(const Bytes &text, u32 lf) {
     Esa e;
     build_esa(e, text);
     const u32 N = e.N;
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1], words;
-    const u32 nlev = fm_ms_tree_shape(N, lf, off, cnt, &words);
-    auto lmin = block<u32>(words);
-    const u32 *src = e.lcp.get();
-    for (u32 k = 1; k <= nlev; k++) {
-        u32 *dst = lmin.get() + off[k];
-        launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], lf, dst, cnt[k]); });
-        src = dst;
-    }
+    const MinTree tree = min_tree_of(e.lcp.get(), N, lf);
+    const u32 *off = tree.off, *lmin = tree.lmin.get();
+    const u32 nlev = tree.nlev, words = tree.words;
     u8 code_of[256] = {}, byte_of[64] = {};
     for (u32 v = 0; v < 256; v++) {
         code_of[v] = (u8)maw_code_of(e.alpha, v);
         if (e.alpha[v >> 6] >> (v & 63) & 1) byte_of[code_of[v] & 63] = (u8)v;
     }
-    FmMsTree T;
-    T.lcp = e.lcp.get(); T.lmin = lmin.get(); T.s_off = off; T.s_cnt = cnt; T.nlev = nlev; T.lf = lf;
+    const FmMsTree T = tree.view(e.lcp.get());
     const u32 windows[][2] = {{2, 0}, {2, 2}, {3, 0}, {3, 5}, {2, 16}, {20, 0}};
     for (int wide = e.sigma <= 64 ? 0 : 1; wide < 2; wide++) {     // (a small alphabet runs under both widths)
         // the OR tree by plain loops: level 1 from the left bytes, every further level from the one below
@@ -203,7 +163,7 @@ static void check_text(const Bytes &text, u32 lf) {
         O.L = e.L.get(); O.ortree = ortree.get(); O.s_off = off; O.s_code = code_of; O.N = N; O.lf = lf; O.primary = e.primary;
         for (const auto &w : windows) {
             MawArgs P;
-            P.lcp = e.lcp.get(); P.lmin = lmin.get(); P.sa = e.sa.get(); P.chg = e.chg.get(); P.L = e.L.get();
+            P.lcp = e.lcp.get(); P.lmin = lmin; P.sa = e.sa.get(); P.chg = e.chg.get(); P.L = e.L.get();
             P.ortree = ortree.get(); P.N = N; P.lf = lf; P.primary = e.primary; P.min_len = w[0]; P.max_len = w[1];
             for (u32 i = 0; i < 4; i++) P.alpha[i] = e.alpha[i];
             const std::vector<std::vector<Word>> want = by_stack_walk(e, w[0], w[1]);
@@ -230,24 +190,10 @@ static void check_text(const Bytes &text, u32 lf) {
     g_texts++;
 }
 
-static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
-    Bytes t(n);
-    for (u8 &b : t) b = sigma > 4 ? (u8)(rng() % sigma * (256 / sigma) + (sigma == 65 ? 0 : 1)) : (u8)("ACGT"[rng() % sigma]);
-    return t;
-}
-static Bytes periodic(u32 n, u32 p) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string a = "A", b = "AB";
-    while (b.size() < n) {
-        const std::string c = b + a;
-        a = b;
-        b = c;
-    }
-    return Bytes(b.begin(), b.begin() + n);
+// above four letters the codes are spread over the whole byte range, 256 / sigma apart, so that the wide sets have members
+// in all four words; sigma = 65 starts at byte 0
+static Bytes spread_text(std::mt19937 &rng, u32 n, u32 sigma) {
+    return random_text(rng, n, sigma > 4 ? byte_values(sigma == 65 ? 0 : 1, sigma, 256 / sigma) : letters("ACGT", sigma));
 }
 
 int main() {
@@ -257,7 +203,7 @@ int main() {
             check_text(Bytes(n, 'A'), lf);
             for (u32 p : {2u, 3u, 7u}) check_text(periodic(n, p), lf);
             check_text(fibonacci(n), lf);
-            for (u32 sigma : {1u, 2u, 4u, 64u, 65u, 256u}) check_text(random_text(rng, n, sigma), lf);
+            for (u32 sigma : {1u, 2u, 4u, 64u, 65u, 256u}) check_text(spread_text(rng, n, sigma), lf);
             if (n > 1100) continue;
             Bytes twice = random_text(rng, n, 4);   // a text followed by its own copy; a text whose last byte is new
             twice.insert(twice.end(), twice.begin(), twice.end());

@@ -6,19 +6,9 @@
 // For every table and every (capacity, batch) the two walks must give the same tiles -- base, valid, q, last -- in the
 // same order, the protocol around the cursor must hold (msd_dir_walk's `bad`), and the fills must be what the table
 // implies where that is easy to say.
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
 
 #include "tc_msd_dir.hpp"
-
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            return 1;                                                             \
-        }                                                                         \
-    } while (0)
+#include "check_common.hpp"   // EXPECT
 
 static const uint32_t TILE = 8192;
 

@@ -3,7 +3,7 @@
 //       text-compression_amd/host/check/pal_kernels.cpp -o pal_kernels && ./pal_kernels
 // TC_FM_MS_HOST_CHECK compiles pal_centre_kernel and the range minimum of csrc/tc_lz.hpp it calls as plain C++, as
 // host/check/tr_kernels.cpp does for the tandem-repeat kernel: the HIP keywords defined away, a workgroup of one lane, the
-// lanes of a grid run one after another.  Everything is built naively here -- the joint text S = text . sigma(reverse(text)),
+// lanes of a grid run one after another.  Everything is built naively -- the joint text S = text . sigma(reverse(text)),
 // its suffixes sorted directly, the LCP array by comparing neighbours, the inverse array by scatter, the min tree by
 // fm_lmin_kernel level over level at fan-outs 4 and 64 -- in heap blocks of exactly the entries the library's arrays hold,
 // so a read one element outside any of them stops the run.  Every centre's word, for the budgets 0, 1, 3 and 16 and under
@@ -14,34 +14,10 @@
 // clamp cut a range minimum and ended a direct compare, some lane used all m + 1 turns, some lane dropped a trailing
 // mismatch, and both the direct compare and the range minimum decided extensions.  The joint-text, count, fill and
 // longest kernels need a workgroup's scan or atomics: they are checked on the device only.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_pal.hpp"
-
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-
-typedef std::vector<u8> Bytes;
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
 // ---- isa, lcp and the LCP min tree of one text, naively, in blocks of the library's sizes --------------------------------
 struct Esa {
@@ -49,39 +25,10 @@ struct Esa {
     std::unique_ptr<u32[]> isa, lcp;
 };
 static void build_esa(Esa &e, const Bytes &text) {
-    const u32 n = (u32)text.size(), N = e.N = n + 1;
-    std::vector<u32> sa(N);
-    for (u32 i = 0; i < N; i++) sa[i] = i;
-    std::sort(sa.begin(), sa.end(), [&](u32 x, u32 y) {         // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    e.isa = block<u32>(N);
-    e.lcp = block<u32>(N);
-    for (u32 j = 0; j < N; j++) {
-        u32 l = 0;
-        if (j) {
-            const u32 a = sa[j - 1], b = sa[j];
-            while (a + l < n && b + l < n && text[a + l] == text[b + l]) l++;
-        }
-        e.lcp[j] = l;
-        e.isa[sa[j]] = j;
-    }
-}
-struct Tree {
-    u32 nlev = 0;
-    std::unique_ptr<u32[]> lmin;
-};
-static void build_tree(Tree &t, const u32 *level0, u32 N, u32 lf) {
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1], words;
-    t.nlev = fm_ms_tree_shape(N, lf, off, cnt, &words);
-    t.lmin = block<u32>(words);
-    const u32 *src = level0;
-    for (u32 k = 1; k <= t.nlev; k++) {
-        u32 *dst = t.lmin.get() + off[k];
-        launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], lf, dst, cnt[k]); });
-        src = dst;
-    }
+    const std::vector<u32> sa = sort_suffixes(text);
+    e.N = (u32)sa.size();
+    e.isa = block_of(inverse_of(sa));
+    e.lcp = block_of(lcp_of(text, sa));
 }
 
 static u8 g_sigma[2][256];      // [0: the identity, 1: the DNA complement]
@@ -109,8 +56,7 @@ static void check_text(const Bytes &text, u32 lf) {
         for (u32 k = 0; k < n; k++) S[k] = text[k], S[n + k] = sigma[text[n - 1 - k]];
         Esa E;
         build_esa(E, S);
-        Tree tl;
-        build_tree(tl, E.lcp.get(), N, lf);
+        const MinTree tl = min_tree_of(E.lcp.get(), N, lf);
         auto s_blk = block<u8>(n2);
         std::copy(S.begin(), S.end(), s_blk.get());
         auto word = block<u64>(n2 - 1);
@@ -134,25 +80,6 @@ static void check_text(const Bytes &text, u32 lf) {
     g_texts++;
 }
 
-static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
-    Bytes t(n);
-    for (u8 &b : t) b = sigma == 256 ? (u8)rng() : (u8)("ACGT"[rng() % sigma]);
-    return t;
-}
-static Bytes periodic(u32 n, u32 p) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string a = "A", b = "AB";
-    while (b.size() < n) {
-        const std::string c = b + a;
-        a = b;
-        b = c;
-    }
-    return Bytes(b.begin(), b.begin() + n);
-}
 // w . sigma(reverse(w)), with an odd length's middle byte between: the whole text is one palindrome
 static Bytes whole(std::mt19937 &rng, u32 n, const u8 *sigma) {
     Bytes t = random_text(rng, n, 4);

@@ -3,7 +3,7 @@
 //       text-compression_amd/host/check/rep_kernels.cpp -o rep_kernels && ./rep_kernels
 // TC_FM_MS_HOST_CHECK compiles rep_row_kernel and the two row searches of csrc/tc_fm_ms.hpp it calls as plain C++, as
 // host/check/lz_kernels.cpp does for the LPF kernel: the HIP keywords defined away, a workgroup of one lane, the lanes of a
-// grid run one after another.  Everything is built naively here -- suffixes sorted directly, the LCP array by comparing
+// grid run one after another.  Everything is built naively -- suffixes sorted directly, the LCP array by comparing
 // neighbours, the last column from the text, the change counts by a running sum, the min tree by fm_lmin_kernel level over
 // level at fan-outs 4 and 64 -- in heap blocks of exactly the rows the library's arrays hold, so a read one element outside
 // any of them stops the run.  Every row's packed word, for both kinds and several filters, is compared with what one stack
@@ -11,34 +11,10 @@
 // interval is booked at its representative row.  Texts: unary, periodic (2, 3, 7), Fibonacci, random over 1, 2, 4 and 256
 // letters, a text followed by its copy, lengths 1 .. 2200, and the two 257-occurrence texts of the device tests.  The
 // flag, count and fill kernels need a workgroup scan or a device scan: they are checked on the device only.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_rep.hpp"
-
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-
-typedef std::vector<u8> Bytes;
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
 // ---- the enhanced suffix array of a text, naively, in blocks of the library's sizes --------------------------------------
 struct Esa {
@@ -51,23 +27,12 @@ struct Esa {
 };
 static void build_esa(Esa &e, const Bytes &text) {
     const u32 n = e.n = (u32)text.size(), N = e.N = n + 1;
-    e.sa.resize(N);
-    for (u32 i = 0; i < N; i++) e.sa[i] = i;
-    std::sort(e.sa.begin(), e.sa.end(), [&](u32 x, u32 y) {     // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    e.lcp = block<u32>(N);
+    e.sa = sort_suffixes(text);
+    e.lcp = block_of(lcp_of(text, e.sa));
     e.L = block<u8>(N);
     e.chg = block<u64>(N);
     e.left.assign(N, -1);
     for (u32 j = 0; j < N; j++) {
-        u32 l = 0;
-        if (j) {
-            const u32 a = e.sa[j - 1], b = e.sa[j];
-            while (a + l < n && b + l < n && text[a + l] == text[b + l]) l++;
-        }
-        e.lcp[j] = l;
         if (e.sa[j] == 0) e.primary = j;
         e.left[j] = e.sa[j] ? (int)text[e.sa[j] - 1] : -1;
         e.L[j] = e.sa[j] ? text[e.sa[j] - 1] : (u8)0;             // the sentinel slot holds byte 0, as sa_build writes it
@@ -115,15 +80,7 @@ static void check_text(const Bytes &text, u32 lf) {
     Esa e;
     build_esa(e, text);
     const u32 N = e.N;
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1], words;
-    const u32 nlev = fm_ms_tree_shape(N, lf, off, cnt, &words);
-    auto lmin = block<u32>(words);
-    const u32 *src = e.lcp.get();
-    for (u32 k = 1; k <= nlev; k++) {
-        u32 *dst = lmin.get() + off[k];
-        launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], lf, dst, cnt[k]); });
-        src = dst;
-    }
+    const std::unique_ptr<u32[]> lmin = min_tree_of(e.lcp.get(), N, lf).lmin;
     auto pack = block<u64>(N);
     const u32 filters[][2] = {{1, 2}, {2, 2}, {1, 3}, {3, 4}, {20, 2}, {1, 257}, {1, 258}};
     for (int super = 0; super < 2; super++)
@@ -146,25 +103,6 @@ static void check_text(const Bytes &text, u32 lf) {
     g_texts++;
 }
 
-static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
-    Bytes t(n);
-    for (u8 &b : t) b = sigma == 256 ? (u8)rng() : (u8)("ACGT"[rng() % sigma]);
-    return t;
-}
-static Bytes periodic(u32 n, u32 p) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string a = "A", b = "AB";
-    while (b.size() < n) {
-        const std::string c = b + a;
-        a = b;
-        b = c;
-    }
-    return Bytes(b.begin(), b.begin() + n);
-}
 // w = 01 02 03, then (c, w) for c = 0 .. 255: 257 occurrences of w, every left context another one (Nothing among them).
 // doubled >= 0: the byte in front of the last w is `doubled`, so one left context occurs twice.
 static Bytes many_left(int doubled) {

@@ -6,18 +6,10 @@
 // chain in the first doubling round; one after a plain round that shed less than 1/256 of at least 2^20 members; its
 // second pass keeps h; a chain round that resolved less than an eighth makes the next attempt wait 2, then 4 plain
 // rounds, and after three such rounds there are none; TC_SA_CHAIN=2 ignores the back-off, 0 never chains.
-#include <cstdio>
 
 static int env_int(const char *, int dflt) { return dflt; }   // (the knobs at their defaults, whatever the environment)
 #include "tc_sa_plan.hpp"
-
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            return 1;                                                             \
-        }                                                                         \
-    } while (0)
+#include "check_common.hpp"   // EXPECT
 
 static const uint64_t N = 1ull << 24;
 

@@ -3,7 +3,8 @@
 //       text-compression_amd/host/check/sus_kernels.cpp -o sus_kernels && ./sus_kernels
 // TC_FM_MS_HOST_CHECK compiles sus_prefix_lane, sus_mark_lane and sus_point_lane, the range minimum of csrc/tc_lz.hpp and
 // the row search of csrc/tc_fm_ms.hpp as plain C++, as host/check/maw_kernels.cpp does for the absent words: the HIP keywords
-// defined away, the lanes run one after another.  Everything around them is built naively here -- suffixes sorted directly,
+// defined away, the lanes run one after another.  Everything around them is built naively, the suffix array, the LCP array and the
+// tree by check_common.hpp and check_esa.hpp -- suffixes sorted directly,
 // the LCP array by comparing neighbours, the two scans by running loops, the min tree by fm_lmin_kernel level over level at
 // fan-outs 4 and 64 -- in heap blocks of exactly the entries the library's arrays hold, so a read or a store one element
 // outside any of them stops the run.  Every up, every MUS and every point answer is compared with brute force: the longest
@@ -13,35 +14,12 @@
 // periodic (2, 3, 7), Fibonacci, random over 1, 2, 4 and 200 letters, a text followed by its copy, a long MUS with a short one
 // at its end (the leftmost search climbs to the top of the tree), and the staircase: many MUS over one position, the shortest
 // in the middle.  The kernels around the lanes need a workgroup: they are checked on the device only.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <map>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_sus.hpp"
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-
-typedef std::vector<u8> Bytes;
 struct Pair {
     u32 s, len;
     bool operator==(const Pair &o) const { return s == o.s && len == o.len; }
@@ -128,20 +106,8 @@ static u64 g_tie_left = 0, g_interior = 0, g_uncovered = 0, g_up0 = 0, g_first =
 static void check_text(const Bytes &text, u32 lf) {
     const u32 n = (u32)text.size(), N = n + 1;
     // the enhanced suffix array, naively
-    auto sa = block<u32>(N), lcp = block<u32>(N);
-    for (u32 i = 0; i < N; i++) sa[i] = i;
-    std::sort(sa.get(), sa.get() + N, [&](u32 x, u32 y) {       // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    for (u32 j = 0; j < N; j++) {
-        u32 l = 0;
-        if (j) {
-            const u32 a = sa[j - 1], b = sa[j];
-            while (a + l < n && b + l < n && text[a + l] == text[b + l]) l++;
-        }
-        lcp[j] = l;
-    }
+    const std::vector<u32> order = sort_suffixes(text);
+    auto sa = block_of(order), lcp = block_of(lcp_of(text, order));
     // up: one lane per row, every entry written exactly once
     auto up = block<u32>(n);
     for (u32 i = 0; i < n; i++) up[i] = 0xdeadbeefu;
@@ -170,17 +136,9 @@ static void check_text(const Bytes &text, u32 lf) {
     nxt[n] = n;
     for (u32 p = n; p-- > 0;) nxt[p] = mlen[p] != SUS_NONE ? p : nxt[p + 1];
     // the min tree over mlen
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1], words;
-    const u32 nlev = fm_ms_tree_shape(n, lf, off, cnt, &words);
-    auto lmin = block<u32>(words);
-    const u32 *src = mlen.get();
-    for (u32 k = 1; k <= nlev; k++) {
-        u32 *dst = lmin.get() + off[k];
-        launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], lf, dst, cnt[k]); });
-        src = dst;
-    }
-    FmMsTree T;
-    T.lcp = mlen.get(); T.lmin = lmin.get(); T.s_off = off; T.s_cnt = cnt; T.nlev = nlev; T.lf = lf;
+    const MinTree tree = min_tree_of(mlen.get(), n, lf);
+    const u32 nlev = tree.nlev;
+    const FmMsTree T = tree.view(mlen.get());
     // one lane per position
     const std::vector<Pair> want = brute_point(want_up);
     memset(lz_climbed, 0, sizeof lz_climbed);
@@ -231,25 +189,6 @@ static void check_text(const Bytes &text, u32 lf) {
     g_mus += mus.size();
 }
 
-static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
-    Bytes t(n);
-    for (u8 &b : t) b = sigma > 4 ? (u8)(rng() % sigma + 1) : (u8)("ACGT"[rng() % sigma]);
-    return t;
-}
-static Bytes periodic(u32 n, u32 p) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string a = "A", b = "AB";
-    while (b.size() < n) {
-        const std::string c = b + a;
-        a = b;
-        b = c;
-    }
-    return Bytes(b.begin(), b.begin() + n);
-}
 static void append(Bytes &t, const Bytes &x) { t.insert(t.end(), x.begin(), x.end()); }
 // a Y b . Y b q . a Y q: the MUS (0, |Y| + 2) and, at its last byte, the MUS b Y[0] of length 2 -- nothing starts between them
 static Bytes long_then_short(std::mt19937 &rng, u32 m) {

@@ -4,7 +4,7 @@
 //       text-compression_amd/host/check/tm_kernels.cpp -o tm_kernels && ./tm_kernels
 // TC_FM_MS_HOST_CHECK compiles the bodies as plain C++, as host/check/lz_kernels.cpp does for the range minimum and
 // host/check/fm_ms_kernels.cpp for the two row searches that the kernel calls: the HIP keywords defined away, a workgroup
-// of one lane, the lanes of a grid run one after another.  Everything is built naively here -- the suffixes of Q T sorted
+// of one lane, the lanes of a grid run one after another.  Everything is built naively -- the suffixes of Q T sorted
 // directly, the LCP array by comparing neighbours, the min tree by fm_lmin_kernel level over level at fan-outs 4 and 64,
 // the T-row counts and the two row lists by a loop -- in heap blocks of exactly the size the library uses, so a read or
 // write one element outside any of them stops the run.  tm_row_kernel, one lane per Q row, both instances, with ms_pos
@@ -15,46 +15,10 @@
 // whose nearest T row lies thousands of rows away.  The program asserts what no device test can see: the clamp to Q's end
 // fired, and at fan-out 4 both row searches climbed to every level of the tree (host/check/lz_kernels.cpp asserts the same of
 // the range minimum).
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <string>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_tm.hpp"
-
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-
-typedef std::vector<u8> Bytes;
-
-// the suffixes of t in order, the empty one first (a proper prefix sorts first)
-static std::vector<u32> sort_suffixes(const Bytes &t) {
-    const u32 n = (u32)t.size();
-    std::vector<u32> sa(n + 1);
-    for (u32 i = 0; i <= n; i++) sa[i] = i;
-    std::sort(sa.begin(), sa.end(), [&](u32 x, u32 y) {
-        const int c = std::memcmp(t.data() + x, t.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    return sa;
-}
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
 static u64 g_pairs = 0, g_positions = 0;
 static u32 g_max_levels = 0;
@@ -66,36 +30,17 @@ static void check_pair(const Bytes &Q, const Bytes &T, u32 lf) {
     std::vector<std::vector<u32>> cp(a + 1, std::vector<u32>(b + 1, 0));    // cp[i][j] = the common prefix of Q[i ..) and T[j ..)
     for (u32 i = a; i-- > 0;)
         for (u32 j = b; j-- > 0;) cp[i][j] = Q[i] == T[j] ? cp[i + 1][j + 1] + 1 : 0;
-    const std::vector<u32> tsa = sort_suffixes(T);
-    std::vector<u32> trank(b + 1);
-    for (u32 j = 0; j <= b; j++) trank[tsa[j]] = j;
+    const std::vector<u32> trank = inverse_of(sort_suffixes(T));
     // ---- the enhanced suffix array of Q T and what the library derives from it
     Bytes X(Q);
     X.insert(X.end(), T.begin(), T.end());
     const std::vector<u32> xsa = sort_suffixes(X);
-    auto sa = block<u32>(N), lcp = block<u32>(N);
-    for (u32 r = 0; r < N; r++) {
-        sa[r] = xsa[r];
-        u32 l = 0;
-        if (r) {
-            const u32 x = xsa[r - 1], y = xsa[r];
-            while (x + l < n && y + l < n && X[x + l] == X[y + l]) l++;
-        }
-        lcp[r] = l;
-    }
-    u32 off[FM_MS_MAXLEV + 1], cnt_lev[FM_MS_MAXLEV + 1], words;
-    const u32 nlev = fm_ms_tree_shape(N, lf, off, cnt_lev, &words);
-    EXPECT(nlev >= 1 && cnt_lev[nlev] <= (1u << lf) && cnt_lev[0] == N);
+    auto sa = block_of(xsa), lcp = block_of(lcp_of(X, xsa));
+    const MinTree tree = min_tree_of(lcp.get(), N, lf);
+    const u32 nlev = tree.nlev;
+    EXPECT(nlev >= 1 && tree.cnt[nlev] <= (1u << lf) && tree.cnt[0] == N);
     if (lf == 2 && nlev > g_max_levels) g_max_levels = nlev;
-    auto lmin = block<u32>(words);
-    {
-        const u32 *src = lcp.get();
-        for (u32 k = 1; k <= nlev; k++) {
-            u32 *dst = lmin.get() + off[k];
-            launch((cnt_lev[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt_lev[k - 1], lf, dst, cnt_lev[k]); });
-            src = dst;
-        }
-    }
+    const u32 *lmin = tree.lmin.get();
     auto cnt = block<u64>((size_t)N + 1);
     auto trow = block<u32>(b), qrow = block<u32>(a);
     u32 nt = 0, nq = 0;
@@ -110,10 +55,10 @@ static void check_pair(const Bytes &Q, const Bytes &T, u32 lf) {
     auto len1 = block<u32>(a), len0 = block<u32>(a), pos = block<u32>(a), occ = block<u32>(a), pos_only = block<u32>(a),
          occ_only = block<u32>(a);
     for (u32 i = 0; i < a; i++) len1[i] = len0[i] = pos[i] = occ[i] = pos_only[i] = occ_only[i] = 0xdeadbeefu;
-    launch(a, [&] { tm_row_kernel<true>(sa.get(), lcp.get(), lmin.get(), N, lf, cnt.get(), trow.get(), qrow.get(), a, b, TM_ALL, len1.get(), pos.get(), occ.get()); });
-    launch(a, [&] { tm_row_kernel<false>(sa.get(), lcp.get(), lmin.get(), N, lf, cnt.get(), trow.get(), qrow.get(), a, b, TM_ALL, len0.get(), nullptr, nullptr); });
-    launch(a, [&] { tm_row_kernel<true>(sa.get(), lcp.get(), lmin.get(), N, lf, cnt.get(), trow.get(), qrow.get(), a, b, TM_ALL, len0.get(), pos_only.get(), nullptr); });
-    launch(a, [&] { tm_row_kernel<true>(sa.get(), lcp.get(), lmin.get(), N, lf, cnt.get(), trow.get(), qrow.get(), a, b, TM_ALL, len0.get(), nullptr, occ_only.get()); });
+    launch(a, [&] { tm_row_kernel<true>(sa.get(), lcp.get(), lmin, N, lf, cnt.get(), trow.get(), qrow.get(), a, b, TM_ALL, len1.get(), pos.get(), occ.get()); });
+    launch(a, [&] { tm_row_kernel<false>(sa.get(), lcp.get(), lmin, N, lf, cnt.get(), trow.get(), qrow.get(), a, b, TM_ALL, len0.get(), nullptr, nullptr); });
+    launch(a, [&] { tm_row_kernel<true>(sa.get(), lcp.get(), lmin, N, lf, cnt.get(), trow.get(), qrow.get(), a, b, TM_ALL, len0.get(), pos_only.get(), nullptr); });
+    launch(a, [&] { tm_row_kernel<true>(sa.get(), lcp.get(), lmin, N, lf, cnt.get(), trow.get(), qrow.get(), a, b, TM_ALL, len0.get(), nullptr, occ_only.get()); });
     for (u32 i = 0; i < a; i++) {
         u32 best = 0, count = 0, at = 0;
         for (u32 j = 0; j < b; j++) best = std::max(best, cp[i][j]);
@@ -131,31 +76,11 @@ static void check_pair(const Bytes &Q, const Bytes &T, u32 lf) {
     for (u32 i : {0u, a / 2, a - 1}) {
         auto l1 = block<u32>(1), p1 = block<u32>(1), o1 = block<u32>(1);
         l1[0] = p1[0] = o1[0] = 0xdeadbeefu;
-        launch(a, [&] { tm_row_kernel<true>(sa.get(), lcp.get(), lmin.get(), N, lf, cnt.get(), trow.get(), qrow.get(), a, b, i, l1.get(), p1.get(), o1.get()); });
+        launch(a, [&] { tm_row_kernel<true>(sa.get(), lcp.get(), lmin, N, lf, cnt.get(), trow.get(), qrow.get(), a, b, i, l1.get(), p1.get(), o1.get()); });
         EXPECT(l1[0] == len1[i] && p1[0] == pos[i] && o1[0] == occ[i]);
     }
     g_pairs++;
     g_positions += a;
-}
-
-static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
-    Bytes t(n);
-    for (u8 &b : t) b = sigma == 256 ? (u8)rng() : (u8)("ACGT"[rng() % sigma]);
-    return t;
-}
-static Bytes periodic(u32 n, u32 p, u32 phase = 0) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[(i + phase) % p]);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string a = "A", b = "AB";
-    while (b.size() < n) {
-        const std::string c = b + a;
-        a = b;
-        b = c;
-    }
-    return Bytes(b.begin(), b.begin() + n);
 }
 
 int main() {

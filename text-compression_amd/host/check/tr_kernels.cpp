@@ -3,7 +3,7 @@
 //       text-compression_amd/host/check/tr_kernels.cpp -o tr_kernels && ./tr_kernels
 // TC_FM_MS_HOST_CHECK compiles tr_cand_kernel, the range minimum of csrc/tc_lz.hpp and the upward row search of
 // csrc/tc_fm_ms.hpp it calls as plain C++, as host/check/rep_kernels.cpp does for the repeats kernel: the HIP keywords
-// defined away, a workgroup of one lane, the lanes of a grid run one after another.  Everything is built naively here --
+// defined away, a workgroup of one lane, the lanes of a grid run one after another.  Everything is built naively --
 // the suffixes of the text and of its reverse sorted directly, the LCP arrays by comparing neighbours, the inverse arrays
 // by scatter, the min trees by fm_lmin_kernel level over level at fan-outs 4 and 64 -- in heap blocks of exactly the
 // entries the library's arrays hold, so a read one element outside any of them stops the run.  Every position's two
@@ -15,35 +15,11 @@
 // lengths 1 .. 2200, and 2600 for the last kind.  The program asserts that at fan-out 4 both searches and both range
 // minima reached every level of the tree, and reports the levels.  The scatter, count, fill
 // and order kernels need atomics or a device scan: they are checked on the device only.
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <random>
-#include <string>
 #include <tuple>
-#include <vector>
 
 #define TC_FM_MS_HOST_CHECK
 #include "tc_tr.hpp"
-
-#define EXPECT(cond)                                                              \
-    do {                                                                          \
-        if (!(cond)) {                                                            \
-            std::fprintf(stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #cond); \
-            std::exit(1);                                                         \
-        }                                                                         \
-    } while (0)
-
-template <class F>
-static void launch(u64 grid, F &&kernel) {
-    for (fm_ms_block = 0; fm_ms_block < grid; fm_ms_block++) kernel();
-}
-template <class T>
-static std::unique_ptr<T[]> block(size_t count) { return std::unique_ptr<T[]>(new T[count ? count : 1]); }
-
-typedef std::vector<u8> Bytes;
+#include "check_esa.hpp"      // launch, MinTree; EXPECT, the blocks, the naive suffix array and the texts (check_common.hpp)
 
 // ---- isa, lcp and the LCP min tree of one text, naively, in blocks of the library's sizes --------------------------------
 struct Esa {
@@ -51,39 +27,10 @@ struct Esa {
     std::unique_ptr<u32[]> isa, lcp;
 };
 static void build_esa(Esa &e, const Bytes &text) {
-    const u32 n = (u32)text.size(), N = e.N = n + 1;
-    std::vector<u32> sa(N);
-    for (u32 i = 0; i < N; i++) sa[i] = i;
-    std::sort(sa.begin(), sa.end(), [&](u32 x, u32 y) {         // the empty suffix first: a proper prefix sorts first
-        const int c = std::memcmp(text.data() + x, text.data() + y, std::min(n - x, n - y));
-        return c ? c < 0 : x > y;
-    });
-    e.isa = block<u32>(N);
-    e.lcp = block<u32>(N);
-    for (u32 j = 0; j < N; j++) {
-        u32 l = 0;
-        if (j) {
-            const u32 a = sa[j - 1], b = sa[j];
-            while (a + l < n && b + l < n && text[a + l] == text[b + l]) l++;
-        }
-        e.lcp[j] = l;
-        e.isa[sa[j]] = j;
-    }
-}
-struct Tree {
-    u32 nlev = 0;
-    std::unique_ptr<u32[]> lmin;
-};
-static void build_tree(Tree &t, const u32 *level0, u32 N, u32 lf) {
-    u32 off[FM_MS_MAXLEV + 1], cnt[FM_MS_MAXLEV + 1], words;
-    t.nlev = fm_ms_tree_shape(N, lf, off, cnt, &words);
-    t.lmin = block<u32>(words);
-    const u32 *src = level0;
-    for (u32 k = 1; k <= t.nlev; k++) {
-        u32 *dst = t.lmin.get() + off[k];
-        launch((cnt[k] + 3u) & ~3u, [&] { fm_lmin_kernel(src, cnt[k - 1], lf, dst, cnt[k]); });
-        src = dst;
-    }
+    const std::vector<u32> sa = sort_suffixes(text);
+    e.N = (u32)sa.size();
+    e.isa = block_of(inverse_of(sa));
+    e.lcp = block_of(lcp_of(text, sa));
 }
 
 // ---- the runs of the definition: for every period the maximal stretches of text[k] == text[k + p], at least p long,
@@ -132,11 +79,8 @@ static void check_text(const Bytes &text, u32 lf) {
     build_esa(R, Bytes(text.rbegin(), text.rend()));
     auto comp = block<u32>(N);
     for (u32 j = 0; j < N; j++) comp[j] = N - 1 - F.isa[j];
-    Tree ti, tc, tl, tr;
-    build_tree(ti, F.isa.get(), N, lf);
-    build_tree(tc, comp.get(), N, lf);
-    build_tree(tl, F.lcp.get(), N, lf);
-    build_tree(tr, R.lcp.get(), N, lf);
+    const MinTree ti = min_tree_of(F.isa.get(), N, lf), tc = min_tree_of(comp.get(), N, lf), tl = min_tree_of(F.lcp.get(), N, lf),
+                  tr = min_tree_of(R.lcp.get(), N, lf);
     auto text_blk = block<u8>(n);
     std::copy(text.begin(), text.end(), text_blk.get());
     auto c_start = block<u32>(2 * (size_t)n);
@@ -187,25 +131,6 @@ static void check_text(const Bytes &text, u32 lf) {
     g_texts++;
 }
 
-static Bytes random_text(std::mt19937 &rng, u32 n, u32 sigma) {
-    Bytes t(n);
-    for (u8 &b : t) b = sigma == 256 ? (u8)rng() : (u8)("ACGT"[rng() % sigma]);
-    return t;
-}
-static Bytes periodic(u32 n, u32 p) {
-    Bytes t(n);
-    for (u32 i = 0; i < n; i++) t[i] = (u8)("ACGTNXY"[i % p]);
-    return t;
-}
-static Bytes fibonacci(u32 n) {
-    std::string a = "A", b = "AB";
-    while (b.size() < n) {
-        const std::string c = b + a;
-        a = b;
-        b = c;
-    }
-    return Bytes(b.begin(), b.begin() + n);
-}
 // w x^k y z: the search from position 0 finds its first hit k + 1 positions away, whichever order needs it
 static Bytes far_hit(u32 n, const char *wxyz) {
     Bytes t(n, (u8)wxyz[1]);
